@@ -14,16 +14,28 @@ processes itself (children, before any GPU call); under torchrun it reads
 RANK / LOCAL_RANK / WORLD_SIZE.  Every rank steps its own 4096 envs (weak
 scaling: envs are independent, so the step has no data-path collective; a
 barrier and a max-over-ranks reduction bracket the timed region): "value".
-A second timed phase ("gather_to_root") repeats the steps with the
+With --full, a second timed phase ("gather_to_root") repeats the steps with the
 north star's per-step RCCL gather of every rank's packed outputs to rank 0,
 issued from the C ABI (MEV_GATHER_TO_ROOT) on a communication stream that
 overlaps the next step; --no-gather skips it.
 
 Prints ONE JSON line on rank 0, including "roofline" for the dominant kernel
 (k_step, the only kernel of a step; HBM fraction from HIP events on its stream,
-VALU-issue fraction from the committed SQ counter pass) and "cpu_baseline" (the
-pinned C restatement on every host core, with the reference's survey-container
-numbers quoted beside it).
+VALU-issue fraction from the committed SQ counter pass).
+
+A plain run does only what the headline figure needs: set up, settle the clock,
+warm up, time the steps, write the outputs (--dump-outputs DIR) and print the
+line.  --full adds what takes runs of its own: the "gather_to_root" phase above
+and "cpu_baseline" (the pinned C restatement on every host core, with the
+reference's survey-container numbers quoted beside it).  --config 5, whose value
+IS the gathered rate, runs the gather phase with or without --full.
+
+--dump-outputs DIR: after the timed steps, the arrays the last timed step wrote
+(obs, reward, done, status, ...: what a caller of the step receives) as
+DIR/<name>.npy in float32 (rank r > 0: DIR/<name>.rank<r>.npy).  The envs, seeds
+and actions depend only on the arguments, so two builds can be compared output
+for output.  Above 64 MB in all, a fixed seeded sample of the envs is written
+(DIR/env_index.npy holds the sampled env numbers).
 """
 from __future__ import annotations
 
@@ -143,6 +155,34 @@ def valu_roofline(kernel_ms: float, envs: int):
     return {"achieved": round(achieved, 2), "peak": VALU_PEAK_G, "unit": "G wave-instr/s",
             "frac": round(achieved / VALU_PEAK_G, 4), "SQ_INSTS_VALU_per_launch": inst,
             "source": "profiles/valu_counters.json (rocprofv3 --pmc pass of this bench) / live kernel_ms"}
+
+
+DUMP_BUDGET_BYTES = 64 * 1000 * 1000  # --dump-outputs writes at most this much in all
+
+
+def dump_outputs(directory: str, out: dict, rank: int = 0, budget: int = DUMP_BUDGET_BYTES):
+    """Write the step outputs `out` (name -> device tensor whose first axis is the env) as
+    float32 .npy files.  u8 flags and i32 counters are exact in float32 (steps <= 2^24).  If the
+    arrays exceed `budget` bytes as float32, the same seeded sample of envs is kept of each."""
+    import numpy as np
+
+    os.makedirs(directory, exist_ok=True)
+    arrs = {k: v.detach().cpu().numpy() for k, v in out.items()}
+    E = next(iter(arrs.values())).shape[0]
+    per_env = sum(4 * (a.size // E) for a in arrs.values()) + 4  # (+ the env_index entry)
+    budget -= 256 * (len(arrs) + 1)  # (the .npy headers)
+    pick = None
+    if per_env * E > budget:
+        n = max(1, budget // per_env)
+        pick = np.sort(np.random.default_rng(20240607).choice(E, size=n, replace=False))
+    suffix = "" if rank == 0 else f".rank{rank}"
+    for k, a in arrs.items():
+        assert a.shape[0] == E, (k, a.shape)
+        if pick is not None:
+            a = a[pick]
+        np.save(os.path.join(directory, f"{k}{suffix}.npy"), np.ascontiguousarray(a, dtype=np.float32))
+    if pick is not None:
+        np.save(os.path.join(directory, f"env_index{suffix}.npy"), pick.astype(np.float32))
 
 
 class stdout_to_stderr:
@@ -286,8 +326,15 @@ def main():
                          "8 GPUs = 4096 per GPU, value = the steps WITH the per-step RCCL gather of every rank's "
                          "outputs to rank 0)")
     ap.add_argument("--rays", type=int, default=0, help="LiDAR beams (default: 64 for config 3, 128 for config 5)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the second timed phase (every step's "
+                         "outputs gathered to rank 0 over RCCL, then verified) and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the outputs of the last timed step as DIR/<name>.npy "
+                         "(float32; above 64 MB in all a fixed seeded sample of the envs)")
     ap.add_argument("--no-gather", action="store_true",
-                    help="skip the second timed phase (every step's outputs gathered to rank 0 over RCCL)")
+                    help="with --full: skip the second timed phase (every step's outputs gathered to rank 0 over "
+                         "RCCL)")
     ap.add_argument("--gather-timeout", type=float, default=120.0, help="seconds before a stuck gather is aborted")
     ap.add_argument("--gather-format", choices=("state", "u8", "f32"), default="state",
                     help="packed gather rows (all lossless): state = each agent's post-step state + one LiDAR code "
@@ -303,7 +350,7 @@ def main():
                          "times need them")
     ap.add_argument("--no-kernel-events", action="store_true", help="never record per-kernel HIP events")
     ap.add_argument("--event-every", type=int, default=50, help="record the per-kernel events on every n-th step")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--step-kernel", type=int, default=0,
                     help="0 automatic (fused k_step at this size), 1 k_cars + k_lidar, 2 fused")
     ap.add_argument("--dry-run", action="store_true",
@@ -424,11 +471,13 @@ def main():
     # sanity: outputs are finite and the sim advanced
     last = outs[(W + K - 1) & 1]
     assert torch.isfinite(last["obs"]).all().item(), "non-finite observations"
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last, rank)
 
     # ---- phase 2: the same steps with every step's outputs gathered to rank 0 (RCCL, xGMI)
     gather = None
     comm_stuck = [False]  # a rank whose RCCL init never returned: exit without tearing the handle down
-    if not args.no_gather:
+    if (args.full or args.config == 5) and not args.no_gather:
         gather = {}
         try:
             if world > 1:
@@ -616,7 +665,7 @@ def main():
                                          f"outputs gathered to rank 0 ({args.gather_format} rows)")
             res["config"]["parallelism"] = (f"env-sharded x{world} (one process per GPU) + one RCCL gather of every "
                                             f"rank's packed outputs to rank 0 per step (value)")
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 res["cpu_baseline"] = cpu_baseline()
             except Exception as exc:  # never let the baseline kill the bench line

@@ -335,8 +335,10 @@ int mev_set_env_deal(mev_handle* h, int32_t on);
  * step launched).  A server slot belongs to the handle that took it -- across its
  * server's idle exits and paused stretches -- until the handle is closed, turns
  * serving off, moves to another stream, or has made no host-mode step for 50 ms
- * when another handle asks for a slot; so a round-robin over more small handles
- * than slots serves the first two to step, whatever the timing of idle exits.
+ * (and none since the previous step, or the creation, of the asking handle) when
+ * another handle asks for a slot; so a round-robin over more small handles than
+ * slots serves the first two to step, whatever the timing of idle exits or of
+ * pauses of the host between steps.
  * While it is resident, every device-wide wait of the process
  * (hipDeviceSynchronize, torch.cuda.synchronize(), frees that wait for the
  * device) waits for its idle exit, so the idle limit is adaptive: 8 x the

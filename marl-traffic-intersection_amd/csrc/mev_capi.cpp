@@ -218,6 +218,13 @@ struct mev_handle {
     // steady-clock ns of the handle's last host-mode step (serve_slot: a slot's owner
     // that has made no host step for kServeStaleMs may lose it to another handle)
     std::atomic<int64_t> serve_last_ns{0};
+    // the same in host steps of the whole process (g_host_tick): serve_last_tick is the
+    // handle's last host-mode step, serve_mark the one before it (at first, the handle's
+    // creation).  An owner that has stepped since another handle's mark keeps its slot
+    // from that handle whatever the clock says: a pause of the whole process (a descheduled
+    // or collecting host) between two steps of a round-robin makes nobody stale
+    std::atomic<uint64_t> serve_last_tick{0};
+    uint64_t serve_mark = 0;
     // the server's own stream: non-blocking, at the highest priority, whose hardware
     // queues are not the ones normal-priority streams share (GPU_MAX_HW_QUEUES of them):
     // a resident kernel holds back whatever another stream queues behind it on its queue
@@ -245,6 +252,7 @@ extern "C" {
 static int serve_stop(mev_handle* h);  // with mev_step: the resident step server leaves the stream
 namespace {
 void serve_unlist(mev_handle* h);  // (with mev_step) the handle leaves the resident-server list
+std::atomic<uint64_t> g_host_tick{0};  // host-mode steps of small handles in this process (mev_handle::serve_mark)
 
 // SimParams::beam_cull: the LiDAR's per-box beam culling models the offsets as
 // rel[b] = rel[0] + b*d (to 1e-5 rad, the slack its 2e-4 rad margin covers) with d > 0 and
@@ -528,6 +536,7 @@ int mev_create(const mev_config* cfg, mev_handle** out) {
         *out = nullptr;
         return fail(rc, m);
     }
+    h->serve_mark = g_host_tick.load(std::memory_order_relaxed);
     *out = h;
     return MEV_OK;
 }
@@ -1096,9 +1105,10 @@ int serve_launch(mev_handle* h) {
 // few, and a server launched behind another one's on a shared queue would wait for its
 // idle exit.  Handles beyond the cap step launched (same results).  A slot belongs to
 // the handle that took it -- across its server's idle exits and paused stretches --
-// until the handle is closed, or has made no host step for kServeStaleMs when another
-// handle asks for a slot: which handles are served does not depend on the timing of
-// idle exits (a round-robin over more handles than slots serves the first ones).
+// until the handle is closed, or has made no host step for kServeStaleMs, and none since
+// the previous step (or the creation) of another handle that asks for a slot: which
+// handles are served does not depend on the timing of idle exits or on pauses of the
+// host (a round-robin over more handles than slots serves the first ones).
 constexpr int kMaxResidentServers = 2;
 constexpr int64_t kServeStaleMs = 50;
 std::mutex g_serve_mu;
@@ -1119,8 +1129,9 @@ bool serve_resident(const mev_handle* h) {
 }
 
 // h may keep or start a resident server: it owns a slot, or takes a free one (or
-// one whose owner has stepped no host step for kServeStaleMs and has no server left)
-bool serve_slot(mev_handle* h) {
+// one whose owner has stepped no host step for kServeStaleMs, none since h's step
+// before this one -- `mark` -- and has no server left)
+bool serve_slot(mev_handle* h, uint64_t mark) {
     std::lock_guard<std::mutex> lk(g_serve_mu);
     for (const mev_handle* x : g_serving)
         if (x == h) return true;
@@ -1128,7 +1139,8 @@ bool serve_slot(mev_handle* h) {
         const int64_t t = now_ns();
         for (size_t i = 0; i < g_serving.size(); ++i) {
             const mev_handle* x = g_serving[i];
-            if (!serve_resident(x) && t - x->serve_last_ns.load(std::memory_order_relaxed) > kServeStaleMs * 1000000) {
+            if (!serve_resident(x) && x->serve_last_tick.load(std::memory_order_relaxed) <= mark &&
+                t - x->serve_last_ns.load(std::memory_order_relaxed) > kServeStaleMs * 1000000) {
                 g_serving.erase(g_serving.begin() + long(i));
                 break;
             }
@@ -1299,8 +1311,13 @@ int mev_step(mev_handle* h, const mev_step_args* a) {
     in.auto_reset = (a->flags & MEV_AUTO_RESET) ? 1 : 0;
     in.rng_counter = h->rng_counter++;
     const bool pinned = !dev && !gather && pin_ready(h);  // zero-copy host mode (small handles)
-    if (pinned) h->serve_last_ns.store(now_ns(), std::memory_order_relaxed);  // (a slot owner keeps stepping)
-    const bool serve = pinned && serve_wanted(h) && serve_slot(h);  // ... answered by the resident step server
+    const uint64_t mark = h->serve_mark;
+    if (pinned) {  // (a slot owner keeps stepping)
+        h->serve_last_ns.store(now_ns(), std::memory_order_relaxed);
+        h->serve_mark = g_host_tick.fetch_add(1, std::memory_order_relaxed) + 1;
+        h->serve_last_tick.store(h->serve_mark, std::memory_order_relaxed);
+    }
+    const bool serve = pinned && serve_wanted(h) && serve_slot(h, mark);  // ... answered by the resident step server
     if (!serve)
         if (int r = serve_stop(h)) return r;
     if (dev) {

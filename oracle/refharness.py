@@ -2,8 +2,7 @@
 
 The library is the UNMODIFIED reference simulator (cpp/*.cpp of the reference,
 built in place by oracle/build_ref.sh) plus oracle/ref_harness.cpp.  The build
-lives outside the repository (default /tmp/marl_ref_build), so it never travels
-to the GPU box.  Only
+lives in a directory git ignores (default oracle/_ref): never part of a commit.  Only
 tests/golden/gen_golden.py and bench.py's ``cpu_baseline`` leg use it.
 """
 from __future__ import annotations
@@ -15,7 +14,7 @@ from typing import Sequence
 import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-REF_BUILD = os.environ.get("MEV_REF_BUILD", "/tmp/marl_ref_build")
+REF_BUILD = os.environ.get("MEV_REF_BUILD", os.path.join(HERE, "_ref"))
 LIB_PATH = os.path.join(REF_BUILD, "libref_harness.so")
 
 NF = 15  # float fields per car record (see ref_harness.cpp car_to_rec)

@@ -6,7 +6,7 @@ import tempfile
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(ROOT, "marl-traffic-intersection_amd", "csrc")
-OUT = os.path.join(tempfile.gettempdir(), "mev_native_tests")
+OUT = os.path.join(tempfile.gettempdir(), f"mev_native_tests_{os.getuid()}")  # (one per user: /tmp is shared)
 
 
 def build(name: str, c_sources=()) -> str:

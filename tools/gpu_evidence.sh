@@ -34,9 +34,9 @@ if [ "$what" = bench ] || [ "$what" = all ]; then
       python3 bench.py --no-kernel-events --no-cpu-baseline --no-gather > $OUT/prof_bench.log 2>&1
   find $OUT/prof -name '*kernel_stats.csv' -exec cp {} $OUT/kernel_stats.csv \;
   cut -c1-200 $OUT/kernel_stats.csv
-  timeout -k 10 300 python bench.py > $OUT/bench.json 2> $OUT/bench.err
+  timeout -k 10 300 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
   cat $OUT/bench.json
-  timeout -k 10 300 python bench.py --kernel-events --no-cpu-baseline > $OUT/bench_events.json 2>> $OUT/bench.err
+  timeout -k 10 300 python bench.py --full --kernel-events --no-cpu-baseline > $OUT/bench_events.json 2>> $OUT/bench.err
 fi
 if [ "$what" = sweep ] || [ "$what" = all ]; then
   timeout -k 10 300 python tools/bench_sweep.py --out $OUT/sweep.json > $OUT/sweep.txt 2>&1
