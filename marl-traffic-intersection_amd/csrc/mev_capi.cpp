@@ -617,7 +617,7 @@ int mev_configure_traffic(mev_handle* h, int32_t enabled, float density) {
     if (enabled && h->sp.step_kernel == 2) {
         mev::SimParams q = h->sp;
         q.traffic = 1;
-        if (mev::step_kernel_for(q) == 0)
+        if (mev::plan_step(q).path == 0)
             return fail(MEV_E_INVALID, "the fused step kernel (mev_set_step_kernel 2) cannot hold this handle's NPC slots");
     }
     h->cfg.traffic_flow = enabled;
@@ -1187,7 +1187,7 @@ static bool serve_wanted(mev_handle* h) {
     static const bool off = [] { const char* v = getenv("MEV_NO_SERVE"); return v && v[0] == '1'; }();
     // (only on the handle's own non-blocking stream: a resident server would hold back
     // whatever a caller queues behind it on a stream it shares)
-    if (off || h->serve_mode == 0 || !h->tev.empty() || h->stream != h->own_stream || !mev::serve_fits(h->sp))
+    if (off || h->serve_mode == 0 || !h->tev.empty() || h->stream != h->own_stream || !mev::plan_step(h->sp).serve_fits)
         return false;
     if (h->serve_pause > 0) {  // repeated idle exits between posts: launched steps for a while
         --h->serve_pause;
@@ -1383,7 +1383,7 @@ int mev_step(mev_handle* h, const mev_step_args* a) {
         h->sp_valid = true;
     }
     // the NPC-aware deal (fused traffic k_step only; mev_set_env_deal)
-    const bool deal = !serve && h->sp.traffic && h->sp.deal_cnt && h->deal_on && mev::step_kernel_for(h->sp) == 2;
+    const bool deal = !serve && h->sp.traffic && h->sp.deal_cnt && h->deal_on && mev::plan_step(h->sp).path == 2;
     // classes are NPC-slot counts the next step loads (mev_kernels.hip cars_pre): rings whose
     // ended envs were put in class 0 by an auto-resetting step are not a bound for a step
     // without the reset (the env keeps its NPCs), so such a step deals afresh
@@ -1648,7 +1648,7 @@ int mev_set_step_kernel(mev_handle* h, int32_t kernel) {
     if (kernel < 0 || kernel > 2) return fail(MEV_E_INVALID, "step kernel must be 0 (auto), 1 (two kernels) or 2 (fused)");
     mev::SimParams q = h->sp;
     q.step_kernel = kernel;
-    if (mev::step_kernel_for(q) == 0)
+    if (mev::plan_step(q).path == 0)
         return fail(MEV_E_INVALID, "the fused step kernel does not support this configuration (traffic mode or too much LDS)");
     HIP_TRY(hipSetDevice(h->cfg.device));
     if (int r_ = serve_stop(h)) return r_;  // (the server holds the stream)
@@ -1659,7 +1659,7 @@ int mev_set_step_kernel(mev_handle* h, int32_t kernel) {
 
 int mev_get_step_kernel(const mev_handle* h, int32_t* kernel) {
     if (!h || !kernel) return fail(MEV_E_INVALID, "null argument");
-    *kernel = mev::step_kernel_for(h->sp);
+    *kernel = mev::plan_step(h->sp).path;
     return MEV_OK;
 }
 
@@ -1676,7 +1676,7 @@ int mev_set_step_pack(mev_handle* h, int32_t envs_per_wave) {
 
 int mev_get_step_pack(const mev_handle* h, int32_t* envs_per_wave) {
     if (!h || !envs_per_wave) return fail(MEV_E_INVALID, "null argument");
-    *envs_per_wave = mev::step_kernel_for(h->sp) == 2 ? mev::step_pack(h->sp) : 1;
+    *envs_per_wave = mev::plan_step(h->sp).pack;
     return MEV_OK;
 }
 
@@ -1702,8 +1702,7 @@ int mev_set_env_deal(mev_handle* h, int32_t on) {
 
 int mev_get_step_split(const mev_handle* h, int32_t* split) {
     if (!h || !split) return fail(MEV_E_INVALID, "null argument");
-    const bool fused = mev::step_kernel_for(h->sp) == 2;
-    *split = fused && mev::step_esplit(h->sp) ? 2 : (fused && mev::step_split(h->sp) ? 1 : 0);
+    *split = mev::plan_step(h->sp).split;
     return MEV_OK;
 }
 

@@ -17,6 +17,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "mev_plan.h"
+
 namespace mev {
 
 // The 4-byte fields of each SoA live in ONE allocation, field k at base +
@@ -183,16 +185,12 @@ struct StepInputs {
     int32_t deal_ring;
 };
 
-// The kernels launch_step will use for p: 1 = k_cars + k_lidar, 2 = the fused
-// k_step (one wave per env); 0 when p.step_kernel == 2 but k_step cannot run p
-// (traffic mode, or a pool that does not fit a wave's LDS budget).
-int step_kernel_for(const SimParams& p);
-// envs per k_step wave the fused path uses for p (1, 2 or 4)
-int step_pack(const SimParams& p);
-// whether the fused path runs two waves per workgroup (car part / LiDAR overlap)
-bool step_split(const SimParams& p);
-bool step_esplit(const SimParams& p);
-int esplit_pack(const SimParams& p);
+// The kernels launch_step and launch_serve use for p, their launches and what the
+// getters report: plan_step (mev_plan.h) of p's shape.
+inline StepShape step_shape(const SimParams& p) {
+    return {p.E, p.N, p.R, p.K, p.lidar_slots, p.traffic, p.dims, p.step_kernel, p.step_pack, p.step_split};
+}
+inline StepPlan plan_step(const SimParams& p) { return plan_step(step_shape(p)); }
 // ev (nullable): three events recorded before k_cars, between k_cars and k_lidar, after k_lidar
 // (with k_step: before it, and twice after it)
 // dp: a device copy of p (k_step reads its parameters through it)
@@ -210,7 +208,6 @@ hipError_t launch_observe_reset_lidar(const SimParams& p, const Outputs& out, hi
 // and answers a sid it has served before with nothing.  STOP writes only cmd and
 // seq.  Every workgroup publishes exited[b] = its instance's epoch when it leaves
 // (STOP, or no posting for ServeArgs::idle_ticks).
-constexpr int kServeMaxWG = 64;
 constexpr int kServeLine = 9;  // words of the command line
 constexpr uint32_t kServeStep = 1, kServeStop = 2;
 struct ServeBox {
@@ -229,8 +226,7 @@ struct ServeArgs {
     uint32_t epoch;
     uint32_t idle_ticks;         // 100 MHz ticks
 };
-// whether the handle's step can run as k_serve (fused, one workgroup per env, <= 64 envs)
-bool serve_fits(const SimParams& p);
+// (only where plan_step(p).serve_fits)
 hipError_t launch_serve(const SimParams& p, const SimParams* dp, const ServeArgs& sa, const Outputs& out,
                         hipStream_t s);
 

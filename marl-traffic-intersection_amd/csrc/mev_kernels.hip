@@ -21,8 +21,6 @@
 
 namespace mev {
 
-constexpr int WAVE = 64;
-
 // Diagnostic builds only, never compiled into the product library:
 //  -DMEV_STAMPS: per-env phase timestamps (s_memtime) into SimParams::debug[e*8 + k]
 //   (tools/phase_profile.py);
@@ -70,8 +68,6 @@ __shared__ unsigned long long mev_qst[8 * 8];  // (per wave of the workgroup)
 #ifndef QSTAMP
 #define QSTAMP(k) do {} while (0)
 #endif
-constexpr int MAXN = 64;
-constexpr int MAXK = 64;
 
 // k_step's issue priorities (s_setprio), falling as a wave's remaining work
 // shrinks: the four waves of a SIMD start together and the hardware otherwise
@@ -322,43 +318,6 @@ struct EgoLDS {
     uint8_t colnpc[MAXN];
 };
 
-// capacity KM NPC slots (k_cars / k_reset: MAXK; the fused k_step: the smallest
-// of 32 / 64 that holds the handle's max_npcs, so that the NPC arrays leave room
-// in the wave's LDS for a LiDAR pool).  DIMS: with each NPC's length / width (last).
-template <int KM, bool DIMS = false>
-struct NpcLDST {
-    static constexpr bool kDims = DIMS;
-    static constexpr int kCap = KM;
-    float x[KM], y[KM], v[KM], h[KM], c[KM], s[KM], acc[KM], steer[KM];
-    int32_t pidx[KM], route[KM], intent[KM];
-    uint8_t alive[KM];
-    union {
-        struct {  // the car corners (collision phase, after the controller)
-            float cx[KM][4], cy[KM][4];
-        };
-        struct {  // the controller's round-A states (npc_phase part 2), dead once committed
-            float xn[KM], yn[KM], vn[KM], hn[KM], accn[KM], steern[KM], cn[KM], sn[KM];
-            float mdcn[KM];  // the round-A state's distance to the centre
-        };
-    };
-    unsigned long long col[KM];
-    // the controller's parallel rounds: throttles of round A / B, ghost-scan candidates
-    // (others that passed the filters) and which of them k must yield to, new path index
-    float thr_a[KM], thr_b[KM];
-    unsigned long long em[KM], ym[KM];      // this round's filtered others / yields (scans)
-    unsigned long long em_a[KM], ym_a[KM];  // round A's
-    float mc_a[KM];                         // round A's conflict distance (< 0: none)
-    int32_t pidxn[KM];
-    // the controller's per-NPC terms that depend on its own start-of-step state only
-    int32_t pidx0[KM];          // after the first update_path_index of its turn
-    float nsteer[KM], ntan[KM];  // Car::update's new steering angle and its tangent
-    float accb[KM], mdc[KM];  // cruise throttle, distance to the centre
-    float endx[KM], endy[KM];  // the route's last point (arrival test)
-    // Per-NPC length / width (Car::length / Car::width), after every other array: only in
-    // the kernels that can run a handle with per-car sizes (k_cars, k_reset, k_step<NM =
-    // 0>); zero-length elsewhere, so the compile-time layouts keep their size
-    float len[DIMS ? KM : 0], wid[DIMS ? KM : 0];
-};
 using NpcLDS = NpcLDST<MAXK, true>;
 
 // the size of NPC k (the reference's constant 54 x 24 px unless the handle has cars of
@@ -1449,8 +1408,6 @@ __device__ __forceinline__ void obs_exact_pass(const SimParams& p, unsigned long
 // Dynamic LDS of k_cars, carved for the handle's N egos and K NPC slots.
 // s_waitcnt vmcnt(0) (gfx9 encoding: expcnt and lgkmcnt left at their maximum)
 constexpr int kWaitVmcnt0 = 0x0F70;
-// LDS path windows of the car part's first pass (k_step, no traffic): 4 x 1 KB + 1 KB
-constexpr int kWinBytes = 5 * 1024;
 
 struct CarsLDS {
     float *x, *y, *v, *h, *c, *s, *acc, *steer, *prev_dist, *pa0, *pa1;
@@ -1475,18 +1432,6 @@ struct CarsLDS {
     // dims handles only (null otherwise): each ego's length / width (Car::length / width)
     float *len, *wid;
 };
-
-__host__ __device__ constexpr size_t lds_al(size_t b) { return (b + 15) & ~size_t(15); }
-
-// NPC slots that need obstacle entries in k_cars' LDS (none without traffic)
-__host__ __device__ inline int cars_k(const SimParams& p) { return p.traffic ? p.K : 0; }
-
-// dims: the handle has cars of other sizes (two more per-ego arrays at the end)
-__host__ __device__ constexpr size_t cars_lds_bytes(int N, int K, bool dims = false) {
-    const size_t n = (size_t)N, ob = (size_t)(N + K);
-    return 22 * lds_al(n * 4) + 2 * lds_al(n * 16) + 3 * lds_al(n * 4) + 4 * lds_al(n) + lds_al(n * 8) +
-           lds_al(ob * 16) + 3 * lds_al(ob * 4) + lds_al(n * 16) + (dims ? 2 * lds_al(n * 4) : 0);
-}
 
 __device__ inline CarsLDS carve_cars_lds(unsigned char* base, int N, int K, bool dims = false) {
     const size_t n = (size_t)N, ob = (size_t)(N + K);
@@ -2581,37 +2526,6 @@ constexpr int kMarchHelp = 16;
 constexpr int kNptHelp = 3;
 static_assert(kMarchHelp <= 32, "helper groups have at least 2 lanes");
 
-struct LidarLayout {
-    int ag, dir, res, seg_jo, seg_rg, seg_bx, queue, scr, bytes;
-};
-
-__host__ __device__ inline int lidar_cand_max(const SimParams& p) { return p.N - 1 + (p.traffic ? p.K : 0); }
-
-// with_bx: a per-segment copy of the obstacle box (k_lidar, whose boxes are in
-// HBM); k_step reads them from its own LDS obstacle table instead.
-// beams: capacity of the beam arrays (>= G * R).
-__host__ __device__ constexpr LidarLayout lidar_layout_beams(int G, int beams, int cmax, bool with_bx) {
-    LidarLayout L{};
-    const int C = G * cmax;
-    int off = 0;
-    L.ag = off; off += G * 16;
-    L.dir = off; off += beams * 8;
-    L.res = off; off += beams * 4;
-    off = (off + 15) & ~15;
-    L.seg_rg = off; off += C * 16;
-    L.seg_bx = off; off += with_bx ? C * 16 : 0;
-    L.seg_jo = off; off += C * 4;
-    L.queue = L.seg_rg;
-    if (off < L.queue + beams * 2) off = L.queue + beams * 2;
-    off = (off + 15) & ~15;
-    L.scr = off; off += WAVE * 4;  // the car phase's segment lookup (3c)
-    L.bytes = (off + 15) & ~15;
-    return L;
-}
-__host__ __device__ inline LidarLayout lidar_layout(int G, int R, int cmax, bool with_bx = true) {
-    return lidar_layout_beams(G, G * R, cmax, with_bx);
-}
-
 int lidar_group(int R) {
     // ~256 beams per wave pool: G = 4 agents at R = 64 (measured best of 1..16, tools/kernel_time.py)
     int g = 256 / (R > 0 ? R : 1);
@@ -3284,72 +3198,12 @@ __global__ __launch_bounds__(256, 8) void k_lidar(SimParams p, Outputs out, int 
 }
 
 
-// Agents per LiDAR pool in k_step: the env's N agents in the fewest pools of at
-// most 512 beams, balanced (all N in one pool at config 3; 8 x 96 beams as 4 + 4
-// agents, 384 beams each, not 5 + 3: each pool's march ends on its longest beams,
-// and 4 agents of 96 beams fill six whole 64-lane chunks in phase 1).
-__host__ __device__ constexpr int step_pool_n(int N, int R) {
-    int g = 512 / (R > 0 ? R : 1);
-    g = g < 1 ? 1 : g;
-    if (g >= N) return N;
-    const int pools = (N + g - 1) / g;
-    return (N + pools - 1) / pools;
-}
-__host__ __device__ inline int step_pool(const SimParams& p) { return step_pool_n(p.N, p.R); }
-
-// LDS of one k_step wave: cars LDS, the staged heads [N][31], the beam offsets
-// [R], the env flags [8], then the LiDAR pool of step_pool(p) agents.
-struct StepLayout {
-    int head, rel, envw, lidar, bytes;
-};
-__host__ __device__ inline StepLayout step_layout(const SimParams& p) {
-    StepLayout L;
-    int off = (int)lds_al(cars_lds_bytes(p.N, cars_k(p), true));  // (k_step<NM = 0> keeps the car sizes)
-    L.head = off;  // (no staged heads: the car part writes its rows' heads itself)
-    L.rel = off; off += (int)lds_al((size_t)p.R * 4);
-    L.envw = off; off += 32;
-    L.lidar = off; off += lidar_layout(step_pool(p), p.R, lidar_cand_max(p), false).bytes;
-    L.bytes = off;
-    return L;
-}
-
-// Compile-time LDS geometry (NM > 0): every array sized for its capacity --
-// N <= NM agents, R <= kFixedRays beams per agent, one LiDAR pool of <= 512
-// beams, no NPCs -- so each LDS address is a constant offset from the wave's
-// base instead of a runtime pointer held in an SGPR.  The ~40 runtime LDS
-// pointers of the NM = 0 layout made k_step spill 131 SGPRs into VGPR lanes
-// (a v_readlane per reload).
-constexpr int kFixedRays = 128;
-constexpr int kPoolBeams = 512;
-template <int NM, int KM = 0>
-struct FixedLayout {
-    static_assert(NM >= 1 && NM <= 64, "agents per env");
-    static constexpr int beams = NM * kFixedRays < kPoolBeams ? NM * kFixedRays : kPoolBeams;
-    static constexpr int cars = (int)lds_al(cars_lds_bytes(NM, KM));
-    static constexpr int rel = cars;
-    static constexpr int envw = rel + kFixedRays * 4;
-    static constexpr int lidar = envw + 32;
-    static constexpr LidarLayout lay = lidar_layout_beams(NM, beams, NM - 1 + KM, false);
-    static constexpr int bytes = lidar + lay.bytes;
-};
 template <int NM, int KM>
 __host__ __device__ inline StepLayout step_layout_t(const SimParams& p) {
     if constexpr (NM == 0) return step_layout(p);
     else return StepLayout{FixedLayout<NM, KM>::rel, FixedLayout<NM, KM>::rel, FixedLayout<NM, KM>::envw,
                            FixedLayout<NM, KM>::lidar, FixedLayout<NM, KM>::bytes};
 }
-// the handle's shape fits the compile-time layout of NM agents and (traffic) KM
-// NPC slots within a wave's 10 KB LDS share, the NPC arrays included
-template <int NM, int KM>
-__host__ __device__ inline bool fixed_fits(const SimParams& p) {
-    // R <= 128 puts every pool (step_pool agents) within the layout's beams
-    const bool npcs = KM == 0 ? !p.traffic : (p.traffic && p.K <= KM);
-    const size_t npc_lds = KM == 0 ? 0 : sizeof(NpcLDST<(KM ? KM : 1)>);
-    // (a handle with cars of other sizes runs the runtime layout, NM = 0)
-    return p.N <= NM && p.R <= kFixedRays && npcs && !p.dims &&
-           (size_t)FixedLayout<NM, KM>::bytes + npc_lds <= 10 * 1024;
-}
-
 // agents per phase-1 pass in k_step (independent dependency chains interleaved;
 // 3 or 4 raise register pressure and lose); 1 in the early split's LiDAR wave
 // (8 waves per SIMD)
@@ -3420,15 +3274,6 @@ __device__ __forceinline__ void deal_append(const SimParams& p, const StepInputs
 // workgroup).
 constexpr int kSplitWpe = 4;
 constexpr int kEsplitWpe = 8;
-// the traffic early split: kTsplitEnvs envs (car waves) + one LiDAR wave per workgroup,
-// kTsplitWpe waves per SIMD (config 4: 4096 envs -> 6144 waves on 1024 SIMDs).  Two envs,
-// not four: the LiDAR wave's march of its egos' beams, which the light envs' car waves wait
-// for at barrier H, halves -- config 4 148.4 -> 150.8 M, 1024 / 2048 / 3072 envs 2-4 %
-// faster (profiles/r6_ab_ts2_*.txt; variant builds ts2* via MEV_TSPLIT_ENVS)
-#ifndef MEV_TSPLIT_ENVS
-#define MEV_TSPLIT_ENVS 2
-#endif
-constexpr int kTsplitEnvs = MEV_TSPLIT_ENVS;
 // the traffic early split's LiDAR wave issues at level 1 (its ego phase 1 and road march
 // have slack beside a heavy env's NPC phase, which sets the kernel's end): config 4
 // 143.4 -> 151.2 M against level 3 (profiles/r5_ab_tsprio*_cfg4.txt, four rounds; 2: 149 M,
@@ -3437,7 +3282,6 @@ constexpr int kTsplitEnvs = MEV_TSPLIT_ENVS;
 #define MEV_TSPLIT_LPRIO 1
 #endif
 constexpr int kPrioTsplitLidar = MEV_TSPLIT_LPRIO;
-constexpr int kTsplitRays = kFixedRays;  // LiDAR pool beams per env
 // (6: 2048 three-wave workgroups at 4096 envs, all resident at once.  With four envs per
 // workgroup a 5-wave budget (93 VGPRs) did not fit 4096 envs in one residency round --
 // five waves do not spread evenly over a CU's four SIMDs: 38.3 us against 28.7 us at 3072
@@ -3638,252 +3482,46 @@ static hipError_t launch_part(const SimParams& p, const StepInputs& in, const Ou
     return e;
 }
 
-// NPC slots of the fused kernel's LDS arrays (NpcLDST<KM>): the smallest
-// compiled capacity that holds the handle's max_npcs
-static int fused_npc_cap(const SimParams& p) { return p.K <= 32 ? 32 : 64; }
-
-// LDS of one k_step wave: the dynamic part (cars + one LiDAR pool of
-// step_pool(p) agents) plus, with traffic, the static NPC arrays
-static size_t fused_lds_bytes(const SimParams& p) {
-    size_t b = (size_t)step_layout(p).bytes;
-    // (the runtime-layout traffic kernels hold the NPC sizes too: NpcLDST<KM, true>)
-    if (p.traffic) b += fused_npc_cap(p) == 32 ? sizeof(NpcLDST<32, true>) : sizeof(NpcLDST<64, true>);
-    return b;
-}
-
-// k_step applies when its LDS fits one workgroup (64 KB); it is the automatic
-// choice when it also fits a wave's share at 4 waves per SIMD (128 VGPRs): a CU
-// holds 16 waves, so a wave may take 160 KB / 16 = 10 KB.
-static bool fused_fits(const SimParams& p) {
-    return fused_lds_bytes(p) <= 64 * 1024;
-}
-
-int step_kernel_for(const SimParams& p) {
-    const bool fusable = fused_fits(p);
-    if (p.step_kernel == 1) return 1;
-    if (p.step_kernel == 2) return fusable ? 2 : 0;
-    // auto: fused when a wave's LDS leaves 4 waves per SIMD and either the batch fills
-    // the chip with one wave per env (>= 4 per CU), or an env's beams fit one k_lidar
-    // group anyway (N * R <= 256: the second launch buys nothing, 1 env x 1 agent 70 ->
-    // 82 k steps/s fused), or the env fits the compile-time 8-slot layout: its k_step
-    // (two waves per env below 2048 workgroups, counts at compile time) beats the
-    // LiDAR's finer per-group waves at every batch size since round 6 (8 agents x 64
-    // beams: 64 envs 21.2 -> 16.7 us, 768 envs 27.2 -> 18.3 us; profiles/r6_stepk_small.txt).
-    // Larger envs at small batches keep the two-kernel path.
-    const bool small_env = p.N * p.R <= 256 || (!p.traffic && fixed_fits<8, 0>(p));
-    return (fusable && fused_lds_bytes(p) <= 10 * 1024 && (p.E >= 1024 || small_env)) ? 2 : 1;
-}
-
-// envs per k_step wave (1, 2 or 4) for a handle without traffic whose N agents
-// fit the 8-slot layout: several small envs share a wave's lanes, so one latency
-// chain serves them all.  p.step_pack (mev_set_step_pack) chooses; 0 = automatic.
-// Automatic: the most envs per wave that keeps >= 2048 waves (2 per SIMD) --
-// config 2 (4096 x 1 agent): 2 envs per wave, 177 -> 202 M agent-steps/s; 4
-// envs per wave (1024 waves, one per SIMD) 194 M (profiles/r2_pack_sweep.txt).
-int step_pack(const SimParams& p) {
-    if (p.traffic || !fixed_fits<8, 0>(p)) return 1;
-    if (step_esplit(p)) return esplit_pack(p);
-    int pk = p.step_pack;
-    if (pk != 1 && pk != 2 && pk != 4 && pk != 8) {
-        pk = 4;
-        while (pk > 1 && p.E / pk < 2048) pk /= 2;
-    }
-    while (pk > 1 && pk * p.N > 8) pk /= 2;
-    return pk;
-}
-
-// two waves per fused workgroup (k_step SPLIT) when that keeps <= 4 waves per SIMD
-// (<= 2048 workgroups; 256 CUs x 4 SIMDs)
-constexpr int kSplitMaxWg = 2048;
-// Envs per workgroup of the early split (k_step ESPLIT; 0: it does not apply).  An
-// explicit mev_set_step_pack is kept (reduced to <= 8 agent slots) when the slots'
-// beams fit one 512-beam LiDAR pool.  Automatic: 4 envs while their beams stay
-// <= 256 and >= 1024 workgroups remain, else 2 envs within one pool and >= 1024
-// workgroups, else 0 (the automatic choice then keeps one wave per env / the plain
-// split; mev_set_step_split(3) forces one env per workgroup at 8 waves per SIMD).
-// Measured against the plain split's best, one MI355X (profiles/r3_esplit_shapes.txt):
-// 4096 x 1 x 64 beams (config 2) 13.3 -> 11.6 us per step at 4 envs, 4096 x 4 x 64
-// 24.1 -> 22.0 at 2, 2048 x 1 x 64 12.4 -> 10.0 at 2, 4096 x 1 x 128 15.5 -> 14.4 at 2.
-int esplit_pack(const SimParams& p) {
-    // traffic: kTsplitEnvs one-ego envs per workgroup (every workgroup full, and the
-    // NPC-aware deal's lists of E / 8 envs split into whole workgroups).  Automatic at
-    // every such E: with two envs per workgroup it beats one wave per env from 16 to
-    // 16384 envs -- 16-512 envs 25-35 %, 8192 envs 145 -> 165 M, 16384 160 -> 190 M
-    // agent-steps/s (profiles/r6_ts2_auto_*.txt).  (Round 5's four envs per workgroup
-    // lost at 8192 envs, 55.9 -> 59.0 us, profiles/r5_ab_ts6_cfg4.txt.)
-    if (p.traffic)
-        return fixed_fits<1, 32>(p) && p.R <= kTsplitRays && p.E % (8 * kTsplitEnvs) == 0 &&
-                       (p.step_split == 3 || p.step_split == 0)
-                   ? kTsplitEnvs
-                   : 0;
-    if (!fixed_fits<8, 0>(p) || p.N > 8) return 0;
-    const int nr = p.N * p.R;
-    int pk = p.step_pack;
-    if (pk == 1 || pk == 2 || pk == 4 || pk == 8) {
-        while (pk > 1 && pk * p.N > 8) pk /= 2;
-        return pk * nr <= kPoolBeams ? pk : 0;
-    }
-    if (4 * p.N <= 8 && 4 * nr <= kPoolBeams / 2 && p.E / 4 >= 1024) return 4;
-    if (2 * p.N <= 8 && 2 * nr <= kPoolBeams && p.E / 2 >= 1024) return 2;
-    return p.step_split == 3 && nr <= kPoolBeams ? 1 : 0;
-}
-// the early split: automatic (mode 0) where esplit_pack finds >= 2 envs per
-// workgroup, or forced (mode 3)
-bool step_esplit(const SimParams& p) {
-    if (p.step_split == 1 || p.step_split == 2) return false;
-    const int pk = esplit_pack(p);
-    return p.step_split == 3 ? pk > 0 : pk >= 2;
-}
-bool step_split(const SimParams& p) {
-    if (p.traffic || !fixed_fits<8, 0>(p) || p.step_split == 1 || step_esplit(p)) return false;
-    if (p.step_split == 2) return true;
-    const int pk = step_pack(p);
-    return (p.E + pk - 1) / pk <= kSplitMaxWg;
-}
-
-// the beam count a k_step instantiation fixes at compile time (its P1): 64, 96 or 128
-// beams, every one in the observation; else 0
-static int fixed_r(const SimParams& p) {
-    return (p.R == 64 || p.R == 96 || p.R == 128) && p.lidar_slots == p.R ? p.R : 0;
-}
-
-template <bool TAB>
-static void launch_fused(const SimParams& p, const SimParams* dp, const StepInputs& in, const Outputs& out,
-                         hipStream_t s) {
-    if (p.traffic) {
-        if (fixed_fits<1, 32>(p)) {  // compile-time LDS layout (config 4: one ego, <= 32 NPC slots)
-            const unsigned lds = (unsigned)FixedLayout<1, 32>::bytes;  // + the static NpcLDST
-            if (step_esplit(p)) {  // the traffic early split: kTsplitEnvs car waves + a LiDAR wave
-                constexpr int P = kTsplitEnvs;
-                const unsigned tl = (unsigned)(P * FixedLayout<1, 32>::lidar + lidar_layout_beams(P, P * kTsplitRays, 32, false).bytes);
-                if (fixed_r(p) == 64)  // (config 4: the beam count at compile time)
-                    hipLaunchKernelGGL((k_step<true, TAB, 1, 32, P, true, true, 64>), dim3(p.E / P), dim3((P + 1) * WAVE), tl,
-                                       s, dp, in, out);
-                else
-                    hipLaunchKernelGGL((k_step<true, TAB, 1, 32, P, true, true>), dim3(p.E / P), dim3((P + 1) * WAVE), tl, s,
-                                       dp, in, out);
-                return;
-            }
-            hipLaunchKernelGGL((k_step<true, TAB, 1, 32>), dim3(p.E), dim3(WAVE), lds, s, dp, in, out);
-            return;
-        }
-        const unsigned lds = (unsigned)step_layout(p).bytes;  // + the static NpcLDST
-        if (fused_npc_cap(p) == 32) hipLaunchKernelGGL((k_step<true, TAB, 0, 32>), dim3(p.E), dim3(WAVE), lds, s, dp, in, out);
-        else hipLaunchKernelGGL((k_step<true, TAB, 0, 64>), dim3(p.E), dim3(WAVE), lds, s, dp, in, out);
-    } else if (fixed_fits<8, 0>(p)) {  // compile-time LDS layout
-        const unsigned lds = (unsigned)FixedLayout<8>::bytes;
-        const int pk = step_pack(p);
-        const int wg = (p.E + pk - 1) / pk;
-        const int fr = fixed_r(p);
-        if (step_esplit(p)) {  // early split: a car wave and a LiDAR wave per workgroup
-            if (pk == 8) hipLaunchKernelGGL((k_step<false, TAB, 8, MAXK, 8, true, true>), dim3(wg), dim3(2 * WAVE), lds, s, dp, in, out);
-            else if (pk == 4 && p.N == 1 && fr == 64)  // (config 2: agents per env and beams at compile time)
-                hipLaunchKernelGGL((k_step<false, TAB, 8, MAXK, 4, true, true, 64, 1>), dim3(wg), dim3(2 * WAVE), lds, s, dp, in, out);
-            else if (pk == 4 && p.N == 1)
-                hipLaunchKernelGGL((k_step<false, TAB, 8, MAXK, 4, true, true, 0, 1>), dim3(wg), dim3(2 * WAVE), lds, s, dp, in, out);
-            else if (pk == 4) hipLaunchKernelGGL((k_step<false, TAB, 8, MAXK, 4, true, true>), dim3(wg), dim3(2 * WAVE), lds, s, dp, in, out);
-            else if (pk == 2 && p.N == 1 && fr == 96)  // (the reference's defaults: one agent, 96 beams)
-                hipLaunchKernelGGL((k_step<false, TAB, 8, MAXK, 2, true, true, 96, 1>), dim3(wg), dim3(2 * WAVE), lds, s, dp, in, out);
-            else if (pk == 2 && p.N == 1)
-                hipLaunchKernelGGL((k_step<false, TAB, 8, MAXK, 2, true, true, 0, 1>), dim3(wg), dim3(2 * WAVE), lds, s, dp, in, out);
-            else if (pk == 2) hipLaunchKernelGGL((k_step<false, TAB, 8, MAXK, 2, true, true>), dim3(wg), dim3(2 * WAVE), lds, s, dp, in, out);
-            else hipLaunchKernelGGL((k_step<false, TAB, 8, MAXK, 1, true, true>), dim3(wg), dim3(2 * WAVE), lds, s, dp, in, out);
-            return;
-        }
-        if (step_split(p)) {  // two waves per workgroup (<= 4 waves per SIMD)
-            if (pk == 8) hipLaunchKernelGGL((k_step<false, TAB, 8, MAXK, 8, true>), dim3(wg), dim3(2 * WAVE), lds, s, dp, in, out);
-            else if (pk == 4) hipLaunchKernelGGL((k_step<false, TAB, 8, MAXK, 4, true>), dim3(wg), dim3(2 * WAVE), lds, s, dp, in, out);
-            else if (pk == 2) hipLaunchKernelGGL((k_step<false, TAB, 8, MAXK, 2, true>), dim3(wg), dim3(2 * WAVE), lds, s, dp, in, out);
-            else if (p.N == 8 && fr == 64)  // (configs 3 / 5 and 96 beams' shapes in smaller batches)
-                hipLaunchKernelGGL((k_step<false, TAB, 8, MAXK, 1, true, false, 64, 8>), dim3(wg), dim3(2 * WAVE), lds, s, dp, in, out);
-            else if (p.N == 8 && fr == 96)
-                hipLaunchKernelGGL((k_step<false, TAB, 8, MAXK, 1, true, false, 96, 8>), dim3(wg), dim3(2 * WAVE), lds, s, dp, in, out);
-            else if (p.N == 8 && fr == 128)
-                hipLaunchKernelGGL((k_step<false, TAB, 8, MAXK, 1, true, false, 128, 8>), dim3(wg), dim3(2 * WAVE), lds, s, dp, in, out);
-            else if (p.N == 1)  // (config 1: one agent per env at compile time)
-                hipLaunchKernelGGL((k_step<false, TAB, 8, MAXK, 1, true, false, 0, 1>), dim3(wg), dim3(2 * WAVE), lds, s, dp, in, out);
-            else hipLaunchKernelGGL((k_step<false, TAB, 8, MAXK, 1, true>), dim3(wg), dim3(2 * WAVE), lds, s, dp, in, out);
-            return;
-        }
-        if (pk == 8) hipLaunchKernelGGL((k_step<false, TAB, 8, MAXK, 8>), dim3(wg), dim3(WAVE), lds, s, dp, in, out);
-        else if (pk == 4) hipLaunchKernelGGL((k_step<false, TAB, 8, MAXK, 4>), dim3(wg), dim3(WAVE), lds, s, dp, in, out);
-        else if (pk == 2) hipLaunchKernelGGL((k_step<false, TAB, 8, MAXK, 2>), dim3(wg), dim3(WAVE), lds, s, dp, in, out);
-        else if (fr == 64 && p.N == 8)
-            hipLaunchKernelGGL((k_step<false, TAB, 8, MAXK, 1, false, false, 64, 8>), dim3(wg), dim3(WAVE), lds, s, dp, in, out);
-        else if (fr == 64)
-            hipLaunchKernelGGL((k_step<false, TAB, 8, MAXK, 1, false, false, 64>), dim3(wg), dim3(WAVE), lds, s, dp, in, out);
-        else if (fr == 96 && p.N == 8)
-            hipLaunchKernelGGL((k_step<false, TAB, 8, MAXK, 1, false, false, 96, 8>), dim3(wg), dim3(WAVE), lds, s, dp, in, out);
-        else if (fr == 96)
-            hipLaunchKernelGGL((k_step<false, TAB, 8, MAXK, 1, false, false, 96>), dim3(wg), dim3(WAVE), lds, s, dp, in, out);
-        else if (fr == 128 && p.N == 8)
-            hipLaunchKernelGGL((k_step<false, TAB, 8, MAXK, 1, false, false, 128, 8>), dim3(wg), dim3(WAVE), lds, s, dp, in, out);
-        else if (fr == 128)
-            hipLaunchKernelGGL((k_step<false, TAB, 8, MAXK, 1, false, false, 128>), dim3(wg), dim3(WAVE), lds, s, dp, in, out);
-        else if ((p.R & (WAVE - 1)) == 0)
-            hipLaunchKernelGGL((k_step<false, TAB, 8, MAXK, 1, false, false, 1>), dim3(wg), dim3(WAVE), lds, s, dp, in, out);
-        else hipLaunchKernelGGL((k_step<false, TAB, 8, MAXK, 1, false, false, 2>), dim3(wg), dim3(WAVE), lds, s, dp, in, out);
-    } else {
-        const unsigned lds = (unsigned)step_layout(p).bytes;
-        hipLaunchKernelGGL((k_step<false, TAB, 0>), dim3(p.E), dim3(WAVE), lds, s, dp, in, out);
-    }
-}
+// The compiled k_step and k_serve instantiations, in the order of their keys (kStepKeys,
+// kServeKeys in mev_plan.h), TAB = true before TAB = false: kStepFns[!TAB][row],
+// kServeFns[row][!TAB].  plan_step chooses the key.  (The two shapes name the kernels in
+// the order the code object has always held them, so a change that leaves the kernels
+// alone leaves its .text the same bytes.)
+using StepFn = void (*)(const SimParams*, StepInputs, Outputs);
+using ServeFn = void (*)(const SimParams*, ServeArgs, Outputs);
+#define MEV_STEP_TAB(T, NM, KM, PK, S, ES, P1, NC) k_step<T, true, NM, KM, PK, S, ES, P1, NC>,
+#define MEV_STEP_NOTAB(T, NM, KM, PK, S, ES, P1, NC) k_step<T, false, NM, KM, PK, S, ES, P1, NC>,
+#define MEV_SERVE_FNS(T, NM, KM, PK, S, ES, P1, NC) \
+    {k_serve<T, true, NM, KM, S, P1, NC>, k_serve<T, false, NM, KM, S, P1, NC>},
+static const StepFn kStepFns[2][sizeof kStepKeys / sizeof kStepKeys[0]] = {{MEV_STEP_KERNELS(MEV_STEP_TAB)},
+                                                                           {MEV_STEP_KERNELS(MEV_STEP_NOTAB)}};
+static const ServeFn kServeFns[][2] = {MEV_SERVE_KERNELS(MEV_SERVE_FNS)};
+#undef MEV_STEP_TAB
+#undef MEV_STEP_NOTAB
+#undef MEV_SERVE_FNS
 
 hipError_t launch_step(const SimParams& p, const SimParams* dp, const StepInputs& in, const Outputs& out,
                        hipStream_t s, const hipEvent_t* ev) {
-    const int kind = step_kernel_for(p);
-    if (kind == 0) return hipErrorInvalidValue;
-    if (kind == 2) {
-        if (ev) (void)hipEventRecord(ev[0], s);
-        if (p.dist_tab) launch_fused<true>(p, dp, in, out, s);
-        else launch_fused<false>(p, dp, in, out, s);
-        hipError_t e = hipGetLastError();
-        if (ev && e == hipSuccess) { (void)hipEventRecord(ev[1], s); (void)hipEventRecord(ev[2], s); }
-        return e;
-    }
-    return launch_part(p, in, out, 0, p.E, s, ev);
-}
-
-// k_serve runs the handle's fused step (one workgroup per env): the compile-time
-// layouts of launch_fused for small batches -- the split kernel without traffic,
-// one ego with <= 32 NPC slots -- and, for more NPC slots (env.py's 64), the
-// dynamic traffic layout, which at one env may take more than a wave's 10 KB share
-bool serve_fits(const SimParams& p) {
-    if (step_kernel_for(p) == 0 || p.step_kernel == 1 || p.dims) return false;
-    if (p.E > kServeMaxWG) return false;
-    if (p.traffic) return fixed_fits<1, 32>(p) || (p.K > 32 && fused_fits(p));
-    return fixed_fits<8, 0>(p) && step_pack(p) == 1 && !step_esplit(p) && p.step_split != 1;
+    const StepPlan pl = plan_step(p);
+    if (pl.path == 0) return hipErrorInvalidValue;
+    if (pl.path == 1) return launch_part(p, in, out, 0, p.E, s, ev);
+    const int row = key_row(kStepKeys, pl.step.key);
+    if (row < 0) return hipErrorInvalidValue;  // (a plan without a kernel: a bug, never another kernel)
+    if (ev) (void)hipEventRecord(ev[0], s);
+    hipLaunchKernelGGL(kStepFns[!p.dist_tab][row], dim3(pl.step.grid), dim3(pl.step.block), pl.step.lds, s,
+                       dp, in, out);
+    hipError_t e = hipGetLastError();
+    if (ev && e == hipSuccess) { (void)hipEventRecord(ev[1], s); (void)hipEventRecord(ev[2], s); }
+    return e;
 }
 
 hipError_t launch_serve(const SimParams& p, const SimParams* dp, const ServeArgs& sa, const Outputs& out,
                         hipStream_t s) {
-    if (!serve_fits(p)) return hipErrorInvalidValue;
-    if (p.traffic && fixed_fits<1, 32>(p)) {
-        const unsigned lds = (unsigned)FixedLayout<1, 32>::bytes;
-        if (p.dist_tab) hipLaunchKernelGGL((k_serve<true, true, 1, 32, false>), dim3(p.E), dim3(WAVE), lds, s, dp, sa, out);
-        else hipLaunchKernelGGL((k_serve<true, false, 1, 32, false>), dim3(p.E), dim3(WAVE), lds, s, dp, sa, out);
-    } else if (p.traffic) {
-        const unsigned lds = (unsigned)step_layout(p).bytes;  // + the static NpcLDST<64>
-        if (p.dist_tab) hipLaunchKernelGGL((k_serve<true, true, 0, 64, false>), dim3(p.E), dim3(WAVE), lds, s, dp, sa, out);
-        else hipLaunchKernelGGL((k_serve<true, false, 0, 64, false>), dim3(p.E), dim3(WAVE), lds, s, dp, sa, out);
-    } else {
-        const unsigned lds = (unsigned)FixedLayout<8>::bytes;
-        // (env.py's common shapes with their counts at compile time: one agent, 8 agents x 64 / 96 beams)
-        const dim3 g(p.E), b(2 * WAVE);
-        if (p.N == 1) {
-            if (p.dist_tab) hipLaunchKernelGGL((k_serve<false, true, 8, MAXK, true, 0, 1>), g, b, lds, s, dp, sa, out);
-            else hipLaunchKernelGGL((k_serve<false, false, 8, MAXK, true, 0, 1>), g, b, lds, s, dp, sa, out);
-        } else if (p.N == 8 && fixed_r(p) == 64) {
-            if (p.dist_tab) hipLaunchKernelGGL((k_serve<false, true, 8, MAXK, true, 64, 8>), g, b, lds, s, dp, sa, out);
-            else hipLaunchKernelGGL((k_serve<false, false, 8, MAXK, true, 64, 8>), g, b, lds, s, dp, sa, out);
-        } else if (p.N == 8 && fixed_r(p) == 96) {
-            if (p.dist_tab) hipLaunchKernelGGL((k_serve<false, true, 8, MAXK, true, 96, 8>), g, b, lds, s, dp, sa, out);
-            else hipLaunchKernelGGL((k_serve<false, false, 8, MAXK, true, 96, 8>), g, b, lds, s, dp, sa, out);
-        } else {
-            if (p.dist_tab) hipLaunchKernelGGL((k_serve<false, true, 8, MAXK, true>), g, b, lds, s, dp, sa, out);
-            else hipLaunchKernelGGL((k_serve<false, false, 8, MAXK, true>), g, b, lds, s, dp, sa, out);
-        }
-    }
+    const StepPlan pl = plan_step(p);
+    const int row = pl.serve_fits ? serve_row(pl.serve.key) : -1;
+    if (row < 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(kServeFns[row][!p.dist_tab], dim3(pl.serve.grid), dim3(pl.serve.block),
+                       pl.serve.lds, s, dp, sa, out);
     return hipGetLastError();
 }
 
