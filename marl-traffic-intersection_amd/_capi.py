@@ -40,7 +40,7 @@ EXPORTED = (
     "mev_last_error", "mev_abi_version", "mev_device_count", "mev_config_default", "mev_create", "mev_destroy",
     "mev_get_config", "mev_obs_dim", "mev_set_stream", "mev_sync", "mev_num_points", "mev_point_xy",
     "mev_route_id", "mev_route_info", "mev_route_len", "mev_path_len", "mev_set_ego_routes", "mev_set_traffic_routes",
-    "mev_default_traffic_routes", "mev_reset", "mev_step", "mev_get_outputs", "mev_get_state", "mev_set_state",
+    "mev_default_traffic_routes", "mev_reset", "mev_step", "mev_step_repeat", "mev_get_outputs", "mev_get_state", "mev_set_state",
     "mev_device_outputs", "mev_npc_overflow", "mev_npc_stats", "mev_use_own_stream", "mev_debug_stamps",
     "mev_configure", "mev_configure_traffic", "mev_set_reward", "mev_car_update", "mev_car_check_collision",
     "mev_kernel_timing", "mev_kernel_times", "mev_set_reset_routes", "mev_snapshot_size", "mev_snapshot",
@@ -73,6 +73,13 @@ class MevStepArgs(ctypes.Structure):
         ("done", _vp), ("status", _vp), ("terminated", _vp), ("truncated", _vp), ("agents_alive", _vp),
         ("step", _vp), ("flags", ctypes.c_uint32),
     ]
+
+
+MEV_MAX_REPEAT = 64
+
+
+class MevRepeatArgs(ctypes.Structure):
+    _fields_ = [("step", MevStepArgs), ("repeat", ctypes.c_int32), ("substeps", _vp)]
 
 
 # (name, dtype, per) — per: "ego" [E*N], "npc" [E*K], "env" [E]; order == struct mev_state
@@ -135,6 +142,7 @@ def load_library(variant: str = None):
     L.mev_default_traffic_routes.argtypes = [_vp, i32p, i32p]
     L.mev_reset.argtypes = [_vp, _vp, _vp, ctypes.c_uint32]
     L.mev_step.argtypes = [_vp, ctypes.POINTER(MevStepArgs)]
+    L.mev_step_repeat.argtypes = [_vp, ctypes.POINTER(MevRepeatArgs)]
     L.mev_get_outputs.argtypes = [_vp] + [_vp] * 8 + [ctypes.c_uint32]
     L.mev_get_state.argtypes = [_vp, ctypes.POINTER(MevState)]
     L.mev_set_state.argtypes = [_vp, ctypes.POINTER(MevState)]
@@ -468,6 +476,40 @@ class Handle:
         a.flags = ((MEV_DEVICE_PTRS if device else 0) | (MEV_AUTO_RESET if auto_reset else 0) |
                    (MEV_GATHER_TO_ROOT if gather else 0))
         _check(self._lib.mev_step(self._h, ctypes.byref(a)))
+        return out
+
+    def step_repeat(self, actions, repeat: int, dt: float = 1.0 / 60.0, out: Optional[dict] = None, spawn_route=None,
+                    auto_reset: bool = False, device: bool = False, gather: bool = False):
+        """Frame skip (mev_step_repeat): hold `actions` for up to `repeat` sub-steps of every env
+        in one call -- the reward summed, done / status latched, each env stopping at its first
+        terminated or truncated sub-step -- and cast the LiDAR once, from the state it stopped
+        at.  Returns the outputs of `step` plus `substeps` [E] (sub-steps executed).
+        spawn_route, if given, is [repeat][E].  device=True: every array (a `substeps` entry of
+        `out` included) is a device tensor/pointer.  gather: not supported (the library rejects it)."""
+        if not device:
+            actions = np.ascontiguousarray(actions, np.float32)
+            if actions.size != self.E * self.N * 2:
+                raise ValueError(f"actions must have {self.E}x{self.N}x2 elements, got {actions.shape}")
+            if spawn_route is not None:
+                spawn_route = np.ascontiguousarray(np.asarray(spawn_route, np.int32))
+                if spawn_route.shape != (int(repeat), self.E):
+                    raise ValueError(f"spawn_route must be [{int(repeat)}][{self.E}], got {spawn_route.shape}")
+            if out is None:
+                out = self.alloc_outputs()
+            if out.get("substeps") is None:
+                out["substeps"] = np.zeros(self.E, np.int32)
+        out = out if out is not None else {}
+        a = MevRepeatArgs()
+        for k in _OUT_KEYS:
+            setattr(a.step, k, _ptr(out.get(k)))
+        a.step.actions = _ptr(actions)
+        a.step.dt = float(dt)
+        a.step.spawn_route = _ptr(spawn_route)
+        a.step.flags = ((MEV_DEVICE_PTRS if device else 0) | (MEV_AUTO_RESET if auto_reset else 0) |
+                        (MEV_GATHER_TO_ROOT if gather else 0))
+        a.repeat = int(repeat)
+        a.substeps = _ptr(out.get("substeps"))
+        _check(self._lib.mev_step_repeat(self._h, ctypes.byref(a)))
         return out
 
     # -- multi-GPU gather (mev_comm_*) -------------------------------------

@@ -228,6 +228,15 @@ class _LidarGroup:
         self._stitch(r["obs"], [o["obs"] for o in self._outs])
         return r
 
+    def step_repeat(self, actions, repeat, dt=1.0 / 60.0, out=None):
+        if self._outs is None:
+            self._outs = [h.alloc_outputs() for h in self._hs[1:]]
+        r = self._hs[0].step_repeat(actions, repeat, dt, out=out)
+        for h, o in zip(self._hs[1:], self._outs):
+            h.step_repeat(actions, repeat, dt, out=o)
+        self._stitch(r["obs"], [o["obs"] for o in self._outs])
+        return r
+
     def observations(self):
         return self._stitch(self._hs[0].observations().copy(), [h.observations() for h in self._hs[1:]])
 
@@ -470,6 +479,18 @@ class IntersectionEnv:
 
     def step(self, throttles: Sequence[float], steerings: Sequence[float], dt: float = 1.0 / 60.0) -> StepResult:
         """IntersectionEnv::step (cpp/IntersectionEnv.cpp:133-392) on the GPU."""
+        return self._step(throttles, steerings, dt, None)
+
+    def step_repeat(self, throttles: Sequence[float], steerings: Sequence[float], dt: float = 1.0 / 60.0,
+                    repeat: int = 1) -> StepResult:
+        """Up to `repeat` steps with the same inputs in one device call (mev_step_repeat), as the
+        reference's driver loops them (test.py:144-155): the rewards summed, done / status latched
+        at each car's latest done, stopping at terminated or truncated; the observation -- the
+        LiDAR cast once -- and the flags are those of the last executed step, `.substeps` their
+        number."""
+        return self._step(throttles, steerings, dt, int(repeat))
+
+    def _step(self, throttles, steerings, dt, repeat) -> StepResult:
         h = self._h
         if h is None or self._pending or self._reward_dirty or h.N != len(self._routes) or self._h_lidar != self._lidar \
                 or self._ghost:
@@ -486,7 +507,10 @@ class IntersectionEnv:
             act.fill(0.0)
         act[0, : t.size, 0] = t
         act[0, : s.size, 1] = s
-        out = h.step(act, float(dt), out=self._out)
+        if repeat is None:
+            out = h.step(act, float(dt), out=self._out)
+        else:
+            out = h.step_repeat(act, repeat, float(dt), out=self._out)
         self._fresh = False
         m = 0 if self._ghost else n
         res = StepResult.__new__(StepResult)
@@ -499,6 +523,8 @@ class IntersectionEnv:
         res.terminated = bool(out["terminated"][0])
         res.truncated = bool(out["truncated"][0])
         res.step = int(out["step"][0])
+        if repeat is not None:
+            res.substeps = int(out["substeps"][0])
         return res
 
     def get_observations(self) -> np.ndarray:

@@ -97,6 +97,8 @@ struct mev_handle {
     mev::Outputs last{};  // where the most recent outputs were written
     float* d_actions = nullptr;
     int32_t* d_spawn = nullptr;
+    int32_t* d_spawn_rep = nullptr;  // [MEV_MAX_REPEAT][E] spawn routes of a host-mode mev_step_repeat (made at the first)
+    int32_t* d_substeps = nullptr;   // [E] its sub-step counts
     uint8_t* d_mask = nullptr;
     float* d_paths = nullptr;
     int32_t* d_rlen = nullptr;  // [route_cap] each path's own length (RouteTab::len)
@@ -1447,6 +1449,61 @@ int mev_step(mev_handle* h, const mev_step_args* a) {
         int r = copy_out(h, o, a->obs, a->reward, a->done, a->status, a->terminated, a->truncated, a->agents_alive,
                          a->step, hipMemcpyDeviceToHost);
         if (r) return r;
+        HIP_TRY(hipStreamSynchronize(h->stream));
+    }
+    return MEV_OK;
+}
+
+int mev_step_repeat(mev_handle* h, const mev_repeat_args* ra) {
+    if (!h || !ra) return fail(MEV_E_INVALID, "null argument");
+    const mev_step_args* a = &ra->step;
+    if (!a->actions) return fail(MEV_E_INVALID, "actions required");
+    if (ra->repeat < 1 || ra->repeat > MEV_MAX_REPEAT)
+        return fail(MEV_E_INVALID, "repeat must be in 1.." + std::to_string(MEV_MAX_REPEAT));
+    if (a->flags & MEV_GATHER_TO_ROOT) return fail(MEV_E_INVALID, "mev_step_repeat does not gather (MEV_GATHER_TO_ROOT)");
+    HIP_TRY(hipSetDevice(h->cfg.device));
+    if (int r = serve_stop(h)) return r;  // (the server holds the stream)
+    const bool dev = (a->flags & MEV_DEVICE_PTRS) != 0;
+    const int n = ra->repeat;
+    const size_t E = size_t(h->cfg.num_envs), EN = E * size_t(h->cfg.num_agents);
+    if (!dev) {
+        hipError_t err = hipSuccess;
+        if (a->spawn_route && !h->d_spawn_rep) err = h->alloc(&h->d_spawn_rep, size_t(MEV_MAX_REPEAT) * E);
+        if (err == hipSuccess && ra->substeps && !h->d_substeps) err = h->alloc(&h->d_substeps, E);
+        if (err != hipSuccess) return fail(MEV_E_NOMEM, std::string("device allocation failed: ") + hipGetErrorString(err));
+    }
+    mev::StepInputs in{};
+    in.dt = a->dt;
+    in.auto_reset = (a->flags & MEV_AUTO_RESET) ? 1 : 0;
+    in.rng_counter = h->rng_counter;  // sub-step s: + s (k_cars_repeat)
+    h->rng_counter += uint64_t(n);
+    int32_t* d_sub = nullptr;
+    if (dev) {
+        in.actions = a->actions;
+        in.spawn_route = a->spawn_route;
+        d_sub = ra->substeps;
+    } else {
+        HIP_TRY(hipMemcpyAsync(h->d_actions, a->actions, EN * 2 * sizeof(float), hipMemcpyHostToDevice, h->stream));
+        in.actions = h->d_actions;
+        if (a->spawn_route) {
+            HIP_TRY(hipMemcpyAsync(h->d_spawn_rep, a->spawn_route, size_t(n) * E * sizeof(int32_t), hipMemcpyHostToDevice,
+                                   h->stream));
+            in.spawn_route = h->d_spawn_rep;
+        }
+        if (ra->substeps) d_sub = h->d_substeps;
+    }
+    in.spawn_prob = 1.0f - expf(-h->cfg.traffic_density * a->dt);  // as mev_step
+    const mev::Outputs o = resolve_outputs(h, a->obs, a->reward, a->done, a->status, a->terminated, a->truncated,
+                                           a->agents_alive, a->step, dev);
+    h->deal_valid = false;  // NPC counts change outside the fused step: the deal restarts
+    HIP_TRY(mev::launch_step_repeat(h->sp, in, o, n, d_sub, h->stream));
+    h->last = o;
+    if (!dev) {
+        if (int r = copy_out(h, o, a->obs, a->reward, a->done, a->status, a->terminated, a->truncated, a->agents_alive,
+                             a->step, hipMemcpyDeviceToHost))
+            return r;
+        if (ra->substeps)
+            HIP_TRY(hipMemcpyAsync(ra->substeps, d_sub, E * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
         HIP_TRY(hipStreamSynchronize(h->stream));
     }
     return MEV_OK;

@@ -196,6 +196,12 @@ inline StepPlan plan_step(const SimParams& p) { return plan_step(step_shape(p));
 // dp: a device copy of p (k_step reads its parameters through it)
 hipError_t launch_step(const SimParams& p, const SimParams* dp, const StepInputs& in, const Outputs& out,
                        hipStream_t s, const hipEvent_t* ev = nullptr);
+// The frame-skip call: up to `repeat` sub-steps of the car part per env in one launch
+// (k_cars_repeat: the state stays on the CU in between), then one k_lidar cast from the
+// state each env stopped at.  in.spawn_route, if given, is [repeat][E]; sub-step s uses
+// in.rng_counter + s.  substeps (nullable): [E] sub-steps executed.  Every shape k_cars runs.
+hipError_t launch_step_repeat(const SimParams& p, const StepInputs& in, const Outputs& out, int repeat,
+                              int32_t* substeps, hipStream_t s);
 hipError_t launch_reset(const SimParams& p, const uint8_t* env_mask, const Outputs& out, hipStream_t s,
                         uint64_t rng_counter);
 // recompute the observation rows from the current state with LiDAR = max (after set_state)

@@ -1500,6 +1500,21 @@ struct CarsCtx {
     bool ended;     // (set by cars_post, PK == 1) terminated or truncated this step
 };
 
+// What a frame-skip call (k_cars_repeat) keeps in the wave from one sub-step to the next
+// (cars_pre / cars_post with REP): the sub-step and the window's length, what cars_pre
+// would otherwise read from HBM (the env's counters; the ego and NPC state stay in
+// CarsLDS / NpcLDS), and per agent (lane = agent) the reward sum, the done bit and the
+// status latched at the agent's latest done.
+struct RepCarry {
+    int s, n;          // sub-step 0 .. n - 1 of a window of n
+    int step_prev;     // the env's step counter after the previous sub-step
+    int npcs_prev;     // NPCs alive after the previous sub-step
+    bool first_reset;  // the env was auto-reset at the window's first sub-step
+    float rew;
+    uint8_t any_done, latched;
+    int32_t* substeps;  // [E] sub-steps executed (nullable)
+};
+
 // Phase 1 of the car part for agent i of el on lane group (grp, sub): kinematics
 // (IntersectionEnv.cpp:151-163), path index, base reward (:15-46), status (:165-290).
 // cars_pre runs it over its agents 8 per pass; the traffic early split's LiDAR wave
@@ -1691,10 +1706,16 @@ __device__ __forceinline__ void ego_phase1(const SimParams& p, const StepInputs&
 // runs the NPC phase; the two meet at workgroup barrier H, then this wave goes on from the
 // SAT.  The NPC phase's spawn test reads the ego's start-of-step position, which this wave
 // keeps in envw[0..1] (the LiDAR wave overwrites el.x / el.y with the moved pose).
+// REP (k_cars_repeat, the frame-skip call): sub-step rc->s of a window.  From the second
+// sub-step on nothing is loaded from HBM: the ego state is what cars_post left in el, the
+// NPCs are the survivors in nl, the counters come in rc; the obstacle table and candidate
+// masks stay in LDS (cars_post publishes them in the sub-step the env stops at).
 template <bool TRAFFIC, bool FUSED, class NL, int PK = 1, bool EARLY = false, bool ESPLIT = false, bool DIMS = false,
-          bool TSC = false, int NC = 0>
+          bool TSC = false, int NC = 0, bool REP = false>
 __device__ __forceinline__ CarsCtx cars_pre(const SimParams& p, const StepInputs& in, const Outputs& out, const int e,
-                                            const CarsLDS& el, NL* nl, int npc_cls = kDealClasses - 1) {
+                                            const CarsLDS& el, NL* nl, int npc_cls = kDealClasses - 1,
+                                            const RepCarry* rc = nullptr) {
+    static_assert(!REP || (!FUSED && PK == 1 && !EARLY && !ESPLIT && !TSC && NC == 0), "frame skip: k_cars' layout");
     static_assert(!ESPLIT || FUSED, "early split: k_step");
     static_assert(PK == 1 || (FUSED && !TRAFFIC), "several envs per wave: k_step without traffic");
     static_assert(!DIMS || (PK == 1 && !EARLY && !ESPLIT), "per-car sizes: the runtime-layout kernels");
@@ -1735,157 +1756,177 @@ __device__ __forceinline__ CarsCtx cars_pre(const SimParams& p, const StepInputs
     const int il = lane_on ? tid : 0;
     const int gl = e * NE + il;
     const uint32_t ug = (uint32_t)gl;
-    const uint8_t pending_b = ldu(gmem(p.pending_reset), (uint32_t)ee);
-    const int step_prev = ldu(gmem(p.step_count), (uint32_t)ee);
-    const int npcs_prev = TRAFFIC ? gmem(p.npc.count)[e] : 0;
-    const float a0 = ldu(gmem(in.actions), 2 * ug), a1 = ldu(gmem(in.actions), 2 * ug + 1);
-    const int route_l = ldu(egoi(p, EF_ROUTE), ug);
-    const float x0 = ldu(egof(p, EF_X), ug), y0 = ldu(egof(p, EF_Y), ug), v0 = ldu(egof(p, EF_V), ug);
-    const float h0 = ldu(egof(p, EF_H), ug), acc0 = ldu(egof(p, EF_ACC), ug), steer0 = ldu(egof(p, EF_STEER), ug);
-    const float pd0 = ldu(egof(p, EF_PREV_DIST), ug), pa00 = ldu(egof(p, EF_PA0), ug), pa10 = ldu(egof(p, EF_PA1), ug);
-    const float sx0 = ldu(egof(p, EF_SX), ug), sy0 = ldu(egof(p, EF_SY), ug), sv0 = ldu(egof(p, EF_SV), ug);
-    const float sh0 = ldu(egof(p, EF_SH), ug);
-    const int pidx_l = ldu(egoi(p, EF_PIDX), ug), intent_l = ldu(egoi(p, EF_INTENT), ug);
-    const uint8_t alive_l = ldu(gmem(p.ego.alive), ug);
-    float len_l = CAR_LENGTH, wid_l = CAR_WIDTH;
-    if constexpr (DIMS) {
-        len_l = ldu(gmem(p.ego_dim), 2 * ug);
-        wid_l = ldu(gmem(p.ego_dim), 2 * ug + 1);
-    }
-    // phase 1's first pass in group layout (lane (grp, sub): agent grp), without
-    // traffic (there the NPC phase runs in between, and the window registers would
-    // stay live through it): the agent's route, path index and env reset flag
-    // EARLY (k_step's compile-time layouts without traffic: N <= 8 agent slots, the
-    // window LDS in el.win)
+    // what the rest of the step takes from phase 0
+    int step_no = 0, prev_npcs = 0, eroute = 0, epidx = 0;
+    bool do_reset = false;
+    NpcRegs nreg{};
+    Kin gk{};
+    uint8_t galive_b = 0;
+    float ga0 = 0.0f, ga1 = 0.0f;
+    bool cont = false;  // REP: a later sub-step of a window, its state already in LDS
+    if constexpr (REP) cont = rc->s > 0;
     static_assert(!EARLY || (FUSED && !TRAFFIC), "LDS path windows: k_step without traffic");
     constexpr bool early = EARLY;
-    const int ga = (tid >> 3) < N ? (tid >> 3) : 0;
-    const int eea = PK == 1 ? e : e + ga / NE;
-    int groute = 0, gpidx = 0;
-    bool gpend = false;
-    // (loads in one basic block, in-bounds by clamped indices rather than behind
-    // branches: the scheduler keeps them together ahead of every use)
-    // and its kinematic state and actions: phase 1's kinematics then read no LDS, so
-    // no LDS read waits for round B's DMA before the window is needed (without alias
-    // information an LDS read waits for every LDS DMA in flight)
-    uint8_t gpend_b = 0, galive_b = 0;
-    Kin gk{};
-    float ga0 = 0.0f, ga1 = 0.0f;
-    if constexpr (early) {
-        const uint32_t ugg = (uint32_t)(e * NE + ga);
-        groute = ldu(egoi(p, EF_ROUTE), ugg);
-        gpidx = ldu(egoi(p, EF_PIDX), ugg);
-        gpend_b = ldu(gmem(p.pending_reset), (uint32_t)eea);
-        gk = Kin{ldu(egof(p, EF_X), ugg), ldu(egof(p, EF_Y), ugg), ldu(egof(p, EF_V), ugg), ldu(egof(p, EF_H), ugg),
-                 ldu(egof(p, EF_ACC), ugg), ldu(egof(p, EF_STEER), ugg)};
-        galive_b = ldu(gmem(p.ego.alive), ugg);
-        ga0 = ldu(gmem(in.actions), 2 * ugg);
-        ga1 = ldu(gmem(in.actions), 2 * ugg + 1);
-    }
-    float rl0 = 0.0f, rl1 = 0.0f;
-    if (FUSED && !ESPLIT) {
-        const int rmax = p.R - 1;
-        rl0 = ldu(gmem(p.rel_angles), (uint32_t)(tid < rmax ? tid : rmax));
-        rl1 = ldu(gmem(p.rel_angles), (uint32_t)(tid + WAVE < rmax ? tid + WAVE : rmax));
-    }
-    NpcRegs nreg{};
-    // in flight with the ego loads; only the slots the env's deal class says are filled (the
-    // class is its NPC count after the previous step; the last class and no deal: every slot)
-    if constexpr (TRAFFIC) nreg = npc_load<DIMS>(p, e, tid, npc_cls < kDealClasses - 1 ? npc_cls : p.K);
-    // every load above is issued before any of their values is used (a use scheduled
-    // between them would put a wait for the first loads in front of the rest)
-    __builtin_amdgcn_sched_barrier(0);
-    static_assert(!TSC || (TRAFFIC && ESPLIT && PK == 1 && !DIMS), "TSC: the traffic early split's car waves");
-    const bool pending = pending_b != 0;
-    gpend = gpend_b != 0;
-    const bool do_reset = in.auto_reset && pending;
-    const int prev_step = do_reset ? 0 : step_prev;
-    const int prev_npcs = TRAFFIC ? (do_reset ? 0 : npcs_prev) : 0;
-    if (TSC && tid == 0) {  // the start-of-step position (the spawn after an auto-reset) for the NPC spawn test
-        float sx_ = x0, sy_ = y0;
-        if (do_reset) {
-            const int rid = reset_route(p, in.rng_counter, ee, 0, route_l);
-            sx_ = gmem(p.rt.spawn)[3 * rid];
-            sy_ = gmem(p.rt.spawn)[3 * rid + 1];
+    if (!cont) {
+        const uint8_t pending_b = ldu(gmem(p.pending_reset), (uint32_t)ee);
+        const int step_prev = ldu(gmem(p.step_count), (uint32_t)ee);
+        const int npcs_prev = TRAFFIC ? gmem(p.npc.count)[e] : 0;
+        const float a0 = ldu(gmem(in.actions), 2 * ug), a1 = ldu(gmem(in.actions), 2 * ug + 1);
+        const int route_l = ldu(egoi(p, EF_ROUTE), ug);
+        const float x0 = ldu(egof(p, EF_X), ug), y0 = ldu(egof(p, EF_Y), ug), v0 = ldu(egof(p, EF_V), ug);
+        const float h0 = ldu(egof(p, EF_H), ug), acc0 = ldu(egof(p, EF_ACC), ug), steer0 = ldu(egof(p, EF_STEER), ug);
+        const float pd0 = ldu(egof(p, EF_PREV_DIST), ug), pa00 = ldu(egof(p, EF_PA0), ug), pa10 = ldu(egof(p, EF_PA1), ug);
+        const float sx0 = ldu(egof(p, EF_SX), ug), sy0 = ldu(egof(p, EF_SY), ug), sv0 = ldu(egof(p, EF_SV), ug);
+        const float sh0 = ldu(egof(p, EF_SH), ug);
+        const int pidx_l = ldu(egoi(p, EF_PIDX), ug), intent_l = ldu(egoi(p, EF_INTENT), ug);
+        const uint8_t alive_l = ldu(gmem(p.ego.alive), ug);
+        float len_l = CAR_LENGTH, wid_l = CAR_WIDTH;
+        if constexpr (DIMS) {
+            len_l = ldu(gmem(p.ego_dim), 2 * ug);
+            wid_l = ldu(gmem(p.ego_dim), 2 * ug + 1);
         }
-        el.envw[0] = __float_as_int(sx_);
-        el.envw[1] = __float_as_int(sy_);
-    }
-    if (!TSC && lane_on) {
-        el.a0[il] = a0;
-        el.a1[il] = a1;
-        el.route[il] = route_l;
-        el.x[il] = x0; el.y[il] = y0; el.v[il] = v0; el.h[il] = h0;
-        el.acc[il] = acc0; el.steer[il] = steer0; el.prev_dist[il] = pd0;
-        el.pa0[il] = pa00; el.pa1[il] = pa10;
-        el.sx[il] = sx0; el.sy[il] = sy0; el.sv[il] = sv0; el.sh[il] = sh0;
-        el.pidx[il] = pidx_l; el.intent[il] = intent_l; el.alive[il] = alive_l;
-    }
-    if (DIMS && lane_on) {  // an env being reset gets new Cars of the default size (Car.h:19-20)
-        el.len[il] = do_reset ? CAR_LENGTH : len_l;
-        el.wid[il] = do_reset ? CAR_WIDTH : wid_l;
-    }
-    if constexpr (FUSED && !ESPLIT) {
-        if (p.R <= 2 * WAVE) {
-            if (tid < p.R) el.rel[tid] = rl0;
-            if (tid + WAVE < p.R) el.rel[tid + WAVE] = rl1;
-        } else {
-            for (int b = tid; b < p.R; b += WAVE) el.rel[b] = gmem(p.rel_angles)[b];
+        // phase 1's first pass in group layout (lane (grp, sub): agent grp), without
+        // traffic (there the NPC phase runs in between, and the window registers would
+        // stay live through it): the agent's route, path index and env reset flag
+        // EARLY (k_step's compile-time layouts without traffic: N <= 8 agent slots, the
+        // window LDS in el.win)
+        const int ga = (tid >> 3) < N ? (tid >> 3) : 0;
+        const int eea = PK == 1 ? e : e + ga / NE;
+        int groute = 0, gpidx = 0;
+        bool gpend = false;
+        // (loads in one basic block, in-bounds by clamped indices rather than behind
+        // branches: the scheduler keeps them together ahead of every use)
+        // and its kinematic state and actions: phase 1's kinematics then read no LDS, so
+        // no LDS read waits for round B's DMA before the window is needed (without alias
+        // information an LDS read waits for every LDS DMA in flight)
+        uint8_t gpend_b = 0;
+        if constexpr (early) {
+            const uint32_t ugg = (uint32_t)(e * NE + ga);
+            groute = ldu(egoi(p, EF_ROUTE), ugg);
+            gpidx = ldu(egoi(p, EF_PIDX), ugg);
+            gpend_b = ldu(gmem(p.pending_reset), (uint32_t)eea);
+            gk = Kin{ldu(egof(p, EF_X), ugg), ldu(egof(p, EF_Y), ugg), ldu(egof(p, EF_V), ugg), ldu(egof(p, EF_H), ugg),
+                     ldu(egof(p, EF_ACC), ugg), ldu(egof(p, EF_STEER), ugg)};
+            galive_b = ldu(gmem(p.ego.alive), ugg);
+            ga0 = ldu(gmem(in.actions), 2 * ugg);
+            ga1 = ldu(gmem(in.actions), 2 * ugg + 1);
         }
-    }
-    if (!TSC && lane_on && do_reset) {  // the lane's env was auto-reset: its agents start from their spawns
-        const int rid = reset_route(p, in.rng_counter, ee, PK == 1 ? il : il - (ee - e) * NE, route_l);
-        const float rx = gmem(p.rt.spawn)[3 * rid], ry = gmem(p.rt.spawn)[3 * rid + 1], rh = gmem(p.rt.spawn)[3 * rid + 2];
-        el.route[il] = rid;
-        el.x[il] = rx; el.y[il] = ry; el.v[il] = 0.0f; el.h[il] = rh;
-        el.acc[il] = 0.0f; el.steer[il] = 0.0f; el.prev_dist[il] = 0.0f; el.pa0[il] = 0.0f; el.pa1[il] = 0.0f;
-        el.sx[il] = rx; el.sy[il] = ry; el.sv[il] = 0.0f; el.sh[il] = rh;
-        el.pidx[il] = 0; el.intent[il] = gmem(p.rt.intent)[rid]; el.alive[il] = 1;
-    }
-    // round B: the first pass's path windows, loaded straight into LDS (gfx950
-    // global_load_lds_dwordx4: no VGPRs held while they are in flight) from the
-    // group-layout route / index registers.  Agent grp's window is the 64 points
-    // from s_e = start_i rounded down to even (16-B aligned: 32 chunks of 2 points,
-    // [start_i, start_i + 50) and the look-ahead target start_i + <= 59 inside it);
-    // lane (grp, sub) loads chunks 4 sub .. 4 sub + 3 (instruction m: chunk 4 sub +
-    // m at win + m KB + grp * 128 + sub * 16) and reads back exactly those, so each
-    // lane's 8 points arrive as 4 aligned 16-B LDS reads.  A fifth instruction brings
-    // the route row's last segment (points plen, plen + 1: lane sub 0) and path[10, 11] (sub 1).
-    // Chunks past the path's end are clamped to its last one: those points lie
-    // beyond every window's range and are never used.
-    int eroute = 0, epidx = 0;
-    if (early) {
-        const bool greset = in.auto_reset && gpend;
-        eroute = greset ? reset_route(p, in.rng_counter, eea, PK == 1 ? ga : ga - (eea - e) * NE, groute) : groute;
-        epidx = greset ? 0 : gpidx;
-        if (greset) {  // agent ga starts from its spawn (as the lane layout above)
-            gk = Kin{gmem(p.rt.spawn)[3 * eroute], gmem(p.rt.spawn)[3 * eroute + 1], 0.0f,
-                     gmem(p.rt.spawn)[3 * eroute + 2], 0.0f, 0.0f};
-            galive_b = 1;
+        float rl0 = 0.0f, rl1 = 0.0f;
+        if (FUSED && !ESPLIT) {
+            const int rmax = p.R - 1;
+            rl0 = ldu(gmem(p.rel_angles), (uint32_t)(tid < rmax ? tid : rmax));
+            rl1 = ldu(gmem(p.rel_angles), (uint32_t)(tid + WAVE < rmax ? tid + WAVE : rmax));
         }
-        const int start_i = epidx < 0 ? 0 : epidx;
-        const int sub = tid & 7;
-        const uint32_t rbase = (uint32_t)eroute * (uint32_t)(2 * 4 * p.rt.row);  // bytes
-        typedef const __attribute__((address_space(1))) char gchar;
-        gchar* path_b = (gchar*)gmem(p.rt.path);
-        __attribute__((address_space(3))) char* win = (__attribute__((address_space(3))) char*)el.win;
+        // in flight with the ego loads; only the slots the env's deal class says are filled (the
+        // class is its NPC count after the previous step; the last class and no deal: every slot)
+        if constexpr (TRAFFIC) nreg = npc_load<DIMS>(p, e, tid, npc_cls < kDealClasses - 1 ? npc_cls : p.K);
+        // every load above is issued before any of their values is used (a use scheduled
+        // between them would put a wait for the first loads in front of the rest)
+        __builtin_amdgcn_sched_barrier(0);
+        static_assert(!TSC || (TRAFFIC && ESPLIT && PK == 1 && !DIMS), "TSC: the traffic early split's car waves");
+        const bool pending = pending_b != 0;
+        gpend = gpend_b != 0;
+        do_reset = in.auto_reset && pending;
+        const int prev_step = do_reset ? 0 : step_prev;
+        prev_npcs = TRAFFIC ? (do_reset ? 0 : npcs_prev) : 0;
+        if (TSC && tid == 0) {  // the start-of-step position (the spawn after an auto-reset) for the NPC spawn test
+            float sx_ = x0, sy_ = y0;
+            if (do_reset) {
+                const int rid = reset_route(p, in.rng_counter, ee, 0, route_l);
+                sx_ = gmem(p.rt.spawn)[3 * rid];
+                sy_ = gmem(p.rt.spawn)[3 * rid + 1];
+            }
+            el.envw[0] = __float_as_int(sx_);
+            el.envw[1] = __float_as_int(sy_);
+        }
+        if (!TSC && lane_on) {
+            el.a0[il] = a0;
+            el.a1[il] = a1;
+            el.route[il] = route_l;
+            el.x[il] = x0; el.y[il] = y0; el.v[il] = v0; el.h[il] = h0;
+            el.acc[il] = acc0; el.steer[il] = steer0; el.prev_dist[il] = pd0;
+            el.pa0[il] = pa00; el.pa1[il] = pa10;
+            el.sx[il] = sx0; el.sy[il] = sy0; el.sv[il] = sv0; el.sh[il] = sh0;
+            el.pidx[il] = pidx_l; el.intent[il] = intent_l; el.alive[il] = alive_l;
+        }
+        if (DIMS && lane_on) {  // an env being reset gets new Cars of the default size (Car.h:19-20)
+            el.len[il] = do_reset ? CAR_LENGTH : len_l;
+            el.wid[il] = do_reset ? CAR_WIDTH : wid_l;
+        }
+        if constexpr (FUSED && !ESPLIT) {
+            if (p.R <= 2 * WAVE) {
+                if (tid < p.R) el.rel[tid] = rl0;
+                if (tid + WAVE < p.R) el.rel[tid + WAVE] = rl1;
+            } else {
+                for (int b = tid; b < p.R; b += WAVE) el.rel[b] = gmem(p.rel_angles)[b];
+            }
+        }
+        if (!TSC && lane_on && do_reset) {  // the lane's env was auto-reset: its agents start from their spawns
+            const int rid = reset_route(p, in.rng_counter, ee, PK == 1 ? il : il - (ee - e) * NE, route_l);
+            const float rx = gmem(p.rt.spawn)[3 * rid], ry = gmem(p.rt.spawn)[3 * rid + 1], rh = gmem(p.rt.spawn)[3 * rid + 2];
+            el.route[il] = rid;
+            el.x[il] = rx; el.y[il] = ry; el.v[il] = 0.0f; el.h[il] = rh;
+            el.acc[il] = 0.0f; el.steer[il] = 0.0f; el.prev_dist[il] = 0.0f; el.pa0[il] = 0.0f; el.pa1[il] = 0.0f;
+            el.sx[il] = rx; el.sy[il] = ry; el.sv[il] = 0.0f; el.sh[il] = rh;
+            el.pidx[il] = 0; el.intent[il] = gmem(p.rt.intent)[rid]; el.alive[il] = 1;
+        }
+        // round B: the first pass's path windows, loaded straight into LDS (gfx950
+        // global_load_lds_dwordx4: no VGPRs held while they are in flight) from the
+        // group-layout route / index registers.  Agent grp's window is the 64 points
+        // from s_e = start_i rounded down to even (16-B aligned: 32 chunks of 2 points,
+        // [start_i, start_i + 50) and the look-ahead target start_i + <= 59 inside it);
+        // lane (grp, sub) loads chunks 4 sub .. 4 sub + 3 (instruction m: chunk 4 sub +
+        // m at win + m KB + grp * 128 + sub * 16) and reads back exactly those, so each
+        // lane's 8 points arrive as 4 aligned 16-B LDS reads.  A fifth instruction brings
+        // the route row's last segment (points plen, plen + 1: lane sub 0) and path[10, 11] (sub 1).
+        // Chunks past the path's end are clamped to its last one: those points lie
+        // beyond every window's range and are never used.
+        if (early) {
+            const bool greset = in.auto_reset && gpend;
+            eroute = greset ? reset_route(p, in.rng_counter, eea, PK == 1 ? ga : ga - (eea - e) * NE, groute) : groute;
+            epidx = greset ? 0 : gpidx;
+            if (greset) {  // agent ga starts from its spawn (as the lane layout above)
+                gk = Kin{gmem(p.rt.spawn)[3 * eroute], gmem(p.rt.spawn)[3 * eroute + 1], 0.0f,
+                         gmem(p.rt.spawn)[3 * eroute + 2], 0.0f, 0.0f};
+                galive_b = 1;
+            }
+            const int start_i = epidx < 0 ? 0 : epidx;
+            const int sub = tid & 7;
+            const uint32_t rbase = (uint32_t)eroute * (uint32_t)(2 * 4 * p.rt.row);  // bytes
+            typedef const __attribute__((address_space(1))) char gchar;
+            gchar* path_b = (gchar*)gmem(p.rt.path);
+            __attribute__((address_space(3))) char* win = (__attribute__((address_space(3))) char*)el.win;
 #pragma unroll
-        for (int m = 0; m < 4; ++m) {
-            int c = (start_i >> 1) + sub * 4 + m;
-            c = c < (p.rt.plen >> 1) ? c : (p.rt.plen >> 1) - 1;
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(path_b + rbase + c * 16),
-                                             (__attribute__((address_space(3))) void*)(win + m * 1024), 16, 0, 0);
+            for (int m = 0; m < 4; ++m) {
+                int c = (start_i >> 1) + sub * 4 + m;
+                c = c < (p.rt.plen >> 1) ? c : (p.rt.plen >> 1) - 1;
+                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(path_b + rbase + c * 16),
+                                                 (__attribute__((address_space(3))) void*)(win + m * 1024), 16, 0, 0);
+            }
+            const int cx = sub == 0 ? p.rt.plen >> 1 : 5;  // points plen, plen + 1 (last segment) / 10, 11
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(path_b + rbase + cx * 16),
+                                             (__attribute__((address_space(3))) void*)(win + 4 * 1024), 16, 0, 0);
         }
-        const int cx = sub == 0 ? p.rt.plen >> 1 : 5;  // points plen, plen + 1 (last segment) / 10, 11
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(path_b + rbase + cx * 16),
-                                         (__attribute__((address_space(3))) void*)(win + 4 * 1024), 16, 0, 0);
+        step_no = prev_step + 1;  // res.step = ++step_count (:137)
+        // gmem(p.step_count)[e] = step_no is stored with the other env flags (a store this
+        // early would be drained by the vmcnt waits of every later load)
+        // (no fence: an acquire fence would also wait for round B's LDS DMA, which
+        // phase 1 first needs after the kinematics; one wave's LDS operations complete
+        // in order, so ordering the code is enough)
+    } else if constexpr (REP) {
+        // a later sub-step: the counters from the carry, the NPC survivors from nl (lane = slot)
+        step_no = rc->step_prev + 1;
+        prev_npcs = TRAFFIC ? rc->npcs_prev : 0;
+        if constexpr (TRAFFIC) {
+            if (tid < prev_npcs) {
+                nreg.x = nl->x[tid]; nreg.y = nl->y[tid]; nreg.v = nl->v[tid]; nreg.h = nl->h[tid];
+                nreg.acc = nl->acc[tid]; nreg.steer = nl->steer[tid];
+                nreg.pidx = nl->pidx[tid]; nreg.route = nl->route[tid]; nreg.intent = nl->intent[tid];
+                nreg.alive = nl->alive[tid];
+                if constexpr (DIMS) { nreg.len = nl->len[tid]; nreg.wid = nl->wid[tid]; }
+            }
+        }
     }
-    const int step_no = prev_step + 1;  // res.step = ++step_count (:137)
-    // gmem(p.step_count)[e] = step_no is stored with the other env flags (a store this
-    // early would be drained by the vmcnt waits of every later load)
-    // (no fence: an acquire fence would also wait for round B's LDS DMA, which
-    // phase 1 first needs after the kinematics; one wave's LDS operations complete
-    // in order, so ordering the code is enough)
     wave_lds_order();
 
     STAMP(0);
@@ -2038,7 +2079,7 @@ __device__ __forceinline__ CarsCtx cars_pre(const SimParams& p, const StepInputs
         const int4 b4 = make_int4(bx.x0, bx.x1, bx.y0, bx.y1);
         el.box[o] = b4;
         el.px[o] = x; el.py[o] = y; el.ph[o] = h;
-        if (!FUSED) p.ob_box[e * OB + o] = b4;
+        if (!FUSED && !REP) p.ob_box[e * OB + o] = b4;
     }
     for (int i = tid; i < N; i += WAVE) { el.cand[2 * i] = 0ull; el.cand[2 * i + 1] = 0ull; }
     wave_lds_sync();
@@ -2063,7 +2104,7 @@ __device__ __forceinline__ CarsCtx cars_pre(const SimParams& p, const StepInputs
         }
     }
     wave_lds_sync();
-    if (!FUSED) {
+    if (!FUSED && !REP) {
         for (int i = tid; i < N; i += WAVE) {
             const int g = e * NE + i;
             gmem(p.ob_cand)[2 * g] = el.cand[2 * i];
@@ -2139,15 +2180,21 @@ __device__ __forceinline__ unsigned long long ts_ego_phase(const SimParams& p, c
 // k_cars): bonuses, team mix and env flags (:320-370), the reward / done /
 // status outputs and the state write-back, the observation head (:418-520).
 // Reads only the car LDS (the LiDAR never writes it).
-template <bool TRAFFIC, bool FUSED, class NL, int PK = 1, bool DIMS = false, int NC = 0>
+// REP (k_cars_repeat): sub-step rc->s of a frame-skip window.  The reward is summed, the
+// done bit and the status at the latest done are latched in rc; only the sub-step the env
+// stops at (terminated, truncated, or the window's last) writes the outputs, the env
+// flags, the state, the obstacle table / candidate masks and the observation head.
+template <bool TRAFFIC, bool FUSED, class NL, int PK = 1, bool DIMS = false, int NC = 0, bool REP = false>
 __device__ __forceinline__ void cars_post(const SimParams& p, const Outputs& out, const int e, const CarsLDS& el,
-                                          const NL* nl, CarsCtx& cx) {
+                                          const NL* nl, CarsCtx& cx, RepCarry* rc = nullptr) {
+    static_assert(!REP || (!FUSED && PK == 1 && NC == 0), "frame skip: k_cars' layout");
     const int tid = threadIdx.x & (WAVE - 1);
     const int NE = NC ? NC : p.N;  // agents per env (PK > 1: see cars_pre; NC: compile-time)
     const int npk = PK == 1 ? 1 : (p.E - e < PK ? p.E - e : PK);
     const int N = PK == 1 ? NE : npk * NE;
     const int step_no = cx.step_no, ncnt = cx.ncnt;
-    const bool do_reset = cx.do_reset;
+    bool do_reset = cx.do_reset;
+    if constexpr (REP) do_reset = rc->first_reset;  // (the write-back of the spawns an auto-reset drew)
     const int grp = tid >> 3, sub = tid & 7;
     const unsigned long long gmask = 0xFFull << (grp * 8);
     // ---- bonuses, team mix, flags (:320-370), lane = agent
@@ -2204,11 +2251,22 @@ __device__ __forceinline__ void cars_post(const SimParams& p, const Outputs& out
         const bool terminated = p.respawn ? (succ_cnt > 0 && succ_cnt == alive_cnt) : ((done_m & emask) != 0ull);
         const bool truncated = p.max_steps > 0 && step_e >= p.max_steps;
         if (PK == 1) cx.ended = terminated || truncated;
+        uint8_t done_o = done_i, st_o = st_i;
+        if constexpr (REP) {
+            // acc = r (first sub-step) or acc + r, in sub-step order; the latest done's status
+            rc->rew = rc->s == 0 ? rew_i : rc->rew + rew_i;
+            if (done_i) { rc->any_done = 1; rc->latched = st_i; }
+            if (!cx.ended && rc->s + 1 < rc->n) return;  // (wave-uniform) the window goes on
+            rew_i = rc->rew;
+            done_o = rc->any_done;
+            st_o = rc->any_done ? rc->latched : st_i;
+            if (tid == 0 && rc->substeps) rc->substeps[e] = rc->s + 1;
+        }
         if (in_env) {
             const int g = e * NE + i;
             out.rew[g] = rew_i;
-            out.done[g] = done_i;
-            out.status[g] = st_i;
+            out.done[g] = done_o;
+            out.status[g] = st_o;
         }
         if (PK > 1 ? tid < npk : tid == 0) {
             const int ev = e + (PK > 1 ? tid : 0);
@@ -2222,6 +2280,16 @@ __device__ __forceinline__ void cars_post(const SimParams& p, const Outputs& out
     }
     // ---- the final ego state back to HBM (lane = agent)
     ego_writeback(p, e, NE, N, el, do_reset, tid, DIMS);
+    if constexpr (REP) {
+        // the LiDAR hand-off of the state the env stopped at (cars_pre left it in LDS)
+        const int nob = (!TRAFFIC && NE == 1) ? 0 : N + ncnt;
+        for (int o = tid; o < nob; o += WAVE) p.ob_box[e * p.ob_stride + o] = el.box[o];
+        for (int i = tid; i < N; i += WAVE) {
+            const int g = e * NE + i;
+            gmem(p.ob_cand)[2 * g] = el.cand[2 * i];
+            gmem(p.ob_cand)[2 * g + 1] = el.cand[2 * i + 1];
+        }
+    }
     if (out.state) {
         // the state gather format: the post-step state the root rebuilds the head from
         // (launch_decode_state), instead of the head itself
@@ -2361,6 +2429,66 @@ __global__ __launch_bounds__(WAVE) void k_cars(SimParams p, StepInputs in, Outpu
     CarsCtx cx = cars_pre<TRAFFIC, false, NpcLDS, 1, false, false, true>(p, in, out, e, el, nl);
     wave_lds_sync();
     cars_post<TRAFFIC, false, NpcLDS, 1, true>(p, out, e, el, nl, cx);
+}
+
+// The frame-skip call (mev_step_repeat): up to `repeat` sub-steps of the car part for env
+// e in one launch, the same actions held (the reference's driver, test.py:144-155).  The
+// env's state is read from HBM once, before the first sub-step, and the ego state, the
+// env flags, the outputs, the obstacle table and the observation head are written once,
+// in the sub-step the env stops at (terminated, truncated or the last); in between the
+// state stays where cars_pre / cars_post keep it (CarsLDS, NpcLDS, the counters in the
+// carry).  The NPC phase stores its survivors every sub-step, as in a single step, so the
+// NPC slots in HBM hold what k single steps leave there.  Sub-step s takes its spawn
+// decision from spawn_route[s][e] or the Philox counter + s; an auto-reset draws its
+// routes with the first sub-step's counter.  Nothing between two steps reads a LiDAR
+// distance, so k_lidar casts every env once afterwards, from the state it stopped at.
+// The sub-steps run in a loop around the car part, and everything the loop reads from the
+// kernel's arguments is the same in every sub-step: hoisted out of the loop, those values
+// (several hundred scalars: SimParams, the LDS carve) are live across the whole body and
+// spill into vector lanes (274 VGPRs against k_cars' 91: one wave per SIMD).  So the
+// arguments are one struct, and every sub-step reads it through a pointer to the kernel
+// argument segment the compiler cannot follow across the loop: each sub-step loads what
+// it needs, as k_cars does.
+struct RepeatArgs {
+    SimParams p;
+    StepInputs in;
+    Outputs out;
+    int32_t e_begin, repeat;
+    int32_t* substeps;  // [E] sub-steps executed (nullable)
+};
+// (four waves per SIMD, as k_step: 4096 envs are one round of single-wave workgroups on 256 CUs;
+// with the NPC phase 128 VGPRs would spill to scratch: two)
+template <bool TRAFFIC>
+__global__ __launch_bounds__(WAVE, TRAFFIC ? 2 : 4) void k_cars_repeat(RepeatArgs args) {
+    extern __shared__ __align__(16) unsigned char cars_lds[];
+    __shared__ typename std::conditional<TRAFFIC, NpcLDS, char>::type nl_storage;
+    NpcLDS* nl = nullptr;
+    if constexpr (TRAFFIC) nl = &nl_storage;
+    const int repeat = args.repeat;
+    RepCarry rc{0, repeat, 0, 0, false, 0.0f, 0, 0, nullptr};
+    for (int s = 0; s < repeat; ++s) {
+        typedef const __attribute__((address_space(4))) RepeatArgs CArgs;
+        CArgs* ka = (CArgs*)__builtin_amdgcn_kernarg_segment_ptr();  // (args: the first and only argument)
+        asm volatile("" : "+s"(ka));
+        const RepeatArgs& a = *(const RepeatArgs*)ka;
+        const SimParams& p = a.p;
+        const int e = a.e_begin + xcd_env((int)blockIdx.x, (int)gridDim.x);
+        const CarsLDS el = carve_cars_lds(cars_lds, p.N, cars_k(p), true);
+        StepInputs in = a.in;
+        if (in.spawn_route) in.spawn_route += (size_t)s * p.E;
+        in.rng_counter += (uint64_t)s;
+        rc.s = s;
+        rc.substeps = a.substeps;
+        CarsCtx cx = cars_pre<TRAFFIC, false, NpcLDS, 1, false, false, true, false, 0, true>(p, in, a.out, e, el, nl,
+                                                                                             kDealClasses - 1, &rc);
+        wave_lds_sync();
+        if (s == 0) rc.first_reset = cx.do_reset;
+        cars_post<TRAFFIC, false, NpcLDS, 1, true, 0, true>(p, a.out, e, el, nl, cx, &rc);
+        if (cx.ended) break;
+        rc.step_prev = cx.step_no;
+        rc.npcs_prev = cx.ncnt;
+        wave_lds_sync();  // (cars_post's reads of the car LDS before the next sub-step's writes)
+    }
 }
 
 // ------------------------------------------------------------- LiDAR ---
@@ -3449,13 +3577,18 @@ __global__ __launch_bounds__(WAVE) void k_reset(SimParams p, const uint8_t* mask
         obs_exact_pass<TRAFFIC, TRAFFIC>(p, m, dl, el, nl, ncnt, out.obs + (size_t)e * N * p.D, (size_t)p.D);
 }
 
+// repeat > 0: the frame-skip call's looping car kernel in k_cars' place
 static hipError_t launch_part(const SimParams& p, const StepInputs& in, const Outputs& out, int e0, int e1,
-                              hipStream_t s, const hipEvent_t* ev) {
+                              hipStream_t s, const hipEvent_t* ev, int repeat = 0, int32_t* substeps = nullptr) {
     // k_cars then k_lidar over the envs [e0, e1)
     if (e1 <= e0) return hipSuccess;
     if (ev) (void)hipEventRecord(ev[0], s);
     const unsigned cars_lds = (unsigned)cars_lds_bytes(p.N, cars_k(p), true);
-    if (p.traffic) hipLaunchKernelGGL(k_cars<true>, dim3(e1 - e0), dim3(WAVE), cars_lds, s, p, in, out, e0);
+    if (repeat > 0) {
+        const RepeatArgs ra{p, in, out, e0, repeat, substeps};
+        if (p.traffic) hipLaunchKernelGGL(k_cars_repeat<true>, dim3(e1 - e0), dim3(WAVE), cars_lds, s, ra);
+        else hipLaunchKernelGGL(k_cars_repeat<false>, dim3(e1 - e0), dim3(WAVE), cars_lds, s, ra);
+    } else if (p.traffic) hipLaunchKernelGGL(k_cars<true>, dim3(e1 - e0), dim3(WAVE), cars_lds, s, p, in, out, e0);
     else hipLaunchKernelGGL(k_cars<false>, dim3(e1 - e0), dim3(WAVE), cars_lds, s, p, in, out, e0);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
@@ -3513,6 +3646,12 @@ hipError_t launch_step(const SimParams& p, const SimParams* dp, const StepInputs
     hipError_t e = hipGetLastError();
     if (ev && e == hipSuccess) { (void)hipEventRecord(ev[1], s); (void)hipEventRecord(ev[2], s); }
     return e;
+}
+
+hipError_t launch_step_repeat(const SimParams& p, const StepInputs& in, const Outputs& out, int repeat,
+                              int32_t* substeps, hipStream_t s) {
+    if (repeat < 1) return hipErrorInvalidValue;
+    return launch_part(p, in, out, 0, p.E, s, nullptr, repeat, substeps);
 }
 
 hipError_t launch_serve(const SimParams& p, const SimParams* dp, const ServeArgs& sa, const Outputs& out,

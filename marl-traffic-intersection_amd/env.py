@@ -101,9 +101,17 @@ class IntersectionEnv:
             raise ValueError(f"Expected actions shape (N,2) for multi-agent, got {a.shape}")
         return a
 
-    def step(self, actions, dt: float = 1.0 / 60.0):
+    def step(self, actions, dt: float = 1.0 / 60.0, repeat: int = 1):
+        """repeat > 1: hold the actions for up to `repeat` steps in one device call (frame skip,
+        the loop of the reference's test.py:144-155): the rewards are summed, `collisions` holds
+        each car's status at its latest done (else its last status), the observation -- the
+        LiDAR cast once -- and the rest of `info` are the last executed step's, and
+        info["substeps"] says how many ran (fewer when the episode ended inside the window)."""
         a = self._coerce_actions(actions)
-        res = self.env.step(a[:, 0], a[:, 1], float(dt))
+        if int(repeat) > 1:
+            res = self.env.step_repeat(a[:, 0], a[:, 1], float(dt), int(repeat))
+        else:
+            res = self.env.step(a[:, 0], a[:, 1], float(dt))
         self._traffic_cars = None  # read from the device on first access (traffic_cars)
         obs = np.asarray(res.obs, np.float32)
         rewards = np.asarray(res.rewards, np.float32)
@@ -118,6 +126,8 @@ class IntersectionEnv:
             "done": list(res.done),
             "status": list(res.status),
         }
+        if int(repeat) > 1:
+            info["substeps"] = int(res.substeps)
         if self.traffic_flow:
             return obs[0], first, info["terminated"], info["truncated"], info
         return obs, rewards, info["terminated"], info["truncated"], info

@@ -53,7 +53,11 @@ class VecIntersectionEnv:
                  max_steps: int = 2000, traffic_flow: bool = False, traffic_density: float = 0.5,
                  reward_config: Any = None, ego_routes: Optional[Sequence] = None, max_npcs: int = 32,
                  seed: int = 0, device: int = 0, backend: str = "torch", auto_reset: bool = True,
-                 lidar_fov_deg: float = 360.0, lidar_max_dist: float = 250.0, lidar_step: float = 4.0):
+                 lidar_fov_deg: float = 360.0, lidar_max_dist: float = 250.0, lidar_step: float = 4.0,
+                 frame_skip: int = 1):
+        if not 1 <= int(frame_skip) <= _capi.MEV_MAX_REPEAT:
+            raise ValueError(f"frame_skip must be in 1..{_capi.MEV_MAX_REPEAT}")
+        self.frame_skip = int(frame_skip)
         if backend not in ("torch", "numpy"):
             raise ValueError("backend must be 'torch' or 'numpy'")
         if traffic_flow and num_agents != 1:
@@ -93,6 +97,7 @@ class VecIntersectionEnv:
             self._bind_stream()
         else:
             self._out = self._h.alloc_outputs()
+        self._out_rep = None  # the same buffers plus `substeps`, made at the first frame-skip step
 
     # ----------------------------------------------------------------- utils
     @property
@@ -186,9 +191,15 @@ class VecIntersectionEnv:
         self._h.reset(env_mask=env_mask, obs=self._out["obs"])
         return self._out["obs"]
 
-    def step(self, actions, dt: float = 1.0 / 60.0, copy: bool = False, spawn_route=None):
-        """actions [E, N, 2] (throttle, steer) -> (obs, rewards, terminated, truncated, info)."""
-        o = self._out
+    def step(self, actions, dt: float = 1.0 / 60.0, copy: bool = False, spawn_route=None, repeat: Optional[int] = None):
+        """actions [E, N, 2] (throttle, steer) -> (obs, rewards, terminated, truncated, info).
+        repeat (default: the constructor's frame_skip) > 1 holds the actions for up to that many
+        sub-steps in one device call (Handle.step_repeat): rewards are summed, done / status
+        latched, each env stops at its first terminated or truncated sub-step, the LiDAR is cast
+        once, and info["substeps"] [E] says how many sub-steps each env ran; spawn_route is then
+        [repeat][E]."""
+        n = self.frame_skip if repeat is None else int(repeat)
+        o = self._out if n == 1 else self._repeat_out()
         if self.backend == "torch":
             t = self._torch
             self._bind_stream()
@@ -202,15 +213,32 @@ class VecIntersectionEnv:
             sp = None
             if spawn_route is not None:
                 sp = t.as_tensor(spawn_route, dtype=t.int32, device=o["obs"].device).contiguous()
-            self._h.step(a, float(dt), out=o, spawn_route=sp, auto_reset=self.auto_reset, device=True)
+            if n == 1:
+                self._h.step(a, float(dt), out=o, spawn_route=sp, auto_reset=self.auto_reset, device=True)
+            else:
+                self._h.step_repeat(a, n, float(dt), out=o, spawn_route=sp, auto_reset=self.auto_reset, device=True)
             if copy:
                 o = {k: v.clone() for k, v in o.items()}
         else:
-            self._h.step(actions, float(dt), out=o, spawn_route=spawn_route, auto_reset=self.auto_reset)
+            if n == 1:
+                self._h.step(actions, float(dt), out=o, spawn_route=spawn_route, auto_reset=self.auto_reset)
+            else:
+                self._h.step_repeat(actions, n, float(dt), out=o, spawn_route=spawn_route, auto_reset=self.auto_reset)
             if copy:
                 o = {k: v.copy() for k, v in o.items()}
         info = {"done": o["done"], "status": o["status"], "agents_alive": o["agents_alive"], "step": o["step"]}
+        if n > 1:
+            info["substeps"] = o["substeps"]
         return o["obs"], o["reward"], o["terminated"], o["truncated"], info
+
+    def _repeat_out(self):
+        if self._out_rep is None:
+            if self.backend == "torch":
+                sub = self._torch.zeros(self.num_envs, dtype=self._torch.int32, device=self._out["obs"].device)
+            else:
+                sub = np.zeros(self.num_envs, np.int32)
+            self._out_rep = dict(self._out, substeps=sub)
+        return self._out_rep
 
     def observations(self):
         return self._out["obs"]

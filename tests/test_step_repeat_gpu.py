@@ -1,0 +1,324 @@
+"""Frame skip (mev_step_repeat, include/marlenv.h) against the oracle: one call that holds the
+actions for up to `repeat` sub-steps and casts the LiDAR once must equal the reference's step
+looped as its driver loops it (test.py:144-155; tests/repeat_ref.py) -- every output, the
+sub-step count and the full state after every call, bit for bit per env.  Each scenario
+asserts on the oracle side that it reached the cases it is about (dones inside a window,
+windows stopped early, every crash status), so it cannot pass by covering nothing."""
+import numpy as np
+import pytest
+
+from conftest import STEP_KERNELS, use_step_kernel
+import golden_replay as G
+import oracle_replay as R
+import repeat_ref as RR
+
+pytestmark = pytest.mark.gpu
+
+DT = 1.0 / 60.0
+OUT_KEYS = ("obs", "reward", "done", "status", "terminated", "truncated", "agents_alive", "step")
+
+
+def _handle(mev, E, N, rays, use_team=False, respawn=True, max_steps=2000, traffic=False, density=0.5, max_npcs=32,
+            seed=7):
+    return mev.Handle(num_envs=E, num_agents=N, lidar_rays=rays, obs_dim=127, use_team_reward=int(use_team),
+                      respawn_enabled=int(respawn), max_steps=max_steps, traffic_flow=int(traffic),
+                      traffic_density=density, max_npcs=max_npcs, seed=seed, device=0)
+
+
+def _start(h, meta, traffic=False):
+    """Routes, reset, and the oracles of a handle's envs in the same state."""
+    routes, ids = RR.ego_routes(h.route_id, h.E, h.N)
+    h.set_ego_routes(routes)
+    if traffic:
+        h.set_traffic_routes(ids)
+    h.reset()
+    oracles = []
+    for e in range(h.E):
+        o = R.make_oracle(meta)
+        if traffic:
+            o.set_traffic_routes(ids)
+        o.reset([int(r) for r in routes[e]])
+        oracles.append(o)
+    return RR.RepeatRef(oracles, routes)
+
+
+def _scenario(mev, kernel, E, N, rays, repeat, calls, seed, bias, traffic=False, max_npcs=32, dims=False, **cfg):
+    meta = RR.meta(N, rays, traffic=traffic, **cfg)
+    h = _handle(mev, E, N, rays, traffic=traffic, max_npcs=max_npcs, **cfg)
+    use_step_kernel(mev, h, kernel)
+    ref = _start(h, meta, traffic)
+    if dims:  # per-car sizes, the same on both sides (an auto-reset gives new cars of 54 x 24 again)
+        drng = np.random.default_rng(40)
+        ego = np.stack([drng.uniform(40, 70, (E, N)), drng.uniform(18, 30, (E, N))], -1).astype(np.float32)
+        h.set_car_dims(ego, None)
+        for e, o in enumerate(ref.oracles):
+            egos, npcs, sc = o.get_state()
+            egos["len"], egos["wid"] = ego[e, :, 0], ego[e, :, 1]
+            o.set_state(egos, npcs, sc)
+    rng = np.random.default_rng(seed)
+    for c in range(calls):
+        a, sp = RR.draw(rng, E, N, bias, repeat, traffic)
+        out = h.step_repeat(a, repeat, DT, spawn_route=sp, auto_reset=True)
+        ws = ref.step(a, DT, repeat, sp)
+        st = h.get_state()
+        cd = h.car_dims() if dims else None
+        for e in range(E):
+            RR.check_window(f"call {c} env {e}", out, e, ws[e])
+            R.check_state(f"call {c} env {e}", st, e, ref.oracles[e], cd)
+        if traffic:
+            ref.peak_npcs = max(ref.peak_npcs, max(len(o.get_state()[1]) for o in ref.oracles))
+    h.close()
+    ref.close()
+    return ref
+
+
+@pytest.mark.parametrize("kernel", STEP_KERNELS)
+@pytest.mark.parametrize("device", [False, True], ids=["host", "device"])
+def test_repeat_one_equals_step(mev, kernel, device):
+    E, N, rays = 13, 3, 16
+    a_h = _handle(mev, E, N, rays, use_team=True, max_steps=7)
+    use_step_kernel(mev, a_h, kernel)
+    b_h = _handle(mev, E, N, rays, use_team=True, max_steps=7)
+    b_h.set_step_kernel(kernel)
+    for h in (a_h, b_h):
+        h.set_ego_routes(RR.ego_routes(h.route_id, E, N)[0])
+        h.reset()
+    rng = np.random.default_rng(1)
+    if device:
+        import torch
+        torch.cuda.set_device(0)
+        dev = {x: {k: torch.as_tensor(v).cuda() for k, v in a_h.alloc_outputs().items()} for x in "ab"}
+        dev["a"]["substeps"] = torch.zeros(E, dtype=torch.int32, device="cuda:0")
+    for c in range(20):
+        a, _ = RR.draw(rng, E, N, 0.6)
+        if device:
+            ta = torch.as_tensor(a).cuda()
+            a_h.step_repeat(ta, 1, DT, out=dev["a"], auto_reset=True, device=True)
+            b_h.step(ta, DT, out=dev["b"], auto_reset=True, device=True)
+            a_h.sync()
+            b_h.sync()
+            oa = {k: v.cpu().numpy() for k, v in dev["a"].items()}
+            ob = {k: v.cpu().numpy() for k, v in dev["b"].items()}
+        else:
+            oa = a_h.step_repeat(a, 1, DT, auto_reset=True)
+            ob = b_h.step(a, DT, auto_reset=True)
+        for k in OUT_KEYS:
+            assert G.bits_equal(oa[k], ob[k]), (c, k)
+        assert (oa["substeps"] == 1).all()
+        sa, sb = a_h.get_state(), b_h.get_state()
+        for k in sa:
+            assert G.bits_equal(sa[k], sb[k]), (c, k)
+    assert int(sa["step_count"].max()) <= 7  # (max_steps 7: every env was auto-reset)
+    a_h.close()
+    b_h.close()
+
+
+@pytest.mark.parametrize("kernel", STEP_KERNELS)
+def test_respawn_on_team_reward(mev, kernel):
+    ref = _scenario(mev, kernel, E=24, N=3, rays=32, repeat=5, calls=30, seed=3, bias=0.6, use_team=True,
+                    max_steps=23)
+    print("mid-window dones", ref.mid_dones, "early stops", ref.early_stops, "resets", ref.resets, ref.status_count)
+    assert ref.mid_dones >= 10 and ref.early_stops >= 50
+    assert all(v > 0 for v in ref.status_count.values())
+
+
+@pytest.mark.parametrize("kernel", STEP_KERNELS)
+def test_respawn_off(mev, kernel):
+    ref = _scenario(mev, kernel, E=24, N=3, rays=32, repeat=4, calls=40, seed=5, bias=0.6, use_team=False,
+                    respawn=False, max_steps=200)
+    print("early stops", ref.early_stops, ref.status_count)
+    assert ref.early_stops >= 20
+
+
+@pytest.mark.parametrize("kernel", STEP_KERNELS)
+@pytest.mark.parametrize("dims", [False, True], ids=["54x24", "car_dims"])
+def test_runtime_layout_twelve_agents(mev, kernel, dims):
+    ref = _scenario(mev, kernel, E=6, N=12, rays=16, repeat=6, calls=20, seed=2, bias=0.6, use_team=True,
+                    max_steps=50, dims=dims)
+    print("mid-window dones", ref.mid_dones, "early stops", ref.early_stops, ref.status_count)
+    assert ref.mid_dones >= 20
+
+
+@pytest.mark.parametrize("kernel", STEP_KERNELS)
+@pytest.mark.parametrize("max_npcs", [32, 64])
+def test_traffic_spawn_replay(mev, kernel, max_npcs):
+    ref = _scenario(mev, kernel, E=16, N=1, rays=32, repeat=4, calls=60, seed=11, bias=0.5, traffic=True,
+                    density=5.0, max_steps=150, max_npcs=max_npcs)
+    print("peak NPCs", ref.peak_npcs, "early stops", ref.early_stops, ref.status_count)
+    assert ref.peak_npcs >= 6 and ref.status_count[RR.CRASH_CAR] >= 20 and ref.early_stops >= 8
+
+
+def test_philox_spawner_equals_single_steps(mev):
+    """The on-device spawner: sub-step s draws with the handle's counter + (s - 1) and the call
+    advances it by `repeat`, so for envs that do not end one call leaves the handle exactly where
+    the single steps do -- state, outputs and the draws after it."""
+    E, N, rays, n = 32, 1, 16, 4
+    hs = [_handle(mev, E, N, rays, traffic=True, density=20.0, max_steps=0, seed=5) for _ in range(2)]
+    for h in hs:
+        routes, ids = RR.ego_routes(h.route_id, E, N)
+        h.set_ego_routes(routes)
+        h.set_traffic_routes(ids)
+        h.reset()
+    A, B = hs
+    rng = np.random.default_rng(6)
+    for c in range(6):
+        a, _ = RR.draw(rng, E, N, 0.5)
+        oa = A.step_repeat(a, n, DT, auto_reset=True)
+        acc = any_done = None
+        latched = np.zeros((E, N), np.uint8)
+        for s in range(n):
+            ob = {k: v.copy() for k, v in B.step(a, DT, auto_reset=True).items()}
+            assert not ob["terminated"].any() and not ob["truncated"].any(), (c, s)  # (no env ends here)
+            acc = ob["reward"].copy() if s == 0 else (acc + ob["reward"]).astype(np.float32)
+            any_done = ob["done"].copy() if s == 0 else any_done | ob["done"]
+            latched = np.where(ob["done"] != 0, ob["status"], latched)
+        for k in ("obs", "terminated", "truncated", "agents_alive", "step"):
+            assert G.bits_equal(oa[k], ob[k]), (c, k)
+        assert G.bits_equal(oa["reward"], acc), c
+        assert G.bits_equal(oa["done"], any_done), c
+        assert G.bits_equal(oa["status"], np.where(any_done != 0, latched, ob["status"])), c
+        assert (oa["substeps"] == n).all()
+        sa, sb = A.get_state(), B.get_state()
+        for k in sa:
+            assert G.bits_equal(sa[k], sb[k]), (c, k)
+    assert int(sb["npc_count"].max()) >= 3  # (density 20: the spawner ran)
+    a, _ = RR.draw(rng, E, N, 0.5)
+    oa, ob = A.step(a, DT, auto_reset=True), B.step(a, DT, auto_reset=True)  # the counters agree
+    for k in OUT_KEYS:
+        assert G.bits_equal(oa[k], ob[k]), k
+    for h in hs:
+        h.close()
+
+
+def test_interplay_with_server_snapshot_and_errors(mev):
+    E, N, rays, n = 2, 2, 16, 3
+    meta = RR.meta(N, rays, use_team=True, max_steps=40)
+    h = _handle(mev, E, N, rays, use_team=True, max_steps=40)
+    ref = _start(h, meta)
+    rng = np.random.default_rng(8)
+
+    def plain(tag):
+        a, _ = RR.draw(rng, E, N, 0.6)
+        out = h.step(a, DT, auto_reset=True)
+        ws = ref.step(a, DT, 1)
+        for e in range(E):
+            R.check_step(f"{tag} env {e}", out, e, ws[e])
+
+    def window(tag):
+        a, _ = RR.draw(rng, E, N, 0.6)
+        out = h.step_repeat(a, n, DT, auto_reset=True)
+        ws = ref.step(a, DT, n)
+        for e in range(E):
+            RR.check_window(f"{tag} env {e}", out, e, ws[e])
+
+    plain("served step")
+    assert h.serve_stats()["steps"] == 1 and h.serve_stats()["running"]
+    window("repeat after a served step")
+    assert h.serve_stats()["running"] == 0
+    plain("step after repeat")
+    # snapshot, repeat call, restore, the same call again
+    snap = h.snapshot()
+    a, _ = RR.draw(rng, E, N, 0.6)
+    o1 = {k: v.copy() for k, v in h.step_repeat(a, n, DT, auto_reset=True).items()}
+    ws = ref.step(a, DT, n)
+    for e in range(E):
+        RR.check_window(f"repeat after snapshot env {e}", o1, e, ws[e])
+    g1 = {k: v.copy() for k, v in h.get_outputs().items()}
+    for k in OUT_KEYS:
+        assert G.bits_equal(g1[k], o1[k]), k  # (the call's outputs are the handle's last outputs)
+    s1 = h.get_state()
+    h.restore(snap)
+    o2 = h.step_repeat(a, n, DT, auto_reset=True)
+    for k in o1:
+        assert G.bits_equal(o1[k], o2[k]), k
+    s2 = h.get_state()
+    for k in s1:
+        assert G.bits_equal(s1[k], s2[k]), k
+    # errors leave the handle untouched
+    for bad in (dict(repeat=0), dict(repeat=mev._capi.MEV_MAX_REPEAT + 1), dict(repeat=n, gather=True)):
+        with pytest.raises(mev.MevError):
+            h.step_repeat(a, bad.pop("repeat"), DT, auto_reset=True, **bad)
+    plain("step after the refused calls")
+    h.close()
+    ref.close()
+
+
+def _vec_layer(mev, backend):
+    import pkgload
+    pkgload.load()
+    from marl_traffic_intersection_amd import vec_env
+    E, N, rays, n = 4, 2, 16, 3
+    meta = RR.meta(N, rays, use_team=True, max_steps=10)
+    v = vec_env.VecIntersectionEnv(E, N, lidar_rays=rays, use_team_reward=True, max_steps=10, backend=backend,
+                                   frame_skip=n)
+    ref = _start(v.handle, meta)
+    rng = np.random.default_rng(9)
+    for c in range(15):
+        a, _ = RR.draw(rng, E, N, 0.6)
+        obs, rew, term, trunc, info = v.step(a)
+        if backend == "torch":
+            obs, rew, term, trunc = (x.cpu().numpy() for x in (obs, rew, term, trunc))
+            info = {k: x.cpu().numpy() for k, x in info.items()}
+        out = dict(obs=obs, reward=rew, terminated=term, truncated=trunc, **info)
+        ws = ref.step(a, DT, n)
+        for e in range(E):
+            RR.check_window(f"{backend} call {c} env {e}", out, e, ws[e])
+    assert ref.early_stops >= 4  # (max_steps 10, windows of 3: the fourth window of an episode stops at 1)
+    # a per-call repeat of 1 is today's step
+    a, _ = RR.draw(rng, E, N, 0.6)
+    obs, rew, term, trunc, info = v.step(a, repeat=1)
+    assert "substeps" not in info
+    v.close()
+    ref.close()
+
+
+def test_vec_env_numpy_frame_skip(mev):
+    _vec_layer(mev, "numpy")
+
+
+def test_vec_env_torch_frame_skip(mev):
+    import torch
+    if not torch.cuda.is_available():
+        pytest.skip("torch does not see the device")
+    _vec_layer(mev, "torch")
+
+
+def test_drop_in_env_step_repeat(mev):
+    import pkgload
+    pkgload.load()
+    from marl_traffic_intersection_amd import cpp_backend, env as env_mod
+    E, N, rays, n = 4, 2, 16, 3
+    meta = RR.meta(N, rays, use_team=True, max_steps=10)
+    status_names = ("ALIVE", "DEAD", "SUCCESS", "CRASH_WALL", "CRASH_LINE", "CRASH_CAR")
+    envs, oracles, routes = [], [], None
+    for e in range(E):
+        d = env_mod.IntersectionEnv({"num_agents": N, "use_team_reward": True, "max_steps": 10})
+        d.env.lidars = [cpp_backend.Lidar(rays)] * N
+        o = R.make_oracle(meta)
+        routes = [o.route_id(s - 1, 12 + t - 1) for s, t in RR.ROUTES3[:N]]  # env.py's default routes
+        o.reset(routes)
+        envs.append(d)
+        oracles.append(o)
+    rng = np.random.default_rng(10)
+    early = 0
+    for c in range(15):
+        a, _ = RR.draw(rng, E, N, 0.6)
+        for e, (d, o) in enumerate(zip(envs, oracles)):
+            obs, rew, term, trunc, info = d.step(a[e], DT, repeat=n)
+            w = RR.repeat_step(o, a[e], DT, n)
+            tag = f"call {c} env {e}"
+            assert G.bits_equal(np.asarray(obs, np.float32), w["obs"]), tag
+            assert G.bits_equal(np.asarray(rew, np.float32), w["rew"]), tag
+            assert (int(term), int(trunc), info["agents_alive"], info["step"], info["substeps"]) == \
+                (w["terminated"], w["truncated"], w["agents_alive"], w["step"], w["substeps"]), tag
+            assert info["status"] == [status_names[s] for s in w["status"]], tag
+            assert info["done"] == [int(x) for x in w["done"]], tag
+            assert list(info["collisions"].values()) == [status_names[s] for s in w["status"]], tag
+            early += w["substeps"] < n
+            if term or trunc:  # no auto-reset in the drop-in env: the caller resets
+                d.reset()
+                d.env.lidars = [cpp_backend.Lidar(rays)] * N
+                o.reset(routes)
+    assert early >= 4
+    for d in envs:
+        d.close()
