@@ -288,11 +288,11 @@ int mev_config_default(mev_config* c) {
     memset(c, 0, sizeof(*c));
     c->num_envs = 1;
     c->num_agents = 1;
-    c->num_lanes = 3;
+    c->num_lanes = mev::kRefNumLanes;
     c->lidar_rays = 96;  // cpp/IntersectionEnv.cpp:113-116
     c->lidar_fov_deg = 360.0f;
-    c->lidar_max_dist = 250.0f;
-    c->lidar_step = 4.0f;
+    c->lidar_max_dist = mev::kRefLidarMaxDist;
+    c->lidar_step = mev::kRefLidarStep;
     c->obs_dim = 0;
     c->traffic_flow = 0;
     c->traffic_density = 0.5f;  // cpp/IntersectionEnv.h:35
@@ -324,25 +324,27 @@ int mev_create(const mev_config* cfg, mev_handle** out) {
     HIP_TRY(hipSetDevice(c.device));
     // LiDAR probe distances exactly as Lidar.cpp:33 accumulates them (validated
     // before any allocation: this error path owns nothing)
+    // (the world's derived values, the probe count among them: mev_refworld.h)
+    const mev::WorldConsts wc = mev::world_consts(c.num_lanes, c.lidar_max_dist, c.lidar_step);
+    if (wc.lidar_steps > mev::kMaxMarchProbes) return fail(MEV_E_INVALID, "lidar_max_dist / lidar_step too large");
+    const bool dist_mul_exact = wc.dist_exact;
     std::vector<float> dists;
-    bool dist_mul_exact = true;
-    for (float dist = 0.0f; dist < c.lidar_max_dist; dist += c.lidar_step) {
-        if (dist != float(dists.size()) * c.lidar_step) dist_mul_exact = false;
-        dists.push_back(dist);
-        if (dists.size() > (1u << 20)) return fail(MEV_E_INVALID, "lidar_max_dist / lidar_step too large");
-    }
+    dists.reserve(size_t(wc.lidar_steps));
+    for (float dist = 0.0f; int(dists.size()) < wc.lidar_steps; dist += c.lidar_step) dists.push_back(dist);
 
     auto* h = new mev_handle();
     h->cfg = c;
     {
         const char* nd = getenv("MEV_NO_DEAL");
         h->deal_on = !(nd && nd[0] == '1');
+        const char* nw = getenv("MEV_NO_WORLD_CONST");
+        h->sp.no_world_const = nw && nw[0] == '1';
     }
     if (h->cfg.traffic_density < 0.0f) h->cfg.traffic_density = 0.0f;  // configure_traffic (:56-60)
     h->D = D;
     h->lidar_slots = std::min(c.lidar_rays, D - mev::OBS_HEAD);
     {  // the compact gather format's LiDAR codes -> floats (Lidar::normalized, Lidar.cpp:92-98)
-        const float inv = (c.lidar_max_dist > 0.0f) ? (1.0f / c.lidar_max_dist) : 0.0f;
+        const float inv = wc.lidar_inv;
         h->h_lidar_table.assign(256, 0.0f);
         h->h_lidar_table[0] = c.lidar_max_dist * inv;  // no hit: max_dist
         for (size_t k = 0; k < dists.size() && k + 1 < size_t(mev::kLidarCodeDead); ++k)
@@ -498,21 +500,21 @@ int mev_create(const mev_config* cfg, mev_handle** out) {
     // parameters
     p.E = E; p.N = N; p.R = c.lidar_rays; p.K = c.max_npcs; p.D = D;
     p.lidar_slots = h->lidar_slots;
-    p.num_lanes = c.num_lanes;
-    p.irw = int(c.num_lanes * int(mev::LANE_WIDTH_PX));
-    p.line_stop = int(c.num_lanes * int(mev::LANE_WIDTH_PX)) + int(mev::CORNER_RADIUS);  // LineMask.cpp:52-54
-    p.rw = c.num_lanes * mev::LANE_WIDTH_PX;  // RoadGeometry.h:16
+    p.num_lanes = wc.num_lanes;
+    p.irw = wc.irw;
+    p.line_stop = wc.line_stop;
+    p.rw = wc.rw;
     p.use_team = c.use_team_reward;
     p.respawn = c.respawn_enabled;
     p.traffic = c.traffic_flow;
     p.max_steps = c.max_steps;
     p.k_prog = c.reward[0]; p.v_min = c.reward[1]; p.k_stuck = c.reward[2]; p.k_cv = c.reward[3];
     p.k_co = c.reward[4]; p.k_succ = c.reward[5]; p.k_sm = c.reward[6]; p.alpha = c.reward[7];
-    p.max_progress = mev::hypotf(float(mev::WIDTH), float(mev::HEIGHT));  // IntersectionEnv.cpp:22
-    p.lidar_max = c.lidar_max_dist;
-    p.lidar_step = c.lidar_step;
-    p.lidar_inv = (c.lidar_max_dist > 0.0f) ? (1.0f / c.lidar_max_dist) : 0.0f;  // Lidar.cpp:94
-    p.lidar_steps = int(dists.size());
+    p.max_progress = mev::world_max_progress();
+    p.lidar_max = wc.lidar_max;
+    p.lidar_step = wc.lidar_step;
+    p.lidar_inv = wc.lidar_inv;
+    p.lidar_steps = wc.lidar_steps;
     p.ob_stride = N + c.max_npcs;
     p.dist_tab = d_dist;
     p.seed = c.seed;

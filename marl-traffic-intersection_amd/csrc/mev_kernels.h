@@ -18,6 +18,7 @@
 #include <stdint.h>
 
 #include "mev_plan.h"
+#include "mev_refworld.h"
 
 namespace mev {
 
@@ -110,6 +111,10 @@ struct SimParams {
     float max_progress;      // hypot(750, 750)
     float lidar_max, lidar_step, lidar_inv;
     int32_t lidar_steps;      // S = number of march probes (dist < max_dist)
+    // host side: never choose the kernels that hold the reference's world at compile time
+    // (MEV_NO_WORLD_CONST=1 at mev_create).  (In the four bytes that pad dist_tab to its
+    // alignment: every other field keeps its offset.)
+    int32_t no_world_const;
     const float* dist_tab;    // [S] accumulated probe distances, or null when dist_k == k*step exactly
     uint64_t seed;
     EgoSoA ego;
@@ -187,8 +192,17 @@ struct StepInputs {
 
 // The kernels launch_step and launch_serve use for p, their launches and what the
 // getters report: plan_step (mev_plan.h) of p's shape.
+// whether p's world is kRefWorld, field by field (what StepWorld<true> replaces with constants)
+inline bool reference_world(const SimParams& p) {
+    constexpr WorldConsts w = kRefWorld;
+    return p.num_lanes == w.num_lanes && p.irw == w.irw && p.line_stop == w.line_stop && p.rw == w.rw &&
+           p.lidar_max == w.lidar_max && p.lidar_step == w.lidar_step && p.lidar_inv == w.lidar_inv &&
+           p.lidar_steps == w.lidar_steps && p.dist_tab == nullptr && p.max_progress == world_max_progress() &&
+           p.beam_cull == 1;
+}
 inline StepShape step_shape(const SimParams& p) {
-    return {p.E, p.N, p.R, p.K, p.lidar_slots, p.traffic, p.dims, p.step_kernel, p.step_pack, p.step_split};
+    return {p.E, p.N, p.R, p.K, p.lidar_slots, p.traffic, p.dims, p.step_kernel, p.step_pack, p.step_split,
+            !p.no_world_const && !p.dims && reference_world(p)};
 }
 inline StepPlan plan_step(const SimParams& p) { return plan_step(step_shape(p)); }
 // ev (nullable): three events recorded before k_cars, between k_cars and k_lidar, after k_lidar

@@ -274,10 +274,10 @@ __device__ inline int reset_route(const SimParams& p, uint64_t ctr, int e, int i
 // host, e.g. step 4) we multiply, otherwise read the host-accumulated table.
 // TAB: the handle's probe distances are not exactly k*step (they accumulate
 // dist += step like Lidar.cpp:33), read them from the table
-template <bool TAB>
+template <bool TAB, bool WC = false>
 __device__ inline float march_dist(const SimParams& p, int k) {
     if constexpr (TAB) return gmem(p.dist_tab)[k];
-    else return (float)k * p.lidar_step;
+    else return (float)k * StepWorld<WC>::lidar_step(p);
 }
 
 // XCD-aware env order: the dispatcher deals workgroups round-robin over the 8
@@ -1532,13 +1532,15 @@ struct RepCarry {
 // cars_pre runs it over its agents 8 per pass; the traffic early split's LiDAR wave
 // runs it for its envs' egos, one env per lane group (el then differs per group).
 // (EARLY: eroute .. ga1 are the group-layout registers of the state round, see cars_pre)
-template <bool EARLY, bool DIMS>
+// (WC: the reference's world at compile time, StepWorld)
+template <bool EARLY, bool DIMS, bool WC = false>
 __device__ __forceinline__ void ego_phase1(const SimParams& p, const StepInputs& in, const CarsLDS& el, const int i,
                                            const bool act, const int ii, const int grp, const int sub,
                                            const unsigned long long gmask, const int eroute, const int epidx,
                                            const Kin& gk, const uint8_t galive_b, const float ga0, const float ga1) {
     constexpr bool early = EARLY;
     constexpr bool dims = DIMS;
+    using W = StepWorld<WC>;
     const int plen = p.rt.plen;
     const GF2 P = gf2(p.rt.path + (size_t)(early ? eroute : el.route[ii]) * (2 * p.rt.row));
     const int pidx0 = early ? epidx : el.pidx[ii];
@@ -1633,7 +1635,7 @@ __device__ __forceinline__ void ego_phase1(const SimParams& p, const StepInputs&
         float r_prog = 0.0f;
         if (prev > 0.0f) {
             const float progress = prev - cur;
-            const float normalized = (p.max_progress > 0.0f) ? (progress / p.max_progress) : 0.0f;
+            const float normalized = (W::max_progress(p) > 0.0f) ? (progress / W::max_progress(p)) : 0.0f;
             r_prog = p.k_prog * normalized;
         }
         const float speed_ms = (k.v * FPS) / SCALE;
@@ -1666,10 +1668,10 @@ __device__ __forceinline__ void ego_phase1(const SimParams& p, const StepInputs&
         const bool corner = sub < 4;
         const float px_ = corner ? qx : 0.5f * (qx + rx), py_ = corner ? qy : 0.5f * (qy + ry);
         const float M = 100.0f;
-        const bool lm = is_line_px((int)px_, (int)py_, p.line_stop);
+        const bool lm = is_line_px((int)px_, (int)py_, W::line_stop(p));
         oos_q = alive && corner && (qx < -M || qx > float(WIDTH) + M || qy < -M || qy > float(HEIGHT) + M);
-        off_q = alive && corner && !is_on_road(qx, qy, p.rw);
-        line_q = alive && ((corner && hits_yellow_line(qx, qy, p.rw)) || lm);
+        off_q = alive && corner && !is_on_road(qx, qy, W::rw(p));
+        line_q = alive && ((corner && hits_yellow_line(qx, qy, W::rw(p))) || lm);
     }
     const bool any_oos = (ballot(oos_q) & gmask) != 0ull;
     const bool any_off = (ballot(off_q) & gmask) != 0ull;
@@ -1722,8 +1724,9 @@ __device__ __forceinline__ void ego_phase1(const SimParams& p, const StepInputs&
 // sub-step on nothing is loaded from HBM: the ego state is what cars_post left in el, the
 // NPCs are the survivors in nl, the counters come in rc; the obstacle table and candidate
 // masks stay in LDS (cars_post publishes them in the sub-step the env stops at).
+// WC: the reference's world at compile time (StepWorld / StepRows; k_step's rows with it).
 template <bool TRAFFIC, bool FUSED, class NL, int PK = 1, bool EARLY = false, bool ESPLIT = false, bool DIMS = false,
-          bool TSC = false, int NC = 0, bool REP = false>
+          bool TSC = false, int NC = 0, bool REP = false, bool WC = false>
 __device__ __forceinline__ CarsCtx cars_pre(const SimParams& p, const StepInputs& in, const Outputs& out, const int e,
                                             const CarsLDS& el, NL* nl, int npc_cls = kDealClasses - 1,
                                             const RepCarry* rc = nullptr) {
@@ -1971,7 +1974,7 @@ __device__ __forceinline__ CarsCtx cars_pre(const SimParams& p, const StepInputs
         const int i = i0 + grp;
         const bool act = i < N;
         const int ii = act ? i : 0;  // idle groups mirror agent 0 so every lane reaches the ballots
-        ego_phase1<early, dims>(p, in, el, i, act, ii, grp, sub, gmask, eroute, epidx, gk, galive_b, ga0, ga1);
+        ego_phase1<early, dims, WC>(p, in, el, i, act, ii, grp, sub, gmask, eroute, epidx, gk, galive_b, ga0, ga1);
     }
     // The LDS DMA of round B has landed (the loop waited for it before reading the
     // window), but the compiler cannot see that on every path into here, and with an
@@ -2110,7 +2113,7 @@ __device__ __forceinline__ CarsCtx cars_pre(const SimParams& p, const StepInputs
                 const int4 bx = el.box[o];
                 const float ddx = fmaxf(fmaxf((float)bx.x - cx, cx - (float)bx.y), 0.0f);
                 const float ddy = fmaxf(fmaxf((float)bx.z - cy, cy - (float)bx.w), 0.0f);
-                const float reach = p.lidar_max + 2.0f;
+                const float reach = StepWorld<WC>::lidar_max(p) + 2.0f;
                 if (ddx * ddx + ddy * ddy <= reach * reach) atomicOr(&el.cand[2 * a + (o >> 6)], 1ull << (o & 63));
             }
         }
@@ -2196,10 +2199,15 @@ __device__ __forceinline__ unsigned long long ts_ego_phase(const SimParams& p, c
 // done bit and the status at the latest done are latched in rc; only the sub-step the env
 // stops at (terminated, truncated, or the window's last) writes the outputs, the env
 // flags, the state, the obstacle table / candidate masks and the observation head.
-template <bool TRAFFIC, bool FUSED, class NL, int PK = 1, bool DIMS = false, int NC = 0, bool REP = false>
+// WCP1 > 0: plain observation rows of 31 + WCP1 columns, every one a LiDAR slot, at compile time
+// (StepWorld / StepRows; k_step's rows with the reference's world).
+template <bool TRAFFIC, bool FUSED, class NL, int PK = 1, bool DIMS = false, int NC = 0, bool REP = false,
+          int WCP1 = 0>
 __device__ __forceinline__ void cars_post(const SimParams& p, const Outputs& out, const int e, const CarsLDS& el,
                                           const NL* nl, CarsCtx& cx, RepCarry* rc = nullptr) {
     static_assert(!REP || (!FUSED && PK == 1 && NC == 0), "frame skip: k_cars' layout");
+    using RW = StepRows<(WCP1 > 0), WCP1>;
+    static_assert(WCP1 == 0 || (!TRAFFIC && FUSED && !DIMS), "constant rows: the compile-time layout's head writes");
     const int tid = threadIdx.x & (WAVE - 1);
     const int NE = NC ? NC : p.N;  // agents per env (PK > 1: see cars_pre; NC: compile-time)
     const int npk = PK == 1 ? 1 : (p.E - e < PK ? p.E - e : PK);
@@ -2302,7 +2310,7 @@ __device__ __forceinline__ void cars_post(const SimParams& p, const Outputs& out
             gmem(p.ob_cand)[2 * g + 1] = el.cand[2 * i + 1];
         }
     }
-    if (out.state) {
+    if (RW::state(out)) {
         // the state gather format: the post-step state the root rebuilds the head from
         // (launch_decode_state), instead of the head itself
         const size_t n = (size_t)out.state_n;
@@ -2383,7 +2391,7 @@ __device__ __forceinline__ void cars_post(const SimParams& p, const Outputs& out
             const float f2 = (self ? v : ov - v) / PHYSICS_MAX_SPEED;
             const float f3 = self ? h / PI_F : wr;
             if (act) {
-                float* row = out.obs + (size_t)(e * NE + i) * out.obs_ld;
+                float* row = out.obs + (size_t)(e * NE + i) * RW::obs_ld(out);
                 constexpr bool HD = FUSED;  // (k_cars' heads stay plain: its rows' blocks come from a second kernel)
                 if (!alv) {
                     for (int cc = sub; cc < OBS_HEAD; cc += 8) obs_store<HD>(row + cc, 0.0f);
@@ -2402,7 +2410,7 @@ __device__ __forceinline__ void cars_post(const SimParams& p, const Outputs& out
                         for (int q = 0; q < 5; ++q) obs_store<HD>(o + q, 0.0f);
                     }
                 }
-                for (int cc = OBS_HEAD + p.lidar_slots + sub; cc < out.obs_ld; cc += 8) obs_store<HD>(row + cc, 0.0f);
+                for (int cc = OBS_HEAD + RW::lidar_slots(p) + sub; cc < RW::obs_ld(out); cc += 8) obs_store<HD>(row + cc, 0.0f);
             }
         }
     } else if constexpr (!kFew) {
@@ -2760,11 +2768,16 @@ struct LidarSrcLdsEnvs {
 // P1 = 1: R is a multiple of 64 (the dense phase-1 walk below is not compiled in); P1 = 2: R is
 // not (the dense walk for every pool, the agent-pair loop not compiled in); P1 >= 64: R = P1, a
 // compile-time beam count (64: config 3, 96: the reference's default LiDAR, 128: config 5).
-template <bool TAB, int ILP, class Src, int NPT = LIDAR_NPR, bool HELP = false, int PART = 0, int P1 = 0>
+// WC: the reference's world and plain rows at compile time (StepWorld / StepRows; k_step's rows with them).
+template <bool TAB, int ILP, class Src, int NPT = LIDAR_NPR, bool HELP = false, int PART = 0, int P1 = 0,
+          bool WC = false>
 __device__ __forceinline__ void lidar_body(const SimParams& p, const Outputs& out, const Src& src, const int G,
                                            const int a0, const int na, const int lane, unsigned char* base,
                                            const LidarLayout& lay, const unsigned long long redo = 0ull,
                                            const unsigned long long alive_in = 0ull) {
+    static_assert(!WC || (!TAB && P1 >= WAVE), "the reference's world: no distance table, the beams at compile time");
+    using W = StepWorld<WC>;
+    using RW = StepRows<WC, P1>;
     const int R = P1 >= WAVE ? P1 : p.R;  // (P1 >= 64: exactly that many beams, a compile-time count)
     const int LS = P1 >= WAVE ? P1 : p.lidar_slots;  // (and every beam in the observation: fixed_r)
     float4* ag = reinterpret_cast<float4*>(base + lay.ag);
@@ -2790,19 +2803,19 @@ __device__ __forceinline__ void lidar_body(const SimParams& p, const Outputs& ou
     if (PART != 2 && __popcll(am) != na) {  // dead agents: LiDAR block of the observation is zero (:425-427)
         for (int j = 0; j < na; ++j) {
             if ((am >> j) & 1ull) continue;
-            if (out.lidar_u8) {  // compact gather format: the dead-agent code
-                uint8_t* crow = out.lidar_u8 + (size_t)(a0 + j) * LS;
+            if (RW::lidar_u8(out)) {  // compact gather format: the dead-agent code
+                uint8_t* crow = RW::lidar_u8(out) + (size_t)(a0 + j) * LS;
                 for (int b = lane; b < LS; b += WAVE) crow[b] = (uint8_t)kLidarCodeDead;
                 continue;
             }
-            float* row = out.obs + (size_t)(a0 + j) * out.obs_ld + OBS_HEAD;
+            float* row = out.obs + (size_t)(a0 + j) * RW::obs_ld(out) + OBS_HEAD;
             for (int b = lane; b < LS; b += WAVE) row[b] = 0.0f;
         }
     }
     wave_lds_sync();
-    const float stp = p.lidar_step;
-    const int S = p.lidar_steps;
-    const float rwf = (float)p.irw;
+    const float stp = W::lidar_step(p);
+    const int S = W::lidar_steps(p);
+    const float rwf = (float)W::irw(p);
     const float inv_stp = __builtin_amdgcn_rcpf(stp);
     const float crf = CORNER_RADIUS, ccen = rwf + crf;
     const float cr2p1 = crf * crf + 1.0f;
@@ -3148,7 +3161,7 @@ __device__ __forceinline__ void lidar_body(const SimParams& p, const Outputs& ou
     // a ray outside it never meets the slab, so none of its probes can land in
     // the box.
     const float rel0 = src.rel(0);
-    const bool all_beams = R == 1 || !p.beam_cull;  // (no linear model of the offsets: SimParams::beam_cull)
+    const bool all_beams = R == 1 || !W::beam_cull(p);  // (no linear model of the offsets: SimParams::beam_cull)
     const float dphi = R > 1 ? (src.rel(R - 1) - rel0) / (float)(R - 1) : 1.0f;
     const float idphi = 1.0f / dphi;
     const float period = 6.28318531f * idphi;  // beam indices per revolution
@@ -3259,8 +3272,9 @@ __device__ __forceinline__ void lidar_body(const SimParams& p, const Outputs& ou
                 for (int kk = ka; kk <= kb; ++kk) {
                     // a runtime table test here, not march_dist<TAB>: measured 4 us per
                     // step faster in k_step, and without it k_lidar's 64-VGPR
-                    // allocation spills ~180 registers
-                    const float d = p.dist_tab ? gmem(p.dist_tab)[kk] : (float)kk * p.lidar_step;
+                    // allocation spills ~180 registers (WC: the pointer is null, and still tested
+                    // here: StepWorld)
+                    const float d = p.dist_tab ? gmem(p.dist_tab)[kk] : (float)kk * W::lidar_step(p);
                     const int px = (int)(a.x + dd.x * d), py = (int)(a.y + dd.y * d);
                     if (px >= bx.x && px <= bx.y && py >= bx.z && py <= bx.w) {
                         atomicMin(&res[slot], (kk << 1) | 1);
@@ -3278,10 +3292,10 @@ __device__ __forceinline__ void lidar_body(const SimParams& p, const Outputs& ou
     if (Src::kBoxLds) return;
 #endif
     // 3d: Lidar::normalized (:92-98), the LiDAR block of each alive agent's row
-    if (out.lidar_u8) {  // compact gather format: one code per beam (0 no hit, k + 1 hit at probe k)
+    if (RW::lidar_u8(out)) {  // compact gather format: one code per beam (0 no hit, k + 1 hit at probe k)
         for (int j = 0; j < nal; ++j) {
             const int g = __float_as_int(ag[j].w);
-            uint8_t* crow = out.lidar_u8 + (size_t)g * LS;
+            uint8_t* crow = RW::lidar_u8(out) + (size_t)g * LS;
             for (int b = lane; b < LS; b += WAVE) {
                 const int r = res[j * R + b];
                 crow[b] = (uint8_t)((r & 1) ? (r >> 1) + 1 : 0);
@@ -3297,8 +3311,9 @@ __device__ __forceinline__ void lidar_body(const SimParams& p, const Outputs& ou
         // (the LiDAR constants read once and pinned in VGPRs by one asm: the compiler cannot
         // rematerialize an asm result, so it stops re-issuing their scalar loads for every
         // row -- three dependent scalar-cache round trips per row)
-        float l_max = p.lidar_max, l_step = p.lidar_step, l_inv = p.lidar_inv;
-        asm volatile("" : "+v"(l_max), "+v"(l_step), "+v"(l_inv));
+        // (WC: they are literals, nothing to pin)
+        float l_max = W::lidar_max(p), l_step = W::lidar_step(p), l_inv = W::lidar_inv(p);
+        if constexpr (!WC) asm volatile("" : "+v"(l_max), "+v"(l_step), "+v"(l_inv));
         auto row_value = [&](int r) {
             const float dk = TAB ? gmem(p.dist_tab)[r >> 1] : (float)(r >> 1) * l_step;
             return ((r & 1) ? dk : l_max) * l_inv;
@@ -3311,17 +3326,17 @@ __device__ __forceinline__ void lidar_body(const SimParams& p, const Outputs& ou
             for (int u = 0; u < 8; ++u) {
                 if (j0 + u < nal && beam) {
                     const int g = __builtin_amdgcn_readlane(gl, j0 + u);
-                    obs_store<true>(&out.obs[(size_t)g * out.obs_ld + OBS_HEAD + lane], row_value(rr[u]));
+                    obs_store<true>(&out.obs[(size_t)g * RW::obs_ld(out) + OBS_HEAD + lane], row_value(rr[u]));
                 }
             }
         }
     } else {
         for (int j = 0; j < nal; ++j) {
             const int g = __float_as_int(ag[j].w);
-            float* row = out.obs + (size_t)g * out.obs_ld + OBS_HEAD;
+            float* row = out.obs + (size_t)g * RW::obs_ld(out) + OBS_HEAD;
             for (int b = lane; b < LS; b += WAVE)
-                obs_store<true>(row + b,
-                             ((res[j * R + b] & 1) ? march_dist<TAB>(p, res[j * R + b] >> 1) : p.lidar_max) * p.lidar_inv);
+                obs_store<true>(row + b, ((res[j * R + b] & 1) ? march_dist<TAB, WC>(p, res[j * R + b] >> 1) : W::lidar_max(p)) *
+                                             W::lidar_inv(p));
         }
     }
 }
@@ -3440,8 +3455,10 @@ constexpr int kPrioTsplitCars = MEV_TSPLIT_CPRIO;  // the traffic early split's 
 constexpr int kPrioEsplitCarPhase = 1;
 // P1 (lidar_body's): 1 a LiDAR of a multiple of 64 beams, 2 of another beam count, >= 64 exactly P1
 // beams (64: config 3, 96: the reference's default LiDAR, 128: config 5)
+// WC: the handle's world is the reference's and the call's rows are plain (StepWorld / StepRows, mev_refworld.h):
+// the one-wave-per-env kernels of NC = 8 agents with P1 = 64 / 128 beams, without the table
 template <bool TRAFFIC, bool TAB, int NM, int KM = MAXK, int PK = 1, bool SPLIT = false, bool ESPLIT = false, int P1 = 0,
-          int NC = 0>
+          int NC = 0, bool WC = false>
 __global__ __launch_bounds__((TRAFFIC && ESPLIT) ? (PK + 1) * WAVE : (SPLIT ? 2 * WAVE : WAVE),
                              (TRAFFIC && ESPLIT) ? kTsplitWpe
                                                  : ((ESPLIT && PK == 1) ? kEsplitWpe : (SPLIT ? kSplitWpe : 4))) void k_step(
@@ -3471,6 +3488,7 @@ __global__ __launch_bounds__(SPLIT ? 2 * WAVE : WAVE, SPLIT ? kSplitWpe : 4) voi
     constexpr int PK = 1;
     constexpr bool ESPLIT = false;
     constexpr int P1 = SP1, NC = SNC;  // (the beams and agents per env at compile time, as in k_step)
+    constexpr bool WC = false;          // (the world and the rows at run time)
     const int lane = threadIdx.x & (WAVE - 1);
     const bool w0 = threadIdx.x < WAVE;
     ServeBox* box = sa.box;
@@ -3638,9 +3656,9 @@ static hipError_t launch_part(const SimParams& p, const StepInputs& in, const Ou
 // alone leaves its .text the same bytes.)
 using StepFn = void (*)(const SimParams*, StepInputs, Outputs);
 using ServeFn = void (*)(const SimParams*, ServeArgs, Outputs);
-#define MEV_STEP_TAB(T, NM, KM, PK, S, ES, P1, NC) k_step<T, true, NM, KM, PK, S, ES, P1, NC>,
-#define MEV_STEP_NOTAB(T, NM, KM, PK, S, ES, P1, NC) k_step<T, false, NM, KM, PK, S, ES, P1, NC>,
-#define MEV_SERVE_FNS(T, NM, KM, PK, S, ES, P1, NC) \
+#define MEV_STEP_TAB(T, NM, KM, PK, S, ES, P1, NC, WC) k_step<T, true, NM, KM, PK, S, ES, P1, NC, false>,
+#define MEV_STEP_NOTAB(T, NM, KM, PK, S, ES, P1, NC, WC) k_step<T, false, NM, KM, PK, S, ES, P1, NC, WC != 0>,
+#define MEV_SERVE_FNS(T, NM, KM, PK, S, ES, P1, NC, WC) \
     {k_serve<T, true, NM, KM, S, P1, NC>, k_serve<T, false, NM, KM, S, P1, NC>},
 static const StepFn kStepFns[2][sizeof kStepKeys / sizeof kStepKeys[0]] = {{MEV_STEP_KERNELS(MEV_STEP_TAB)},
                                                                            {MEV_STEP_KERNELS(MEV_STEP_NOTAB)}};
@@ -3651,9 +3669,12 @@ static const ServeFn kServeFns[][2] = {MEV_SERVE_KERNELS(MEV_SERVE_FNS)};
 
 hipError_t launch_step(const SimParams& p, const SimParams* dp, const StepInputs& in, const Outputs& out,
                        hipStream_t s, const hipEvent_t* ev) {
-    const StepPlan pl = plan_step(p);
+    StepPlan pl = plan_step(p);
     if (pl.path == 0) return hipErrorInvalidValue;
     if (pl.path == 1) return launch_part(p, in, out, 0, p.E, s, ev);
+    // the rows at compile time (StepKey::wc) only for this call's plain rows: 31 + R floats, every
+    // column written by the step, neither compact gather format
+    if (!(out.obs_ld == OBS_HEAD + p.R && p.D == out.obs_ld && !out.lidar_u8 && !out.state)) pl.step.key.wc = 0;
     const int row = key_row(kStepKeys, pl.step.key);
     if (row < 0) return hipErrorInvalidValue;  // (a plan without a kernel: a bug, never another kernel)
     if (ev) (void)hipEventRecord(ev[0], s);

@@ -13,6 +13,7 @@ struct StepShape {
     int E, N, R, K, lidar_slots;      // envs, agents, beams, NPC slots, beams in the observation
     int traffic, dims;                // traffic mode; some car is not 54 x 24
     int step_kernel, step_pack, step_split;  // mev_set_step_kernel / _pack / _split (0: automatic)
+    int world = 0;                    // the reference's world (kRefWorld, mev_refworld.h), every car 54 x 24
 };
 
 // k_step's template arguments (k_serve's: PK = 1, no ESPLIT), TAB aside
@@ -22,10 +23,11 @@ struct StepKey {
     bool split, esplit;
     int p1, nc;  // the beams and the agents per env fixed at compile time, 0: neither (p1 1 / 2: only
                  // whether the beams are a multiple of 64 / not)
+    int wc = 0;  // the reference's world and plain observation rows at compile time (StepWorld / StepRows, mev_refworld.h)
 };
 constexpr bool operator==(const StepKey& a, const StepKey& b) {
     return a.traffic == b.traffic && a.nm == b.nm && a.km == b.km && a.pk == b.pk && a.split == b.split &&
-           a.esplit == b.esplit && a.p1 == b.p1 && a.nc == b.nc;
+           a.esplit == b.esplit && a.p1 == b.p1 && a.nc == b.nc && a.wc == b.wc;
 }
 struct StepLaunch {
     StepKey key;
@@ -48,56 +50,61 @@ constexpr int kServeMaxWG = 64;
 // (<= 2048 workgroups; 256 CUs x 4 SIMDs)
 constexpr int kSplitMaxWg = 2048;
 
-// the compiled kernels: X(TRAFFIC, NM, KM, PK, SPLIT, ESPLIT, P1, NC), each for both TAB
-#define MEV_STEP_KERNELS(X)                                                                            \
-    /* traffic: the early split (config 4: its 64 beams at compile time), one ego and <= 32 NPC slots, \
-       the runtime layouts */                                                                          \
-    X(true, 1, 32, kTsplitEnvs, true, true, 64, 0)                                                     \
-    X(true, 1, 32, kTsplitEnvs, true, true, 0, 0)                                                      \
-    X(true, 1, 32, 1, false, false, 0, 0)                                                              \
-    X(true, 0, 32, 1, false, false, 0, 0)                                                              \
-    X(true, 0, 64, 1, false, false, 0, 0)                                                              \
-    /* the early split (config 2: 4 envs x 1 agent x 64 beams; the reference's defaults: 1 x 96) */    \
-    X(false, 8, MAXK, 8, true, true, 0, 0)                                                             \
-    X(false, 8, MAXK, 4, true, true, 64, 1)                                                            \
-    X(false, 8, MAXK, 4, true, true, 0, 1)                                                             \
-    X(false, 8, MAXK, 4, true, true, 0, 0)                                                             \
-    X(false, 8, MAXK, 2, true, true, 96, 1)                                                            \
-    X(false, 8, MAXK, 2, true, true, 0, 1)                                                             \
-    X(false, 8, MAXK, 2, true, true, 0, 0)                                                             \
-    X(false, 8, MAXK, 1, true, true, 0, 0)                                                             \
-    /* two waves per workgroup (configs 3 / 5 and 96 beams in smaller batches; config 1: one agent) */ \
-    X(false, 8, MAXK, 8, true, false, 0, 0)                                                            \
-    X(false, 8, MAXK, 4, true, false, 0, 0)                                                            \
-    X(false, 8, MAXK, 2, true, false, 0, 0)                                                            \
-    X(false, 8, MAXK, 1, true, false, 64, 8)                                                           \
-    X(false, 8, MAXK, 1, true, false, 96, 8)                                                           \
-    X(false, 8, MAXK, 1, true, false, 128, 8)                                                          \
-    X(false, 8, MAXK, 1, true, false, 0, 1)                                                            \
-    X(false, 8, MAXK, 1, true, false, 0, 0)                                                            \
-    /* one wave per workgroup */                                                                       \
-    X(false, 8, MAXK, 8, false, false, 0, 0)                                                           \
-    X(false, 8, MAXK, 4, false, false, 0, 0)                                                           \
-    X(false, 8, MAXK, 2, false, false, 0, 0)                                                           \
-    X(false, 8, MAXK, 1, false, false, 64, 8)                                                          \
-    X(false, 8, MAXK, 1, false, false, 64, 0)                                                          \
-    X(false, 8, MAXK, 1, false, false, 96, 8)                                                          \
-    X(false, 8, MAXK, 1, false, false, 96, 0)                                                          \
-    X(false, 8, MAXK, 1, false, false, 128, 8)                                                         \
-    X(false, 8, MAXK, 1, false, false, 128, 0)                                                         \
-    X(false, 8, MAXK, 1, false, false, 1, 0)                                                           \
-    X(false, 8, MAXK, 1, false, false, 2, 0)                                                           \
-    /* the runtime layout */                                                                           \
-    X(false, 0, MAXK, 1, false, false, 0, 0)
+// the compiled kernels: X(TRAFFIC, NM, KM, PK, SPLIT, ESPLIT, P1, NC, WC), each for both TAB (a WC row's
+// TAB slot holds the row's kernel without WC: the reference's LiDAR step reads no distance table)
+#define MEV_STEP_KERNELS(X)                                                                               \
+    /* traffic: the early split (config 4: its 64 beams at compile time), one ego and <= 32 NPC slots,    \
+       the runtime layouts */                                                                             \
+    X(true, 1, 32, kTsplitEnvs, true, true, 64, 0, 0)                                                     \
+    X(true, 1, 32, kTsplitEnvs, true, true, 0, 0, 0)                                                      \
+    X(true, 1, 32, 1, false, false, 0, 0, 0)                                                              \
+    X(true, 0, 32, 1, false, false, 0, 0, 0)                                                              \
+    X(true, 0, 64, 1, false, false, 0, 0, 0)                                                              \
+    /* the early split (config 2: 4 envs x 1 agent x 64 beams; the reference's defaults: 1 x 96) */       \
+    X(false, 8, MAXK, 8, true, true, 0, 0, 0)                                                             \
+    X(false, 8, MAXK, 4, true, true, 64, 1, 0)                                                            \
+    X(false, 8, MAXK, 4, true, true, 0, 1, 0)                                                             \
+    X(false, 8, MAXK, 4, true, true, 0, 0, 0)                                                             \
+    X(false, 8, MAXK, 2, true, true, 96, 1, 0)                                                            \
+    X(false, 8, MAXK, 2, true, true, 0, 1, 0)                                                             \
+    X(false, 8, MAXK, 2, true, true, 0, 0, 0)                                                             \
+    X(false, 8, MAXK, 1, true, true, 0, 0, 0)                                                             \
+    /* two waves per workgroup (configs 3 / 5 and 96 beams in smaller batches; config 1: one agent) */    \
+    X(false, 8, MAXK, 8, true, false, 0, 0, 0)                                                            \
+    X(false, 8, MAXK, 4, true, false, 0, 0, 0)                                                            \
+    X(false, 8, MAXK, 2, true, false, 0, 0, 0)                                                            \
+    X(false, 8, MAXK, 1, true, false, 64, 8, 0)                                                           \
+    X(false, 8, MAXK, 1, true, false, 96, 8, 0)                                                           \
+    X(false, 8, MAXK, 1, true, false, 128, 8, 0)                                                          \
+    X(false, 8, MAXK, 1, true, false, 0, 1, 0)                                                            \
+    X(false, 8, MAXK, 1, true, false, 0, 0, 0)                                                            \
+    /* one wave per workgroup */                                                                          \
+    X(false, 8, MAXK, 8, false, false, 0, 0, 0)                                                           \
+    X(false, 8, MAXK, 4, false, false, 0, 0, 0)                                                           \
+    X(false, 8, MAXK, 2, false, false, 0, 0, 0)                                                           \
+    X(false, 8, MAXK, 1, false, false, 64, 8, 0)                                                          \
+    X(false, 8, MAXK, 1, false, false, 64, 0, 0)                                                          \
+    X(false, 8, MAXK, 1, false, false, 96, 8, 0)                                                          \
+    X(false, 8, MAXK, 1, false, false, 96, 0, 0)                                                          \
+    X(false, 8, MAXK, 1, false, false, 128, 8, 0)                                                         \
+    X(false, 8, MAXK, 1, false, false, 128, 0, 0)                                                         \
+    X(false, 8, MAXK, 1, false, false, 1, 0, 0)                                                           \
+    X(false, 8, MAXK, 1, false, false, 2, 0, 0)                                                           \
+    /* the runtime layout */                                                                              \
+    X(false, 0, MAXK, 1, false, false, 0, 0, 0)                                                           \
+    /* one wave per env with the reference's world and plain rows at compile time (the metric's           \
+       config 3, config 5) */                                                                             \
+    X(false, 8, MAXK, 1, false, false, 64, 8, 1)                                                          \
+    X(false, 8, MAXK, 1, false, false, 128, 8, 1)
 // k_serve's (env.py's common shapes with their counts at compile time: one agent, 8 agents x 64 / 96 beams)
 #define MEV_SERVE_KERNELS(X)               \
-    X(true, 1, 32, 1, false, false, 0, 0)  \
-    X(true, 0, 64, 1, false, false, 0, 0)  \
-    X(false, 8, MAXK, 1, true, false, 0, 1)  \
-    X(false, 8, MAXK, 1, true, false, 64, 8) \
-    X(false, 8, MAXK, 1, true, false, 96, 8) \
-    X(false, 8, MAXK, 1, true, false, 0, 0)
-#define MEV_KEY_ROW(T, NM, KM, PK, S, ES, P1, NC) StepKey{T, NM, KM, PK, S, ES, P1, NC},
+    X(true, 1, 32, 1, false, false, 0, 0, 0)  \
+    X(true, 0, 64, 1, false, false, 0, 0, 0)  \
+    X(false, 8, MAXK, 1, true, false, 0, 1, 0)  \
+    X(false, 8, MAXK, 1, true, false, 64, 8, 0) \
+    X(false, 8, MAXK, 1, true, false, 96, 8, 0) \
+    X(false, 8, MAXK, 1, true, false, 0, 0, 0)
+#define MEV_KEY_ROW(T, NM, KM, PK, S, ES, P1, NC, WC) StepKey{T, NM, KM, PK, S, ES, P1, NC, WC},
 constexpr StepKey kStepKeys[] = {MEV_STEP_KERNELS(MEV_KEY_ROW)};
 constexpr StepKey kServeKeys[] = {MEV_SERVE_KERNELS(MEV_KEY_ROW)};
 #undef MEV_KEY_ROW
@@ -110,6 +117,7 @@ inline int key_row(const StepKey (&keys)[n], const StepKey& k) {
 }
 // k_serve's row for the plan's serve key: that key's, else its unspecialised one's
 inline int serve_row(StepKey k) {
+    k.wc = 0;  // (k_serve has no such rows)
     const int r = key_row(kServeKeys, k);
     if (r >= 0) return r;
     k.p1 = k.nc = 0;
@@ -225,8 +233,11 @@ inline StepPlan plan_step(const StepShape& p) {
             p1 = fr ? fr : (p.R & (WAVE - 1)) == 0 ? 1 : 2;
             nc = fr && p.N == 8 ? 8 : 0;
         }
+        // the reference's world at compile time: the one-wave-per-env kernels of 8 agents x 64 / 128
+        // beams (the metric's shape and config 5's; launch_step also asks for plain rows)
         const bool two = esplit || split;  // a car wave and a LiDAR wave
-        st = {{false, 8, MAXK, pack, two, esplit, p1, nc}, wg, two ? 2u * WAVE : 1u * WAVE, FixedLayout<8>::bytes};
+        const int wc = p.world && !two && pack == 1 && nc == 8 && (p1 == 64 || p1 == 128);
+        st = {{false, 8, MAXK, pack, two, esplit, p1, nc, wc}, wg, two ? 2u * WAVE : 1u * WAVE, FixedLayout<8>::bytes};
         one = st;  // (k_serve: only where this is one workgroup per env, below)
     } else {
         st = one = {{false, 0, MAXK, 1, false, false, 0, 0}, (unsigned)p.E, WAVE, dyn_lds};

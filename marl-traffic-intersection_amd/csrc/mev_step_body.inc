@@ -1,11 +1,13 @@
 // mev_step_body.inc -- the body of one fused step of a workgroup's envs
 // (mev_kernels.hip): included as the body of k_step, and inside a lambda in
 // k_serve's loop (its returns then end the step, not the server).  Expects in
-// scope: the template parameters TRAFFIC, TAB, NM, KM, PK, SPLIT, ESPLIT, P1, NC and
+// scope: the template parameters TRAFFIC, TAB, NM, KM, PK, SPLIT, ESPLIT, P1, NC, WC and
 // pp (const SimParams*), in (StepInputs), out (Outputs).  Kept textually in the
 // kernel: passing the step to an inlined function changed k_step's code (1.2 %
 // slower at config 3, profiles/r3_ab_step_body.txt).
     static_assert(!SPLIT || !TRAFFIC || ESPLIT, "split waves with traffic: the early split");
+    static_assert(!WC || (!TRAFFIC && !TAB && NM > 0 && PK == 1 && !SPLIT && P1 >= WAVE && NC > 0),
+                  "the world at compile time: one wave per env, the counts at compile time, no table");
     const SimParams& p = *pp;
     extern __shared__ __align__(16) unsigned char step_lds[];
     const int wv = SPLIT ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : 0;
@@ -211,12 +213,12 @@
     }
     if constexpr (!(TRAFFIC && ESPLIT)) {  // (the traffic early split returned above)
     CarsCtx cx{};
-    if (wv == 0) cx = cars_pre<TRAFFIC, true, NLT, PK, (!TRAFFIC && NM > 0), false, DIMS, false, NCE>(p, in, out, e, el, nl, npc_cls);
+    if (wv == 0) cx = cars_pre<TRAFFIC, true, NLT, PK, (!TRAFFIC && NM > 0), false, DIMS, false, NCE, false, WC>(p, in, out, e, el, nl, npc_cls);
     if (SPLIT) __syncthreads();
     else wave_lds_sync();
 #if !defined(MEV_EXP_STOP) || MEV_EXP_STOP != 0  // timing-only stop0: the car part without cars_post
     if (wv == 0) {
-        cars_post<TRAFFIC, true, NLT, PK, DIMS, NCE>(p, out, e, el, nl, cx);
+        cars_post<TRAFFIC, true, NLT, PK, DIMS, NCE, false, (WC ? P1 : 0)>(p, out, e, el, nl, cx);
         wave_lds_sync();
     }
 #endif
@@ -242,7 +244,7 @@
         if (j0 > 0) wave_lds_sync();
         if (j0 > 0) __builtin_amdgcn_s_setprio(kPrioLidar);  // each further pool (cars and LiDAR start at one level)
         const int na = NS - j0 < G ? NS - j0 : G;
-        lidar_body<TAB, kPhase1Ilp, LidarSrcLds, LIDAR_NPR, true, 0, P1>(
+        lidar_body<TAB, kPhase1Ilp, LidarSrcLds, LIDAR_NPR, true, 0, P1, WC>(
             p, out, LidarSrcLds{el, g0}, G, g0 + j0, na, lane, lbase, lay);
     }
 #if defined(MEV_STAMPS_Q)
