@@ -1701,9 +1701,9 @@ __device__ __forceinline__ void ego_phase1(const SimParams& p, const StepInputs&
 // k_step): el and nl are this wave's LDS.  Only what the LiDAR needs runs
 // here -- kinematics, status, car-car resolution, respawn, the obstacle table
 // and candidate masks; the rest (bonuses, team mix, flags, the state
-// write-back and the observation head) is cars_post, which k_step runs after
-// the LiDAR so that its latency-bound chain overlaps other waves' LiDAR
-// instead of delaying this wave's.  FUSED: the LiDAR runs in the same wave
+// write-back and the observation head) is cars_post, which k_step runs right
+// after this part and before the LiDAR (mev_step_body.inc; in the split kernels
+// the car wave runs it beside the LiDAR wave).  FUSED: the LiDAR runs in the same wave
 // (k_step) and reads the obstacle table and candidate masks from LDS, so they
 // are not published to HBM.
 // ESPLIT (k_step's early split, one env per two-wave workgroup): the LiDAR wave
@@ -2191,8 +2191,8 @@ __device__ __forceinline__ unsigned long long ts_ego_phase(const SimParams& p, c
     return am;
 }
 
-// The rest of the car part (after the LiDAR in k_step, right after cars_pre in
-// k_cars): bonuses, team mix and env flags (:320-370), the reward / done /
+// The rest of the car part (right after cars_pre, in k_step before the LiDAR):
+// bonuses, team mix and env flags (:320-370), the reward / done /
 // status outputs and the state write-back, the observation head (:418-520).
 // Reads only the car LDS (the LiDAR never writes it).
 // REP (k_cars_repeat): sub-step rc->s of a frame-skip window.  The reward is summed, the
@@ -2659,7 +2659,8 @@ __device__ inline void slab_clip(float c0, float dc, float idc, float a, float b
 // seg_bx int4[C] (the box); C = G * cmax, cmax = the most
 // candidate boxes one agent can have (every other ego, plus the NPC slots).
 // The road march's queue of unfinished beams, ushort[G*R], is only live
-// before the car phase and shares the segment area.
+// before the car phase and shares the segment area.  (The 8-slot fused kernels keep
+// one segment per lane instead: no seg_jo, seg_rg int4[64]; lidar_body's phase 3.)
 
 // Probes tested per step of the road march (phase 1's first probes after a beam's
 // safe stretch from the car centre, and each pooled iteration).
@@ -2769,8 +2770,10 @@ struct LidarSrcLdsEnvs {
 // not (the dense walk for every pool, the agent-pair loop not compiled in); P1 >= 64: R = P1, a
 // compile-time beam count (64: config 3, 96: the reference's default LiDAR, 128: config 5).
 // WC: the reference's world and plain rows at compile time (StepWorld / StepRows; k_step's rows with them).
+// SEGL: the car phase's segments by lane (phase 3 below): the fused kernels of the 8-slot layout without
+// traffic, whose pools have at most 8 agents and whose waves at most 8 boxes.
 template <bool TAB, int ILP, class Src, int NPT = LIDAR_NPR, bool HELP = false, int PART = 0, int P1 = 0,
-          bool WC = false>
+          bool WC = false, bool SEGL = false>
 __device__ __forceinline__ void lidar_body(const SimParams& p, const Outputs& out, const Src& src, const int G,
                                            const int a0, const int na, const int lane, unsigned char* base,
                                            const LidarLayout& lay, const unsigned long long redo = 0ull,
@@ -3143,7 +3146,19 @@ __device__ __forceinline__ void lidar_body(const SimParams& p, const Outputs& ou
     int4* seg_rg = reinterpret_cast<int4*>(base + lay.seg_rg);
     int4* seg_bx = reinterpret_cast<int4*>(base + lay.seg_bx);
     int* scr = reinterpret_cast<int*>(base + lay.scr);
+    //
+    // SEGL (at most 8 agents in the pool, at most 8 boxes in the wave's table): lane 8*j + o
+    // is the segment of compacted agent j and box o, present iff bit o of the agent's
+    // candidate mask is set -- no list (3a), no seg_jo: 3b runs in the segment's own lane
+    // (its agent and its box are independent LDS reads), absent segments count 0 pairs in
+    // 3c's scan, and a pair's segment index gives its agent and box (sm >> 3, sm & 7).
+    // seg_rg then has 64 entries: 8 past the layout's C = 56, into seg_jo's words, which
+    // this path never uses (and still below scr: the static_assert after FixedLayout).
     int M = 0;
+#if defined(MEV_SEG_COUNTS)  // diagnostic: the pool's segments, pairs and 3c lookup passes (tools/seg_counts.py)
+    int dbg_t = 0, dbg_pass = 0;
+#endif
+    if constexpr (!SEGL) {
     // 3a: lane j < nal fetches agent j's candidate masks once; the loop then
     // reads them with readlane instead of two dependent LDS round trips per agent
     unsigned long long cl0 = 0ull, cl1 = 0ull;
@@ -3156,6 +3171,7 @@ __device__ __forceinline__ void lidar_body(const SimParams& p, const Outputs& ou
         M += n0 + __popcll(c1);
     }
     wave_lds_sync();
+    }
     // 3b: beam ranges.  Beam b points along h + rel[b], rel[b] = rel[0] + b*dphi;
     // the range covers the angular span of the box's real slab (box_lo/box_hi):
     // a ray outside it never meets the slab, so none of its probes can land in
@@ -3165,6 +3181,147 @@ __device__ __forceinline__ void lidar_body(const SimParams& p, const Outputs& ou
     const float dphi = R > 1 ? (src.rel(R - 1) - rel0) / (float)(R - 1) : 1.0f;
     const float idphi = 1.0f / dphi;
     const float period = 6.28318531f * idphi;  // beam indices per revolution
+    if constexpr (SEGL) {
+        static_assert(std::is_same<Src, LidarSrcLds>::value, "segments by lane: one box table in the wave's LDS");
+        // 3b's range arithmetic and 3c's probes: operation for operation those of the list path below
+        // (the ranges of box bx seen from the agent at a: three lo | count << 16, and the total)
+        auto seg_range = [&](const float4& a, const int4& bx) -> int4 {
+            const float ex0 = box_lo(bx.x), ex1 = box_hi(bx.y);
+            const float ey0 = box_lo(bx.z), ey1 = box_hi(bx.w);
+            int4 rg;
+            if (all_beams || (a.x >= ex0 && a.x <= ex1 && a.y >= ey0 && a.y <= ey1)) {  // (on its edge too)
+                rg = make_int4(0 | (R << 16), 0, 0, R);  // inside the widened box: every beam
+            } else {
+                // the box's silhouette seen from the agent (outside it): the two corners
+                // that bound its angular span -- the near side's ends when the agent faces
+                // a side, else the corners across the diagonal the agent does not lie on
+                const bool lx = a.x < ex0, hx = a.x > ex1, ly = a.y < ey0, hy = a.y > ey1;
+                const bool mx = !lx && !hx, my = !ly && !hy;
+                const float Xa = my ? (lx ? ex0 : ex1) : (mx ? ex0 : ((lx == ly) ? ex1 : ex0));
+                const float Ya = my ? ey0 : (mx ? (ly ? ey0 : ey1) : ey0);
+                const float Xb = my ? Xa : (mx ? ex1 : ((lx == ly) ? ex0 : ex1));
+                const float Yb = my ? ey1 : (mx ? Ya : ey1);
+                // (relative to the direction of the box centre, as with four corners: both
+                // lie within +-pi/2 of it even when the agent nearly touches the box)
+                const float phc = atan2_fast(-(0.5f * (ey0 + ey1) - a.y), 0.5f * (ex0 + ex1) - a.x);
+                const float da = wrap_pi_fast(atan2_fast(-(Ya - a.y), Xa - a.x) - phc);
+                const float db = wrap_pi_fast(atan2_fast(-(Yb - a.y), Xb - a.x) - phc);
+                const float dmin = fminf(0.0f, fminf(da, db)), dmax = fmaxf(0.0f, fmaxf(da, db));
+                float w = phc + dmin - a.z - rel0;
+                w -= 6.28318531f * floorf(w * 0.159154943f);  // [0, 2*pi)
+                // beams b with rel0 + b*dphi in the span, widened by 2e-4 rad (20x the
+                // error of atan2_fast and of the linear model of the host's angles)
+                const float marg = 2.0e-4f;
+                const float ulo = (w - marg) * idphi, uhi = (w + (dmax - dmin) + marg) * idphi;
+                int lo[3], cn[3];
+#pragma unroll
+                for (int sft = 0; sft < 3; ++sft) {
+                    const float sh = (float)(sft - 1) * period;
+                    int l0 = (int)ceilf(ulo + sh), l1 = (int)floorf(uhi + sh);
+                    l0 = l0 < 0 ? 0 : l0;
+                    l1 = l1 > R - 1 ? R - 1 : l1;
+                    lo[sft] = l0;
+                    cn[sft] = l1 >= l0 ? l1 - l0 + 1 : 0;
+                }
+                rg = make_int4(lo[0] | (cn[0] << 16), lo[1] | (cn[1] << 16), lo[2] | (cn[2] << 16), cn[0] + cn[1] + cn[2]);
+            }
+            return rg;
+        };
+        // 3c's pair r of a segment (agent j at a, box bx, ranges rg): its beam, the probes that
+        // can land in the box, and the earliest of them that does
+        auto pair_probe = [&](const float4& a, const int4& rg, const int4& bx, const int j, const int r) {
+            const int cA = rg.x >> 16, cB = rg.y >> 16;
+            const int b = r < cA ? (rg.x & 0xffff) + r
+                                 : (r < cA + cB ? (rg.y & 0xffff) + r - cA : (rg.z & 0xffff) + r - cA - cB);
+            const int slot = j * R + b;
+            const int kr = res[slot] >> 1;
+            const float2 dd = dir[slot];
+            // probes that can land in the box: the ray's interval inside the
+            // box's real slab (see box_lo), as a superset range of k ...
+            float lo = 0.0f, hi = 1.0e6f;
+            slab_clip(a.x, dd.x, __builtin_amdgcn_rcpf(dd.x), box_lo(bx.x), box_hi(bx.y), lo, hi);
+            slab_clip(a.y, dd.y, __builtin_amdgcn_rcpf(dd.y), box_lo(bx.z), box_hi(bx.w), lo, hi);
+            // d_k = k*step exactly without the table: the slab's 0.01 px absorbs the
+            // rounding of k = lo/step; the table's accumulated distances get one probe
+            int ka, kb;
+            if (TAB) {
+                ka = (int)(fmaxf(lo, 0.0f) * inv_stp) - 1;
+                kb = (int)(fminf(hi, 1.0e6f) * inv_stp) + 1;
+            } else {
+                ka = (int)ceilf(fmaxf(lo, 0.0f) * inv_stp);
+                kb = (int)(fminf(hi, 1.0e6f) * inv_stp);
+            }
+            ka = ka < 1 ? 1 : ka;  // no car test at dist == 0
+            kb = kb < kr - 1 ? kb : kr - 1;
+            if (lo > hi) kb = 0;
+            // ... resolved by exact probes in march order
+            for (int kk = ka; kk <= kb; ++kk) {
+                // a runtime table test here, not march_dist<TAB>: measured 4 us per
+                // step faster in k_step, and without it k_lidar's 64-VGPR
+                // allocation spills ~180 registers (WC: the pointer is null, and still tested
+                // here: StepWorld)
+                const float d = p.dist_tab ? gmem(p.dist_tab)[kk] : (float)kk * W::lidar_step(p);
+                const int px = (int)(a.x + dd.x * d), py = (int)(a.y + dd.y * d);
+                if (px >= bx.x && px <= bx.y && py >= bx.z && py <= bx.w) {
+                    atomicMin(&res[slot], (kk << 1) | 1);
+                    break;
+                }
+            }
+        };
+        const int sj = lane >> 3, so = lane & 7;
+        bool seg = false;
+        float4 sa = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        int4 sbx = make_int4(0, 0, 0, 0);
+        if (sj < nal) {  // (ag[] holds nal agents; the table has a slot for each of the 8 boxes)
+            sa = ag[sj];
+            sbx = src.box(0, so);
+            unsigned long long c0, c1;
+            src.cand(__float_as_int(sa.w), c0, c1);
+            seg = (((unsigned)c0 >> so) & 1u) != 0u;
+        }
+        const unsigned long long segs = ballot(seg);
+        M = __popcll(segs);
+        if (segs != 0ull) {  // (one alive agent, or nobody near anybody: no car phase)
+            int cnt = 0;
+            if (seg) {
+                const int4 rg = seg_range(sa, sbx);
+                seg_rg[lane] = rg;
+                cnt = rg.w;
+            }
+            wave_lds_sync();
+            const int incl = wave_scan_add(cnt);  // DPP, no LDS round trips
+            const int excl = incl - cnt;
+            const int T = __builtin_amdgcn_readlane(incl, WAVE - 1);
+#if defined(MEV_SEG_COUNTS)
+            dbg_t = T;
+#endif
+            int carry = 0;  // (start << 8 | segment) of the segment running into this chunk
+            for (int q0 = 0; q0 < T; q0 += WAVE) {
+                // (the lookup of the pairs' segments: as in the list path below)
+                const int q = q0 + lane;
+                const bool starts = cnt > 0 && excl >= q0 && excl < q0 + WAVE;
+                scr[lane] = 0;
+                wave_lds_sync();
+                if (starts) scr[excl - q0] = ((excl << 8) | lane) + 1;
+                wave_lds_sync();
+                const int got = wave_scan_max(scr[lane]);
+                wave_lds_sync();
+                const int cur = got > 0 ? got - 1 : carry;
+                carry = __builtin_amdgcn_readlane(cur, WAVE - 1);
+                const int sm = cur & 255;
+#if defined(MEV_SEG_COUNTS)
+                ++dbg_pass;
+#endif
+                if (q < T) {
+                    // the segment's agent, ranges and box: three independent reads
+                    const float4 a = ag[sm >> 3];
+                    const int4 rg = seg_rg[sm];
+                    const int4 bx = src.box(0, sm & 7);
+                    pair_probe(a, rg, bx, sm >> 3, q - (cur >> 8));
+                }
+            }
+        }
+    } else {
     for (int m = lane; m < M; m += WAVE) {
         const int jo = seg_jo[m];
         const float4 a = ag[jo >> 8];
@@ -3238,6 +3395,9 @@ __device__ __forceinline__ void lidar_body(const SimParams& p, const Outputs& ou
             carry = __builtin_amdgcn_readlane(cur, WAVE - 1);
             const int sm = cur & 255;
             const int r = q - (cur >> 8);
+#if defined(MEV_SEG_COUNTS)
+            ++dbg_pass;
+#endif
             if (q < T) {
                 const int m = cb + sm;
                 const int j = seg_jo[m] >> 8;
@@ -3283,7 +3443,19 @@ __device__ __forceinline__ void lidar_body(const SimParams& p, const Outputs& ou
                 }
             }
         }
+#if defined(MEV_SEG_COUNTS)
+        dbg_t += T;
+#endif
     }
+    }
+#if defined(MEV_SEG_COUNTS)  // slots 0-2 the env's first pool, 3-5 its second (pools of one env per wave)
+    if (lane == 0) {
+        unsigned long long* dbg = p.debug + (size_t)(a0 / p.N) * 8 + 3 * (((a0 % p.N) / G) & 1);
+        dbg[0] = (unsigned long long)M;
+        dbg[1] = (unsigned long long)dbg_t;
+        dbg[2] = (unsigned long long)dbg_pass;
+    }
+#endif
     wave_lds_sync();
 #if defined(MEV_STAMPS_R)
     if (lane == 0) p.debug[se_ * 8 + 5 + sp_] = __builtin_amdgcn_s_memrealtime();

@@ -154,6 +154,12 @@ struct FixedLayout {
     static constexpr LidarLayout lay = lidar_layout_beams(NM, beams, NM - 1 + KM, false);
     static constexpr int bytes = lidar + lay.bytes;
 };
+// The 8-slot layout's car phase keeps one segment per lane (lidar_body, SEGL): seg_rg int4[64]
+// from lay.seg_rg, 8 entries past the C = 56 the layout counts.  They lie in seg_jo's words,
+// which that path does not use, and end before scr, which it does.
+static_assert(FixedLayout<8>::lay.seg_bx == FixedLayout<8>::lay.seg_jo &&
+                  FixedLayout<8>::lay.seg_rg + WAVE * 16 <= FixedLayout<8>::lay.scr,
+              "segments by lane: 64 ranges between seg_rg and scr");
 
 // the traffic early split: kTsplitEnvs envs (car waves) + one LiDAR wave per workgroup,
 // kTsplitWpe waves per SIMD (config 4: 4096 envs -> 6144 waves on 1024 SIMDs).  Two envs,

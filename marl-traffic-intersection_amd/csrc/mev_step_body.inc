@@ -20,6 +20,8 @@
 #endif
     QSTAMP(0);
     constexpr int KF = TRAFFIC ? KM : 0;  // NPC obstacle slots of the compile-time layout
+    // the car phase's segments by lane (lidar_body): <= 8 agents per pool, <= 8 boxes per wave
+    constexpr bool SEGL = NM == 8 && KF == 0;
     // agents per env at compile time (0: p.N): NC, or one with the one-ego layout (N >= 1)
     constexpr int NCE = NM == 1 ? 1 : NC;
     const StepLayout sl = step_layout_t<NM, KF>(p);
@@ -189,7 +191,7 @@
             float4* ag = reinterpret_cast<float4*>(lbase + lay.ag);
             if (alive) ag[lane_rank(am)] = make_float4(k.x, k.y, k.h, __int_as_float(g0 + il));
             wave_lds_sync();
-            lidar_body<TAB, kEsplitIlp, LidarSrcLds, LIDAR_NPR, true, 1, P1>(
+            lidar_body<TAB, kEsplitIlp, LidarSrcLds, LIDAR_NPR, true, 1, P1, false, SEGL>(
                 p, out, LidarSrcLds{el, g0}, NS, g0, NS, lane, lbase, lay, 0ull, am);
             __syncthreads();  // barrier B: the car part's obstacle table, candidate masks and respawns
             // respawned egos: their spawn poses into ag[] and their beams marched again
@@ -206,7 +208,7 @@
                 wave_lds_sync();
             }
             __builtin_amdgcn_s_setprio(kPrioEsplitCarPhase);
-            lidar_body<TAB, kEsplitIlp, LidarSrcLds, LIDAR_NPR, true, 2, P1>(
+            lidar_body<TAB, kEsplitIlp, LidarSrcLds, LIDAR_NPR, true, 2, P1, false, SEGL>(
                 p, out, LidarSrcLds{el, g0}, NS, g0, NS, lane, lbase, lay, redo, am);
         }
         return;
@@ -244,7 +246,7 @@
         if (j0 > 0) wave_lds_sync();
         if (j0 > 0) __builtin_amdgcn_s_setprio(kPrioLidar);  // each further pool (cars and LiDAR start at one level)
         const int na = NS - j0 < G ? NS - j0 : G;
-        lidar_body<TAB, kPhase1Ilp, LidarSrcLds, LIDAR_NPR, true, 0, P1, WC>(
+        lidar_body<TAB, kPhase1Ilp, LidarSrcLds, LIDAR_NPR, true, 0, P1, WC, SEGL>(
             p, out, LidarSrcLds{el, g0}, G, g0 + j0, na, lane, lbase, lay);
     }
 #if defined(MEV_STAMPS_Q)
