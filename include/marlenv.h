@@ -248,6 +248,63 @@ typedef struct {
 } mev_repeat_args;
 int mev_step_repeat(mev_handle* h, const mev_repeat_args* args);
 
+/* Open-loop plan rollout: mev_step_repeat's loop with an action row and a dt of its own per
+ * sub-step -- what a planner (CEM, MPPI, tree search) evaluates: T different actions, every
+ * sub-step's reward and done to discount, the observation only at the leaf.  Per env, with
+ * T = length, actions[s] = row s - 1 of step.actions ([T][E][N][2]), dt_s = dt_seq ?
+ * dt_seq[s - 1] : step.dt:
+ *
+ *   if MEV_AUTO_RESET and the env's previous call ended: reset it, exactly as mev_step does
+ *   for s = 1..T:
+ *       r = IntersectionEnv::step(actions[s], dt_s)       (cpp/IntersectionEnv.cpp:133-392)
+ *       reward_seq[s-1][i] = r.rew[i];  done_seq[s-1][i] = r.done[i];  status_seq[s-1][i] = r.status[i]
+ *       acc[i] = s == 1 ? r.rew[i] : acc[i] + r.rew[i]             (f32, in this order)
+ *       if r.done[i]: any_done[i] = 1, latched[i] = r.status[i]
+ *       k = s;  if r.terminated or r.truncated: break
+ *   rows s >= k of reward_seq / done_seq / status_seq = 0.0f / 0 / 0
+ *
+ * obs, reward (= acc), done (= any_done), status (latched), terminated, truncated, agents_alive,
+ * step and substeps[e] = k are defined exactly as for mev_step_repeat; the LiDAR is cast once,
+ * from the state the env stopped at.  The *_seq rows before k hold that sub-step's outputs exactly
+ * as mev_step would write them (team mix included); the rows from k on are zero, so a
+ * discounted sum over all T rows needs no mask (the stopping wave writes them itself: no
+ * preparation of the arrays is needed).  The *_seq arrays are the caller's only: they are not
+ * part of mev_get_outputs, snapshots or DLPack.  Between sub-steps the actions differ, so the
+ * reward's smoothness term sees each sub-step's own previous action, as in single steps.
+ * step.spawn_route, if given, is [T][E]; with the Philox spawner sub-step s uses the handle's
+ * counter + (s - 1) and the counter advances by T per call; sub-step s spawns with probability
+ * 1 - expf(-density * dt_s), computed on the host as mev_step does.  dt_seq is therefore ALWAYS a
+ * host pointer, read before the call returns -- a by-value parameter like step.dt, also with
+ * MEV_DEVICE_PTRS.  So for envs that do not end inside the window one call leaves the handle
+ * (state, outputs, later random draws) exactly where T mev_step calls with actions[s], dt_s
+ * would; with every row equal and dt_seq NULL every shared output equals mev_step_repeat(repeat
+ * = T) bit for bit.
+ * step.flags: MEV_DEVICE_PTRS | MEV_AUTO_RESET (MEV_GATHER_TO_ROOT, a length outside
+ * 1..MEV_MAX_REPEAT or null actions: MEV_E_INVALID, the handle untouched).  Launch path as
+ * mev_step_repeat: a resident step server is stopped first, the runtime-layout kernels run
+ * (any N <= 64, <= 64 NPC slots, per-car sizes, any beam list), not counted by
+ * mev_kernel_timing.  Host mode stages actions, spawn_route and the *_seq arrays in per-handle
+ * device buffers made at the first call (sized for MEV_MAX_REPEAT rows) and is synchronous.
+ * Measured (python tools/bench_sequence.py -> profiles/sequence_sweep.json): at 4096 envs x
+ * 8 agents x 64 beams one call with all three *_seq arrays takes 73.9 us at T = 4 against 102.1 us for four
+ * mev_step calls with the same actions (1.38x), 109.7 against 205.5 us at T = 8 (1.87x), 180.9 against 412.9 us
+ * at T = 16 (2.28x); at T = 2 it loses (56.3 against 51.1 us, 0.91x).  A further sub-step costs 8.9 us (8.4 us in
+ * mev_step_repeat: the difference is the sub-step's action load).  One-ego traffic (4096 x 1 x 64, density 0.5)
+ * loses to single steps at every length, as frame skip does: 174.3 against 103.5 us at T = 4 (0.59x), 0.67x at
+ * T = 16. */
+typedef struct {
+    mev_step_args step;     /* as mev_step, except: step.actions is [length][E][N][2] (row s: sub-step s+1),
+                               step.spawn_route, if given, is [length][E]; step.dt is used when dt_seq is NULL */
+    int32_t length;         /* T, 1..MEV_MAX_REPEAT */
+    const float* dt_seq;    /* optional [length]; ALWAYS a host pointer, read before the call returns
+                               (it is a by-value parameter like step.dt, also with MEV_DEVICE_PTRS) */
+    float*   reward_seq;    /* optional [length][E][N]: sub-step s's reward exactly as mev_step would output it */
+    uint8_t* done_seq;      /* optional [length][E][N] */
+    uint8_t* status_seq;    /* optional [length][E][N] */
+    int32_t* substeps;      /* optional [E] */
+} mev_sequence_args;
+int mev_step_sequence(mev_handle* h, const mev_sequence_args* args);
+
 /* Outputs of the last step / reset, from the handle's own device buffers.
  * Lifetime: after a step that wrote caller-owned output buffers (device
  * pointers in mev_step_args), this call, mev_device_outputs and
@@ -294,6 +351,20 @@ int mev_set_reset_routes(mev_handle* h, const int32_t* routes, int32_t count);
 int mev_snapshot_size(mev_handle* h, uint64_t* bytes);
 int mev_snapshot(mev_handle* h, void* dst, uint32_t flags);
 int mev_restore(mev_handle* h, const void* src, const uint8_t* env_mask, uint32_t flags);
+/* Branching from a snapshot (a planner fans one root env out into E candidates):
+ * env e takes the state, car sizes and last outputs of the SNAPSHOT's env env_map[e]; env_map[e] == -1 leaves
+ * env e as it is.  [E] int32, host or (MEV_DEVICE_PTRS) device, like src.  Same validation as mev_restore.
+ * Host pointers: an entry outside [-1, E) -> MEV_E_RANGE, the handle unchanged.  Device pointers: such an
+ * entry is treated as -1 (the kernel never reads outside the snapshot).  The handle's Philox counter is not
+ * restored (as with env_mask).  The reset route pool (mev_set_reset_routes) is configuration, not state, and
+ * stays the handle's; a car's fixed route (mev_set_ego_routes) is its `route` state field, which a later reset
+ * reuses, so a copy keeps its source's routes (as after a masked mev_restore or mev_set_state).
+ * The on-device spawner is keyed by env index, so two copies of one env
+ * draw different NPC spawns unless the caller replays spawn_route.  The source is the snapshot buffer, never
+ * the live state: any map, a permutation included, is safe.
+ * Measured (profiles/sequence_sweep.json): 59.1 us per call at 4096 envs x 8 agents with device pointers,
+ * level with a masked mev_restore (58.9 us; both include reading the snapshot header back to the host). */
+int mev_restore_map(mev_handle* h, const void* src, const int32_t* env_map, uint32_t flags);
 
 /* Diagnostics (cumulative): route ids in state-format gather messages this handle's route
  * table does not have (mev_unpack_gathered; their rows' look-ahead terms are NaN).

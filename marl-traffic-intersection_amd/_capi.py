@@ -49,7 +49,7 @@ EXPORTED = (
     "mev_packed_layout", "mev_comm_unique_id", "mev_comm_init", "mev_comm_destroy", "mev_gather_result",
     "mev_gather_wait", "mev_output_dlpack", "mev_packed_layout2", "mev_set_gather_format", "mev_lidar_decode_table",
     "mev_unpack_gathered", "mev_add_route", "mev_add_route_n", "mev_set_car_dims", "mev_get_car_dims", "mev_car_dims_active",
-    "mev_set_beam_angles", "mev_get_beam_angles", "mev_decode_errors",
+    "mev_set_beam_angles", "mev_get_beam_angles", "mev_decode_errors", "mev_step_sequence", "mev_restore_map",
 )
 
 
@@ -80,6 +80,14 @@ MEV_MAX_REPEAT = 64
 
 class MevRepeatArgs(ctypes.Structure):
     _fields_ = [("step", MevStepArgs), ("repeat", ctypes.c_int32), ("substeps", _vp)]
+
+
+class MevSequenceArgs(ctypes.Structure):  # mev_sequence_args
+    _fields_ = [("step", MevStepArgs), ("length", ctypes.c_int32), ("dt_seq", ctypes.POINTER(ctypes.c_float)),
+                ("reward_seq", _vp), ("done_seq", _vp), ("status_seq", _vp), ("substeps", _vp)]
+
+
+_SEQ_KEYS = ("reward_seq", "done_seq", "status_seq")
 
 
 # (name, dtype, per) — per: "ego" [E*N], "npc" [E*K], "env" [E]; order == struct mev_state
@@ -143,6 +151,8 @@ def load_library(variant: str = None):
     L.mev_reset.argtypes = [_vp, _vp, _vp, ctypes.c_uint32]
     L.mev_step.argtypes = [_vp, ctypes.POINTER(MevStepArgs)]
     L.mev_step_repeat.argtypes = [_vp, ctypes.POINTER(MevRepeatArgs)]
+    L.mev_step_sequence.argtypes = [_vp, ctypes.POINTER(MevSequenceArgs)]
+    L.mev_restore_map.argtypes = [_vp, _vp, _vp, ctypes.c_uint32]
     L.mev_get_outputs.argtypes = [_vp] + [_vp] * 8 + [ctypes.c_uint32]
     L.mev_get_state.argtypes = [_vp, ctypes.POINTER(MevState)]
     L.mev_set_state.argtypes = [_vp, ctypes.POINTER(MevState)]
@@ -512,6 +522,62 @@ class Handle:
         _check(self._lib.mev_step_repeat(self._h, ctypes.byref(a)))
         return out
 
+    def step_sequence(self, actions, dt=1.0 / 60.0, out: Optional[dict] = None, spawn_route=None,
+                      auto_reset: bool = False, device: bool = False, gather: bool = False, length: Optional[int] = None):
+        """Open-loop plan rollout (mev_step_sequence): actions [T][E][N][2], row s the action of
+        sub-step s + 1; dt a float or a sequence of T floats (always host values).  Each env
+        stops at its first terminated or truncated sub-step; the LiDAR is cast once, from the
+        state it stopped at.  Returns the outputs of `step` (reward summed, done / status latched,
+        as `step_repeat`) plus `substeps` [E] and `reward_seq`, `done_seq`, `status_seq`
+        [T][E][N]: each executed sub-step's own outputs, zero after an env stopped.
+        spawn_route, if given, is [T][E].  device=True: every array (the `substeps` / `*_seq`
+        entries of `out` included; absent ones are not written) is a device tensor/pointer and T
+        is actions.shape[0] (or `length` for a raw pointer).  gather: not supported."""
+        if length is None:
+            shape = getattr(actions, "shape", None) if device else np.shape(actions)
+            if not shape:
+                raise ValueError("step_sequence needs actions of shape [T][E][N][2] (or length=T)")
+            length = int(shape[0])
+        T = int(length)
+        if not device:
+            actions = np.ascontiguousarray(actions, np.float32)
+            if actions.ndim < 2 or actions.size != T * self.E * self.N * 2:
+                raise ValueError(f"actions must be [T][{self.E}][{self.N}][2], got {actions.shape}")
+            if spawn_route is not None:
+                spawn_route = np.ascontiguousarray(np.asarray(spawn_route, np.int32))
+                if spawn_route.shape != (T, self.E):
+                    raise ValueError(f"spawn_route must be [{T}][{self.E}], got {spawn_route.shape}")
+            if out is None:
+                out = self.alloc_outputs()
+            if out.get("substeps") is None:
+                out["substeps"] = np.zeros(self.E, np.int32)
+            for k, dtype in zip(_SEQ_KEYS, (np.float32, np.uint8, np.uint8)):
+                if out.get(k) is None or out[k].shape != (T, self.E, self.N):
+                    out[k] = np.zeros((T, self.E, self.N), dtype)
+        out = out if out is not None else {}
+        a = MevSequenceArgs()
+        for k in _OUT_KEYS:
+            setattr(a.step, k, _ptr(out.get(k)))
+        a.step.actions = _ptr(actions)
+        a.step.spawn_route = _ptr(spawn_route)
+        a.step.flags = ((MEV_DEVICE_PTRS if device else 0) | (MEV_AUTO_RESET if auto_reset else 0) |
+                        (MEV_GATHER_TO_ROOT if gather else 0))
+        a.length = T
+        dts = None
+        if np.ndim(dt) == 0:
+            a.step.dt = float(dt)
+        else:
+            dts = np.ascontiguousarray(dt, np.float32).reshape(-1)
+            if dts.size != T:
+                raise ValueError(f"dt must be a float or {T} floats, got {dts.size}")
+            a.step.dt = float(dts[0]) if T else 0.0
+            a.dt_seq = dts.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
+        for k in _SEQ_KEYS:
+            setattr(a, k, _ptr(out.get(k)))
+        a.substeps = _ptr(out.get("substeps"))
+        _check(self._lib.mev_step_sequence(self._h, ctypes.byref(a)))
+        return out
+
     # -- multi-GPU gather (mev_comm_*) -------------------------------------
     def comm_init(self, unique_id: bytes, world: int, rank: int, root: int = 0, slots: int = 0):
         """Join the RCCL communicator (collective over all ranks); slots = envs of the largest shard."""
@@ -702,7 +768,19 @@ class Handle:
         _check(self._lib.mev_snapshot(self._h, _ptr(dst), MEV_DEVICE_PTRS if device else 0))
         return dst
 
-    def restore(self, src, env_mask=None, device: bool = False):
+    def restore(self, src, env_mask=None, device: bool = False, env_map=None):
+        """Roll every env (or those with env_mask != 0) back to snapshot `src`; or, with env_map
+        ([E] int32), give env e the state, car sizes and last outputs of the snapshot's env
+        env_map[e] (-1: leave env e alone) -- mev_restore_map, a planner's branching."""
+        if env_map is not None:
+            if env_mask is not None:
+                raise ValueError("pass env_mask or env_map, not both")
+            if not device:
+                env_map = np.ascontiguousarray(env_map, np.int32)
+                if env_map.shape != (self.E,):
+                    raise ValueError(f"env_map must have {self.E} entries, got {env_map.shape}")
+            _check(self._lib.mev_restore_map(self._h, _ptr(src), _ptr(env_map), MEV_DEVICE_PTRS if device else 0))
+            return
         mask = None if env_mask is None else (env_mask if device else np.ascontiguousarray(env_mask, np.uint8))
         _check(self._lib.mev_restore(self._h, _ptr(src), _ptr(mask), MEV_DEVICE_PTRS if device else 0))
 

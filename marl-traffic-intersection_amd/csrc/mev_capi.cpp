@@ -99,6 +99,12 @@ struct mev_handle {
     int32_t* d_spawn = nullptr;
     int32_t* d_spawn_rep = nullptr;  // [MEV_MAX_REPEAT][E] spawn routes of a host-mode mev_step_repeat (made at the first)
     int32_t* d_substeps = nullptr;   // [E] its sub-step counts
+    // host-mode mev_step_sequence (each made at the first call that needs it, sized for MEV_MAX_REPEAT rows)
+    float* d_act_seq = nullptr;      // [MEV_MAX_REPEAT][E][N][2] action rows
+    float* d_rew_seq = nullptr;      // [MEV_MAX_REPEAT][E][N] per-step rewards
+    uint8_t* d_done_seq = nullptr;   // [MEV_MAX_REPEAT][E][N]
+    uint8_t* d_status_seq = nullptr; // [MEV_MAX_REPEAT][E][N]
+    int32_t* d_env_map = nullptr;    // [E] env map of a host-mode mev_restore_map
     uint8_t* d_mask = nullptr;
     float* d_paths = nullptr;
     int32_t* d_rlen = nullptr;  // [route_cap] each path's own length (RouteTab::len)
@@ -1511,6 +1517,89 @@ int mev_step_repeat(mev_handle* h, const mev_repeat_args* ra) {
     return MEV_OK;
 }
 
+int mev_step_sequence(mev_handle* h, const mev_sequence_args* sa) {
+    if (!h || !sa) return fail(MEV_E_INVALID, "null argument");
+    const mev_step_args* a = &sa->step;
+    if (!a->actions) return fail(MEV_E_INVALID, "actions required");
+    if (sa->length < 1 || sa->length > MEV_MAX_REPEAT)
+        return fail(MEV_E_INVALID, "length must be in 1.." + std::to_string(MEV_MAX_REPEAT));
+    if (a->flags & MEV_GATHER_TO_ROOT) return fail(MEV_E_INVALID, "mev_step_sequence does not gather (MEV_GATHER_TO_ROOT)");
+    static_assert(mev::kMaxSeq == MEV_MAX_REPEAT, "the kernel's by-value dt / spawn_prob rows");
+    HIP_TRY(hipSetDevice(h->cfg.device));
+    if (int r = serve_stop(h)) return r;  // (the server holds the stream)
+    const bool dev = (a->flags & MEV_DEVICE_PTRS) != 0;
+    const int n = sa->length;
+    const size_t E = size_t(h->cfg.num_envs), EN = E * size_t(h->cfg.num_agents);
+    if (!dev) {
+        const size_t cap = size_t(MEV_MAX_REPEAT);
+        hipError_t err = hipSuccess;
+        if (!h->d_act_seq) err = h->alloc(&h->d_act_seq, cap * EN * 2);
+        if (err == hipSuccess && a->spawn_route && !h->d_spawn_rep) err = h->alloc(&h->d_spawn_rep, cap * E);
+        if (err == hipSuccess && sa->substeps && !h->d_substeps) err = h->alloc(&h->d_substeps, E);
+        if (err == hipSuccess && sa->reward_seq && !h->d_rew_seq) err = h->alloc(&h->d_rew_seq, cap * EN);
+        if (err == hipSuccess && sa->done_seq && !h->d_done_seq) err = h->alloc(&h->d_done_seq, cap * EN);
+        if (err == hipSuccess && sa->status_seq && !h->d_status_seq) err = h->alloc(&h->d_status_seq, cap * EN);
+        if (err != hipSuccess) return fail(MEV_E_NOMEM, std::string("device allocation failed: ") + hipGetErrorString(err));
+    }
+    mev::StepInputs in{};
+    // dt and the spawn probability (host glibc expf, as mev_step) of every sub-step, read from
+    // the caller's memory now and passed by value with the kernel's arguments
+    mev::SeqRows rows{};
+    for (int s = 0; s < n; ++s) {
+        const float dt = sa->dt_seq ? sa->dt_seq[s] : a->dt;
+        rows.dt[s] = dt;
+        rows.spawn_prob[s] = 1.0f - expf(-h->cfg.traffic_density * dt);
+    }
+    in.dt = rows.dt[0];
+    in.spawn_prob = rows.spawn_prob[0];
+    in.auto_reset = (a->flags & MEV_AUTO_RESET) ? 1 : 0;
+    in.rng_counter = h->rng_counter;  // sub-step s: + s (k_cars_repeat)
+    h->rng_counter += uint64_t(n);
+    int32_t* d_sub = nullptr;
+    if (dev) {
+        in.actions = a->actions;
+        in.spawn_route = a->spawn_route;
+        d_sub = sa->substeps;
+        rows.reward = sa->reward_seq;
+        rows.done = sa->done_seq;
+        rows.status = sa->status_seq;
+    } else {
+        HIP_TRY(hipMemcpyAsync(h->d_act_seq, a->actions, size_t(n) * EN * 2 * sizeof(float), hipMemcpyHostToDevice,
+                               h->stream));
+        in.actions = h->d_act_seq;
+        if (a->spawn_route) {
+            HIP_TRY(hipMemcpyAsync(h->d_spawn_rep, a->spawn_route, size_t(n) * E * sizeof(int32_t), hipMemcpyHostToDevice,
+                                   h->stream));
+            in.spawn_route = h->d_spawn_rep;
+        }
+        if (sa->substeps) d_sub = h->d_substeps;
+        if (sa->reward_seq) rows.reward = h->d_rew_seq;
+        if (sa->done_seq) rows.done = h->d_done_seq;
+        if (sa->status_seq) rows.status = h->d_status_seq;
+    }
+    const mev::Outputs o = resolve_outputs(h, a->obs, a->reward, a->done, a->status, a->terminated, a->truncated,
+                                           a->agents_alive, a->step, dev);
+    h->deal_valid = false;  // NPC counts change outside the fused step: the deal restarts
+    HIP_TRY(mev::launch_step_sequence(h->sp, in, o, n, rows, d_sub, h->stream));
+    h->last = o;
+    if (!dev) {
+        if (int r = copy_out(h, o, a->obs, a->reward, a->done, a->status, a->terminated, a->truncated, a->agents_alive,
+                             a->step, hipMemcpyDeviceToHost))
+            return r;
+        if (sa->substeps)
+            HIP_TRY(hipMemcpyAsync(sa->substeps, d_sub, E * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+        if (sa->reward_seq)
+            HIP_TRY(hipMemcpyAsync(sa->reward_seq, rows.reward, size_t(n) * EN * sizeof(float), hipMemcpyDeviceToHost,
+                                   h->stream));
+        if (sa->done_seq)
+            HIP_TRY(hipMemcpyAsync(sa->done_seq, rows.done, size_t(n) * EN, hipMemcpyDeviceToHost, h->stream));
+        if (sa->status_seq)
+            HIP_TRY(hipMemcpyAsync(sa->status_seq, rows.status, size_t(n) * EN, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));
+    }
+    return MEV_OK;
+}
+
 static int sync_internal(mev_handle* h);  // below, with mev_device_outputs
 
 int mev_get_outputs(mev_handle* h, float* obs, float* rew, uint8_t* done, uint8_t* status, uint8_t* term,
@@ -1871,20 +1960,18 @@ int mev_snapshot(mev_handle* h, void* dst, uint32_t flags) {
     return MEV_OK;
 }
 
-int mev_restore(mev_handle* h, const void* src, const uint8_t* env_mask, uint32_t flags) {
-    if (!h || !src) return fail(MEV_E_INVALID, "null argument");
-    HIP_TRY(hipSetDevice(h->cfg.device));
-    if (int r_ = serve_stop(h)) return r_;  // (the server holds the stream)
-    const bool dev = (flags & MEV_DEVICE_PTRS) != 0;
+// A snapshot's header, checked against the handle before a restore touches it: a mismatched
+// snapshot leaves the handle unchanged.  per_env: the restore goes through the per-env copy
+// kernels (k_restore, k_restore_map) and their field table.
+static int snap_read_header(mev_handle* h, const void* src, bool dev, bool per_env, SnapHeader& hd) {
     const size_t E = size_t(h->cfg.num_envs);
-    SnapHeader hd{};
     if (dev) {
         HIP_TRY(hipMemcpyAsync(&hd, src, sizeof(hd), hipMemcpyDeviceToHost, h->stream));
         HIP_TRY(hipStreamSynchronize(h->stream));
     } else {
         memcpy(&hd, src, sizeof(hd));
     }
-    {  // validate before touching the handle: a mismatched snapshot leaves it unchanged
+    {
         const mev::Outputs save_last = h->last;
         h->last = h->internal;  // the field table of a restore (its targets are the internal buffers)
         const std::vector<SnapField> f0 = snap_fields(h);
@@ -1900,8 +1987,50 @@ int mev_restore(mev_handle* h, const void* src, const uint8_t* env_mask, uint32_
         // mev_add_route's): a handle with fewer routes would read past the end of its tables
         if (hd.nroutes < 0 || hd.nroutes > h->nroutes || hd.route_hash != h->route_hash[size_t(hd.nroutes)])
             return fail(MEV_E_INVALID, "snapshot's routes differ from this handle's (mev_add_route)");
-        if (env_mask && f0.size() > size_t(mev::kMaxRestoreFields)) return fail(MEV_E_INVALID, "too many snapshot fields");
+        if (per_env && f0.size() > size_t(mev::kMaxRestoreFields)) return fail(MEV_E_INVALID, "too many snapshot fields");
     }
+    return MEV_OK;
+}
+
+// The snapshot on the device for the per-env copy kernels: a host snapshot is staged in the
+// handle's staging buffer (grown on demand) on the handle's stream.
+static int snap_stage(mev_handle* h, const uint8_t* s, size_t total, bool dev, const uint8_t** dsrc) {
+    *dsrc = s;
+    if (dev) return MEV_OK;
+    if (h->snap_stage_bytes < total) {
+        if (h->d_snap_stage) {
+            HIP_TRY(hipStreamSynchronize(h->stream));
+            HIP_TRY(hipFree(h->d_snap_stage));
+            h->d_snap_stage = nullptr;
+            h->snap_stage_bytes = 0;
+        }
+        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&h->d_snap_stage), total));
+        h->snap_stage_bytes = total;
+    }
+    HIP_TRY(hipMemcpyAsync(h->d_snap_stage, s, total, hipMemcpyHostToDevice, h->stream));
+    *dsrc = h->d_snap_stage;
+    return MEV_OK;
+}
+
+static mev::RestoreTab restore_tab(const std::vector<SnapField>& f, const std::vector<size_t>& off) {
+    mev::RestoreTab tab{};
+    tab.n = int32_t(f.size());
+    for (size_t i = 0; i < f.size(); ++i) {
+        tab.dst[i] = f[i].restore;
+        tab.src_off[i] = off[i];
+        tab.bpe[i] = int32_t(f[i].bpe);
+    }
+    return tab;
+}
+
+int mev_restore(mev_handle* h, const void* src, const uint8_t* env_mask, uint32_t flags) {
+    if (!h || !src) return fail(MEV_E_INVALID, "null argument");
+    HIP_TRY(hipSetDevice(h->cfg.device));
+    if (int r_ = serve_stop(h)) return r_;  // (the server holds the stream)
+    const bool dev = (flags & MEV_DEVICE_PTRS) != 0;
+    const size_t E = size_t(h->cfg.num_envs);
+    SnapHeader hd{};
+    if (int r = snap_read_header(h, src, dev, env_mask != nullptr, hd)) return r;
     // the live outputs are restored into the handle's own buffers; envs a masked
     // restore leaves alone keep their current outputs, so bring those in first
     if (env_mask) {
@@ -1921,32 +2050,54 @@ int mev_restore(mev_handle* h, const void* src, const uint8_t* env_mask, uint32_
     } else {
         const uint8_t* dsrc = s;
         const uint8_t* dmask = env_mask;
-        if (!dev) {  // stage the snapshot and the mask on the device
-            if (h->snap_stage_bytes < total) {
-                if (h->d_snap_stage) {
-                    HIP_TRY(hipStreamSynchronize(h->stream));
-                    HIP_TRY(hipFree(h->d_snap_stage));
-                    h->d_snap_stage = nullptr;
-                    h->snap_stage_bytes = 0;
-                }
-                HIP_TRY(hipMalloc(reinterpret_cast<void**>(&h->d_snap_stage), total));
-                h->snap_stage_bytes = total;
-            }
-            HIP_TRY(hipMemcpyAsync(h->d_snap_stage, s, total, hipMemcpyHostToDevice, h->stream));
+        if (int r = snap_stage(h, s, total, dev, &dsrc)) return r;  // stage the snapshot and the mask on the device
+        if (!dev) {
             HIP_TRY(hipMemcpyAsync(h->d_mask, env_mask, E, hipMemcpyHostToDevice, h->stream));
-            dsrc = h->d_snap_stage;
             dmask = h->d_mask;
         }
-        mev::RestoreTab tab{};
-        tab.n = int32_t(f.size());
-        for (size_t i = 0; i < f.size(); ++i) {
-            tab.dst[i] = f[i].restore;
-            tab.src_off[i] = off[i];
-            tab.bpe[i] = int32_t(f[i].bpe);
-        }
-        HIP_TRY(mev::launch_restore(tab, dsrc, dmask, h->cfg.num_envs, h->stream));
+        HIP_TRY(mev::launch_restore(restore_tab(f, off), dsrc, dmask, h->cfg.num_envs, h->stream));
         h->sp.dims = h->sp.dims || hd.dims;  // (the sizes arrays hold valid entries either way)
     }
+    if (!dev) HIP_TRY(hipStreamSynchronize(h->stream));
+    return MEV_OK;
+}
+
+int mev_restore_map(mev_handle* h, const void* src, const int32_t* env_map, uint32_t flags) {
+    if (!h || !src || !env_map) return fail(MEV_E_INVALID, "null argument");
+    HIP_TRY(hipSetDevice(h->cfg.device));
+    if (int r_ = serve_stop(h)) return r_;  // (the server holds the stream)
+    const bool dev = (flags & MEV_DEVICE_PTRS) != 0;
+    const size_t E = size_t(h->cfg.num_envs);
+    SnapHeader hd{};
+    if (int r = snap_read_header(h, src, dev, true, hd)) return r;
+    if (!dev) {  // (a device map's bad entries are skipped by the kernel)
+        for (size_t e = 0; e < E; ++e)
+            if (env_map[e] < -1 || env_map[e] >= int32_t(E))
+                return fail(MEV_E_RANGE, "env_map[" + std::to_string(e) + "] = " + std::to_string(env_map[e]) +
+                                             " is outside [-1, " + std::to_string(E) + ")");
+        if (!h->d_env_map) {
+            const hipError_t err = h->alloc(&h->d_env_map, E);
+            if (err != hipSuccess)
+                return fail(MEV_E_NOMEM, std::string("device allocation failed: ") + hipGetErrorString(err));
+        }
+    }
+    // envs the map leaves alone keep their current outputs: bring those into the handle's own
+    // buffers, the restore's targets, first (as a masked mev_restore)
+    if (int r = sync_internal(h)) return r;
+    h->last = h->internal;
+    h->deal_valid = false;
+    const std::vector<SnapField> f = snap_fields(h);
+    std::vector<size_t> off;
+    const size_t total = snap_offsets(f, E, &off);
+    const uint8_t* dsrc = nullptr;
+    const int32_t* dmap = env_map;
+    if (int r = snap_stage(h, static_cast<const uint8_t*>(src), total, dev, &dsrc)) return r;
+    if (!dev) {
+        HIP_TRY(hipMemcpyAsync(h->d_env_map, env_map, E * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+        dmap = h->d_env_map;
+    }
+    HIP_TRY(mev::launch_restore_map(restore_tab(f, off), dsrc, dmap, h->cfg.num_envs, h->stream));
+    h->sp.dims = h->sp.dims || hd.dims;  // (the sizes arrays hold valid entries either way)
     if (!dev) HIP_TRY(hipStreamSynchronize(h->stream));
     return MEV_OK;
 }

@@ -216,6 +216,23 @@ hipError_t launch_step(const SimParams& p, const SimParams* dp, const StepInputs
 // in.rng_counter + s.  substeps (nullable): [E] sub-steps executed.  Every shape k_cars runs.
 hipError_t launch_step_repeat(const SimParams& p, const StepInputs& in, const Outputs& out, int repeat,
                               int32_t* substeps, hipStream_t s);
+// The plan-rollout call (mev_step_sequence): launch_step_repeat's loop with an action row, a dt
+// and a spawn probability of its own per sub-step (k_cars_repeat<TRAFFIC, SEQ = true>).
+// in.actions is [length][E][N][2], in.spawn_route (if given) [length][E]; in.dt and
+// in.spawn_prob are not read: sub-step s takes dt[s] and spawn_prob[s], which travel by value
+// in the kernel's argument segment.  reward_seq / done_seq / status_seq (each nullable) are
+// [length][E][N]: row s holds sub-step s's own outputs for the envs that ran it, zero after
+// an env stopped (the wave that stops writes its remaining rows itself).
+constexpr int kMaxSeq = 64;  // == MEV_MAX_REPEAT
+struct SeqRows {
+    float* reward;
+    uint8_t* done;
+    uint8_t* status;
+    float dt[kMaxSeq];
+    float spawn_prob[kMaxSeq];
+};
+hipError_t launch_step_sequence(const SimParams& p, const StepInputs& in, const Outputs& out, int length,
+                                const SeqRows& rows, int32_t* substeps, hipStream_t s);
 hipError_t launch_reset(const SimParams& p, const uint8_t* env_mask, const Outputs& out, hipStream_t s,
                         uint64_t rng_counter);
 // recompute the observation rows from the current state with LiDAR = max (after set_state)
@@ -259,5 +276,8 @@ struct RestoreTab {
     int32_t bpe[kMaxRestoreFields];  // bytes per env
 };
 hipError_t launch_restore(const RestoreTab& tab, const uint8_t* src, const uint8_t* env_mask, int E, hipStream_t s);
+// mapped per-env copy (mev_restore_map): env e takes the slices of the snapshot's env env_map[e];
+// an entry outside [0, E) leaves env e alone
+hipError_t launch_restore_map(const RestoreTab& tab, const uint8_t* src, const int32_t* env_map, int E, hipStream_t s);
 
 }  // namespace mev

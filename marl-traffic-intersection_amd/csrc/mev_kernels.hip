@@ -1527,6 +1527,18 @@ struct RepCarry {
     int32_t* substeps;  // [E] sub-steps executed (nullable)
 };
 
+// A plan-rollout call (k_cars_repeat<TRAFFIC, SEQ = true>) carries nothing more in registers:
+// the action of sub-step s -- the one ego load of a later sub-step -- is loaded at the top of
+// its cars_pre, behind the previous sub-step's row stores, and goes straight into el.a0 /
+// el.a1.  (MEV_SEQ_EARLY_LOAD: an experiment build has the kernel's loop issue it ahead of
+// those stores instead.  Measured 0.3 us per sub-step slower at 4096 x 8 x 64 -- the wave waits
+// for the load at the end of a sub-step with nothing to run beside it -- DESIGN.md 3.2c.)
+#if defined(MEV_SEQ_EARLY_LOAD)
+constexpr bool kSeqEarlyLoad = true;
+#else
+constexpr bool kSeqEarlyLoad = false;
+#endif
+
 // Phase 1 of the car part for agent i of el on lane group (grp, sub): kinematics
 // (IntersectionEnv.cpp:151-163), path index, base reward (:15-46), status (:165-290).
 // cars_pre runs it over its agents 8 per pass; the traffic early split's LiDAR wave
@@ -1726,11 +1738,12 @@ __device__ __forceinline__ void ego_phase1(const SimParams& p, const StepInputs&
 // masks stay in LDS (cars_post publishes them in the sub-step the env stops at).
 // WC: the reference's world at compile time (StepWorld / StepRows; k_step's rows with it).
 template <bool TRAFFIC, bool FUSED, class NL, int PK = 1, bool EARLY = false, bool ESPLIT = false, bool DIMS = false,
-          bool TSC = false, int NC = 0, bool REP = false, bool WC = false>
+          bool TSC = false, int NC = 0, bool REP = false, bool WC = false, bool SEQ = false>
 __device__ __forceinline__ CarsCtx cars_pre(const SimParams& p, const StepInputs& in, const Outputs& out, const int e,
                                             const CarsLDS& el, NL* nl, int npc_cls = kDealClasses - 1,
                                             const RepCarry* rc = nullptr) {
     static_assert(!REP || (!FUSED && PK == 1 && !EARLY && !ESPLIT && !TSC && NC == 0), "frame skip: k_cars' layout");
+    static_assert(!SEQ || REP, "plan rollout: the frame-skip loop");
     static_assert(!ESPLIT || FUSED, "early split: k_step");
     static_assert(PK == 1 || (FUSED && !TRAFFIC), "several envs per wave: k_step without traffic");
     static_assert(!DIMS || (PK == 1 && !EARLY && !ESPLIT), "per-car sizes: the runtime-layout kernels");
@@ -1932,6 +1945,16 @@ __device__ __forceinline__ CarsCtx cars_pre(const SimParams& p, const StepInputs
         // a later sub-step: the counters from the carry, the NPC survivors from nl (lane = slot)
         step_no = rc->step_prev + 1;
         prev_npcs = TRAFFIC ? rc->npcs_prev : 0;
+        if constexpr (SEQ && !kSeqEarlyLoad) {
+            // this sub-step's own action row (in.actions is its row), the only ego load of a later
+            // sub-step (in the experiment build the kernel's loop has issued it ahead of the previous
+            // sub-step's row stores and left it in el.a0 / el.a1)
+            const float a0 = ldu(gmem(in.actions), 2 * ug), a1 = ldu(gmem(in.actions), 2 * ug + 1);
+            if (lane_on) {
+                el.a0[il] = a0;
+                el.a1[il] = a1;
+            }
+        }
         if constexpr (TRAFFIC) {
             if (tid < prev_npcs) {
                 nreg.x = nl->x[tid]; nreg.y = nl->y[tid]; nreg.v = nl->v[tid]; nreg.h = nl->h[tid];
@@ -2202,10 +2225,11 @@ __device__ __forceinline__ unsigned long long ts_ego_phase(const SimParams& p, c
 // WCP1 > 0: plain observation rows of 31 + WCP1 columns, every one a LiDAR slot, at compile time
 // (StepWorld / StepRows; k_step's rows with the reference's world).
 template <bool TRAFFIC, bool FUSED, class NL, int PK = 1, bool DIMS = false, int NC = 0, bool REP = false,
-          int WCP1 = 0>
+          int WCP1 = 0, bool SEQ = false>
 __device__ __forceinline__ void cars_post(const SimParams& p, const Outputs& out, const int e, const CarsLDS& el,
                                           const NL* nl, CarsCtx& cx, RepCarry* rc = nullptr) {
     static_assert(!REP || (!FUSED && PK == 1 && NC == 0), "frame skip: k_cars' layout");
+    static_assert(!SEQ || REP, "plan rollout: the frame-skip loop");
     using RW = StepRows<(WCP1 > 0), WCP1>;
     static_assert(WCP1 == 0 || (!TRAFFIC && FUSED && !DIMS), "constant rows: the compile-time layout's head writes");
     const int tid = threadIdx.x & (WAVE - 1);
@@ -2272,6 +2296,13 @@ __device__ __forceinline__ void cars_post(const SimParams& p, const Outputs& out
         const bool truncated = p.max_steps > 0 && step_e >= p.max_steps;
         if (PK == 1) cx.ended = terminated || truncated;
         uint8_t done_o = done_i, st_o = st_i;
+        if constexpr (SEQ) {
+            // this sub-step's own reward as mev_step writes it (bonuses, team mix), back into the
+            // car LDS beside its done / status: the kernel's loop stores the three to the caller's
+            // per-step rows after cars_post, where nothing else is live (stored from here, the
+            // 128-VGPR instantiation spilled 5 registers to scratch).  Nothing below reads el.rew.
+            if (in_env) el.rew[i] = rew_i;
+        }
         if constexpr (REP) {
             // acc = r (first sub-step) or acc + r, in sub-step order; the latest done's status
             rc->rew = rc->s == 0 ? rew_i : rc->rew + rew_i;
@@ -2479,15 +2510,32 @@ struct RepeatArgs {
     int32_t e_begin, repeat;
     int32_t* substeps;  // [E] sub-steps executed (nullable)
 };
+// SEQ (mev_step_sequence, a planner's open-loop rollout): the same loop with sub-step s's own
+// action row (actions[s][e][i]), dt and spawn probability -- the latter two by value in the
+// argument segment (SeqRows) -- and each executed sub-step's reward / done / status stored to
+// row s of the caller's per-step arrays: after cars_post, from the car LDS (lane = agent).
+// A later sub-step loads its own action at the top of cars_pre (an experiment build issues it
+// here, ahead of the row stores: measured slower, see kSeqEarlyLoad).  The wave
+// zeroes the rows after the sub-step it stopped at itself (no memset before the launch: one
+// launch, and device-mode callers' arrays need no preparation).  The argument struct begins
+// with RepeatArgs, so the loop reads the shared part the same way.
+struct SeqArgs {
+    RepeatArgs r;
+    SeqRows rows;
+};
+static_assert(sizeof(SeqArgs) <= 4096, "the kernel argument segment");
 // (four waves per SIMD, as k_step: 4096 envs are one round of single-wave workgroups on 256 CUs;
 // with the NPC phase 128 VGPRs would spill to scratch: two)
-template <bool TRAFFIC>
-__global__ __launch_bounds__(WAVE, TRAFFIC ? 2 : 4) void k_cars_repeat(RepeatArgs args) {
+template <bool TRAFFIC, bool SEQ = false>
+__global__ __launch_bounds__(WAVE, TRAFFIC ? 2 : 4) void k_cars_repeat(
+    typename std::conditional<SEQ, SeqArgs, RepeatArgs>::type args) {
     extern __shared__ __align__(16) unsigned char cars_lds[];
     __shared__ typename std::conditional<TRAFFIC, NpcLDS, char>::type nl_storage;
     NpcLDS* nl = nullptr;
     if constexpr (TRAFFIC) nl = &nl_storage;
-    const int repeat = args.repeat;
+    int repeat;
+    if constexpr (SEQ) repeat = args.r.repeat;
+    else repeat = args.repeat;
     RepCarry rc{0, repeat, 0, 0, false, 0.0f, 0, 0, nullptr};
     for (int s = 0; s < repeat; ++s) {
         typedef const __attribute__((address_space(4))) RepeatArgs CArgs;
@@ -2502,15 +2550,66 @@ __global__ __launch_bounds__(WAVE, TRAFFIC ? 2 : 4) void k_cars_repeat(RepeatArg
         in.rng_counter += (uint64_t)s;
         rc.s = s;
         rc.substeps = a.substeps;
-        CarsCtx cx = cars_pre<TRAFFIC, false, NpcLDS, 1, false, false, true, false, 0, true>(p, in, a.out, e, el, nl,
-                                                                                             kDealClasses - 1, &rc);
+        if constexpr (SEQ) {
+            const SeqRows& q = reinterpret_cast<const SeqArgs*>(&a)->rows;
+            in.actions += 2 * (size_t)s * ((size_t)p.E * p.N);
+            in.dt = q.dt[s];
+            in.spawn_prob = q.spawn_prob[s];
+        }
+        CarsCtx cx = cars_pre<TRAFFIC, false, NpcLDS, 1, false, false, true, false, 0, true, false, SEQ>(
+            p, in, a.out, e, el, nl, kDealClasses - 1, &rc);
         wave_lds_sync();
         if (s == 0) rc.first_reset = cx.do_reset;
-        cars_post<TRAFFIC, false, NpcLDS, 1, true, 0, true>(p, a.out, e, el, nl, cx, &rc);
+        cars_post<TRAFFIC, false, NpcLDS, 1, true, 0, true, 0, SEQ>(p, a.out, e, el, nl, cx, &rc);
+        if constexpr (SEQ) {
+            // row s of the per-step arrays from the car LDS (cars_post left the final reward in
+            // el.rew; a lane reads back what it wrote).  (Experiment build: in a sub-step that goes
+            // on cars_post has stored nothing, so the next action's load is issued first.)
+            const SeqRows& q = reinterpret_cast<const SeqArgs*>(&a)->rows;
+            const int tid = threadIdx.x & (WAVE - 1);
+            const bool lane_on = tid < p.N;
+            const int il = lane_on ? tid : 0;
+            const uint32_t g = (uint32_t)(e * p.N + il);
+            const size_t en = (size_t)p.E * p.N, row = (size_t)s * en;
+            const bool more = kSeqEarlyLoad && !cx.ended && s + 1 < repeat;  // (wave-uniform; row s + 1 < length)
+            float na0 = 0.0f, na1 = 0.0f;
+            if (more) {
+                const float* nx = a.in.actions + 2 * (row + en);
+                na0 = ldu(gmem(nx), 2 * g);
+                na1 = ldu(gmem(nx), 2 * g + 1);
+            }
+            if (lane_on) {
+                if (q.reward) gmem(q.reward + row)[g] = el.rew[il];
+                if (q.done) gmem(q.done + row)[g] = el.done[il];
+                if (q.status) gmem(q.status + row)[g] = el.status[il];
+            }
+            if (more && lane_on) {
+                el.a0[il] = na0;
+                el.a1[il] = na1;
+            }
+        }
         if (cx.ended) break;
         rc.step_prev = cx.step_no;
         rc.npcs_prev = cx.ncnt;
         wave_lds_sync();  // (cars_post's reads of the car LDS before the next sub-step's writes)
+    }
+    if constexpr (SEQ) {
+        // the rows after the sub-step the env stopped at (rc.s): zero, lane = agent
+        typedef const __attribute__((address_space(4))) SeqArgs CArgs;
+        CArgs* ka = (CArgs*)__builtin_amdgcn_kernarg_segment_ptr();
+        asm volatile("" : "+s"(ka));
+        const SeqArgs& a = *(const SeqArgs*)ka;
+        const int N = a.r.p.N, tid = threadIdx.x & (WAVE - 1);
+        const int e = a.r.e_begin + xcd_env((int)blockIdx.x, (int)gridDim.x);
+        const size_t en = (size_t)a.r.p.E * N;
+        if (tid < N) {
+            for (int z = rc.s + 1; z < repeat; ++z) {
+                const size_t g = (size_t)z * en + (size_t)e * N + tid;
+                if (a.rows.reward) gmem(a.rows.reward)[g] = 0.0f;
+                if (a.rows.done) gmem(a.rows.done)[g] = 0;
+                if (a.rows.status) gmem(a.rows.status)[g] = 0;
+            }
+        }
     }
 }
 
@@ -3783,14 +3882,19 @@ __global__ __launch_bounds__(WAVE) void k_reset(SimParams p, const uint8_t* mask
         obs_exact_pass<TRAFFIC, TRAFFIC>(p, m, dl, el, nl, ncnt, out.obs + (size_t)e * N * p.D, (size_t)p.D);
 }
 
-// repeat > 0: the frame-skip call's looping car kernel in k_cars' place
+// repeat > 0: the frame-skip call's looping car kernel in k_cars' place (rows: its plan-rollout form)
 static hipError_t launch_part(const SimParams& p, const StepInputs& in, const Outputs& out, int e0, int e1,
-                              hipStream_t s, const hipEvent_t* ev, int repeat = 0, int32_t* substeps = nullptr) {
+                              hipStream_t s, const hipEvent_t* ev, int repeat = 0, int32_t* substeps = nullptr,
+                              const SeqRows* rows = nullptr) {
     // k_cars then k_lidar over the envs [e0, e1)
     if (e1 <= e0) return hipSuccess;
     if (ev) (void)hipEventRecord(ev[0], s);
     const unsigned cars_lds = (unsigned)cars_lds_bytes(p.N, cars_k(p), true);
-    if (repeat > 0) {
+    if (repeat > 0 && rows) {
+        const SeqArgs sa{RepeatArgs{p, in, out, e0, repeat, substeps}, *rows};
+        if (p.traffic) hipLaunchKernelGGL((k_cars_repeat<true, true>), dim3(e1 - e0), dim3(WAVE), cars_lds, s, sa);
+        else hipLaunchKernelGGL((k_cars_repeat<false, true>), dim3(e1 - e0), dim3(WAVE), cars_lds, s, sa);
+    } else if (repeat > 0) {
         const RepeatArgs ra{p, in, out, e0, repeat, substeps};
         if (p.traffic) hipLaunchKernelGGL(k_cars_repeat<true>, dim3(e1 - e0), dim3(WAVE), cars_lds, s, ra);
         else hipLaunchKernelGGL(k_cars_repeat<false>, dim3(e1 - e0), dim3(WAVE), cars_lds, s, ra);
@@ -3861,6 +3965,12 @@ hipError_t launch_step_repeat(const SimParams& p, const StepInputs& in, const Ou
                               int32_t* substeps, hipStream_t s) {
     if (repeat < 1) return hipErrorInvalidValue;
     return launch_part(p, in, out, 0, p.E, s, nullptr, repeat, substeps);
+}
+
+hipError_t launch_step_sequence(const SimParams& p, const StepInputs& in, const Outputs& out, int length,
+                                const SeqRows& rows, int32_t* substeps, hipStream_t s) {
+    if (length < 1 || length > kMaxSeq) return hipErrorInvalidValue;
+    return launch_part(p, in, out, 0, p.E, s, nullptr, length, substeps, &rows);
 }
 
 hipError_t launch_serve(const SimParams& p, const SimParams* dp, const ServeArgs& sa, const Outputs& out,
@@ -4004,6 +4114,31 @@ __global__ __launch_bounds__(WAVE) void k_restore(RestoreTab tab, const uint8_t*
 
 hipError_t launch_restore(const RestoreTab& tab, const uint8_t* src, const uint8_t* env_mask, int E, hipStream_t s) {
     hipLaunchKernelGGL(k_restore, dim3(E, tab.n), dim3(WAVE), 0, s, tab, src, env_mask);
+    return hipGetLastError();
+}
+
+// mev_restore_map: block (e, field) copies the slice of the SNAPSHOT's env map[e] of one field
+// into live env e (branching: one source env into many).  The source is the snapshot buffer,
+// never the live state, so any map -- a permutation included -- has no in-place hazard.  An
+// entry outside [0, E) (-1 by contract) leaves env e alone: nothing is read outside the buffer.
+__global__ __launch_bounds__(WAVE) void k_restore_map(RestoreTab tab, const uint8_t* src, const int32_t* map) {
+    const int e = blockIdx.x, f = blockIdx.y, E = gridDim.x;
+    if (f >= tab.n) return;
+    const int m = map[e];
+    if (m < 0 || m >= E) return;
+    const int bpe = tab.bpe[f];
+    const uint8_t* s = src + tab.src_off[f] + (size_t)m * bpe;
+    uint8_t* d = tab.dst[f] + (size_t)e * bpe;
+    if ((bpe & 3) == 0) {
+        for (int w = threadIdx.x; w < (bpe >> 2); w += WAVE)
+            reinterpret_cast<uint32_t*>(d)[w] = reinterpret_cast<const uint32_t*>(s)[w];
+    } else {
+        for (int b = threadIdx.x; b < bpe; b += WAVE) d[b] = s[b];
+    }
+}
+
+hipError_t launch_restore_map(const RestoreTab& tab, const uint8_t* src, const int32_t* env_map, int E, hipStream_t s) {
+    hipLaunchKernelGGL(k_restore_map, dim3(E, tab.n), dim3(WAVE), 0, s, tab, src, env_map);
     return hipGetLastError();
 }
 

@@ -98,6 +98,7 @@ class VecIntersectionEnv:
         else:
             self._out = self._h.alloc_outputs()
         self._out_rep = None  # the same buffers plus `substeps`, made at the first frame-skip step
+        self._out_seq = None  # ... plus the per-step rows of a plan rollout (step_sequence), per plan length
 
     # ----------------------------------------------------------------- utils
     @property
@@ -149,18 +150,27 @@ class VecIntersectionEnv:
             return out
         return self._h.snapshot(out)
 
-    def restore(self, snap, env_mask=None):
-        """Roll all envs (or those with env_mask != 0) back to `snap`; outputs follow."""
+    def restore(self, snap, env_mask=None, env_map=None):
+        """Roll all envs (or those with env_mask != 0) back to `snap`; outputs follow.
+        env_map ([E] ints): env e takes the state and outputs of the snapshot's env env_map[e]
+        (-1 leaves it alone) -- fan one root env out into E candidates (Handle.restore)."""
+        if env_mask is not None and env_map is not None:
+            raise ValueError("pass env_mask or env_map, not both")
         if self.backend == "torch":
             self._bind_stream()
-            mask = None
+            mask = emap = None
             if env_mask is not None:
                 mask = self._torch.as_tensor(env_mask, device=self._out["obs"].device).to(self._torch.uint8)
                 mask = mask.contiguous()
-            self._h.restore(snap, env_mask=mask, device=True)
+            if env_map is not None:
+                emap = self._torch.as_tensor(env_map, device=self._out["obs"].device).to(self._torch.int32)
+                emap = emap.contiguous()
+                if emap.numel() != self.num_envs:
+                    raise ValueError(f"env_map must have {self.num_envs} entries, got {tuple(emap.shape)}")
+            self._h.restore(snap, env_mask=mask, env_map=emap, device=True)
             self._h.get_outputs(self._out, device=True)
             return self._out["obs"]
-        self._h.restore(snap, env_mask=env_mask)
+        self._h.restore(snap, env_mask=env_mask, env_map=env_map)
         return self._h.get_outputs(self._out)["obs"]
 
     def set_traffic_routes(self, routes):
@@ -230,6 +240,65 @@ class VecIntersectionEnv:
         if n > 1:
             info["substeps"] = o["substeps"]
         return o["obs"], o["reward"], o["terminated"], o["truncated"], info
+
+    def step_sequence(self, actions, dt=1.0 / 60.0, spawn_route=None, copy: bool = False):
+        """Open-loop plan rollout: actions [T, E, N, 2], one action row per sub-step (dt: a float or
+        T host floats) -> (obs, rewards, terminated, truncated, info) in one device call
+        (Handle.step_sequence).  obs is the leaf observation (one LiDAR cast), rewards the
+        per-agent sums; info holds done / status / agents_alive / step as after `step`, plus
+        substeps [E] and reward_seq / done_seq / status_seq [T, E, N]: each executed sub-step's own
+        outputs, zero after an env stopped (terminated or truncated), so a discounted sum over
+        the T rows needs no mask.  spawn_route, if given, is [T][E].  torch: stream-ordered on
+        the current stream, zero-copy; the returned tensors are reused by the next call with
+        the same T."""
+        if self.backend == "torch":
+            t = self._torch
+            self._bind_stream()
+            dev = self._out["obs"].device
+            a = actions
+            if not (isinstance(a, t.Tensor) and a.is_cuda and a.dtype == t.float32 and a.is_contiguous()):
+                a = t.as_tensor(a, dtype=t.float32, device=dev).contiguous()
+            if a.dim() < 2 or a.numel() != a.shape[0] * self.num_envs * self.num_agents * 2:
+                raise ValueError(f"actions must be [T, {self.num_envs}, {self.num_agents}, 2], got {tuple(a.shape)}")
+            if a.device.index != self.device_index:
+                raise ValueError("actions are on another device")
+            T = int(a.shape[0])
+            o = self._sequence_out(T)
+            sp = None
+            if spawn_route is not None:
+                sp = t.as_tensor(spawn_route, dtype=t.int32, device=dev).contiguous()
+                if tuple(sp.shape) != (T, self.num_envs):
+                    raise ValueError(f"spawn_route must be [{T}][{self.num_envs}], got {tuple(sp.shape)}")
+            self._h.step_sequence(a, dt, out=o, spawn_route=sp, auto_reset=self.auto_reset, device=True, length=T)
+            if copy:
+                o = {k: v.clone() for k, v in o.items()}
+        else:
+            T = int(np.shape(actions)[0])
+            o = self._sequence_out(T)
+            self._h.step_sequence(actions, dt, out=o, spawn_route=spawn_route, auto_reset=self.auto_reset)
+            if copy:
+                o = {k: v.copy() for k, v in o.items()}
+        info = {k: o[k] for k in ("done", "status", "agents_alive", "step", "substeps", "reward_seq", "done_seq",
+                                  "status_seq")}
+        return o["obs"], o["reward"], o["terminated"], o["truncated"], info
+
+    def _sequence_out(self, T):
+        """The step's output buffers plus substeps and the [T, E, N] per-step rows (kept per T)."""
+        if not 1 <= T <= _capi.MEV_MAX_REPEAT:
+            raise ValueError(f"a plan has 1..{_capi.MEV_MAX_REPEAT} rows, got {T}")
+        if self._out_seq is None or self._out_seq["reward_seq"].shape[0] != T:
+            shape = (T, self.num_envs, self.num_agents)
+            sub = self._repeat_out()["substeps"]
+            if self.backend == "torch":
+                t, dev = self._torch, self._out["obs"].device
+                rows = dict(reward_seq=t.zeros(shape, dtype=t.float32, device=dev),
+                            done_seq=t.zeros(shape, dtype=t.uint8, device=dev),
+                            status_seq=t.zeros(shape, dtype=t.uint8, device=dev))
+            else:
+                rows = dict(reward_seq=np.zeros(shape, np.float32), done_seq=np.zeros(shape, np.uint8),
+                            status_seq=np.zeros(shape, np.uint8))
+            self._out_seq = dict(self._out, substeps=sub, **rows)
+        return self._out_seq
 
     def _repeat_out(self):
         if self._out_rep is None:

@@ -64,7 +64,11 @@ EXPERIMENTS = {"stampsr": ["-DMEV_STAMPS", "-DMEV_STAMPS_R"],
                "noroundb": ["-DMEV_EXP_NOROUNDB"],
                # k_step's phase-1 ILP (agents per pass) 3 / 4, the early split's 2, LiDAR probes per ray 1 / 4
                "p1ilp3": ["-DMEV_PHASE1_ILP=3"], "p1ilp4": ["-DMEV_PHASE1_ILP=4"], "eilp2": ["-DMEV_ESPLIT_ILP=2"],
-               "npr1": ["-DMEV_LIDAR_NPR=1"], "npr4": ["-DMEV_LIDAR_NPR=4"]}
+               "npr1": ["-DMEV_LIDAR_NPR=1"], "npr4": ["-DMEV_LIDAR_NPR=4"],
+               # the plan rollout (k_cars_repeat<.., SEQ>) issuing a sub-step's action load ahead of the
+               # previous sub-step's row stores instead of in its own cars_pre (exact; measured slower:
+               # tools/bench_sequence.py)
+               "seqearly": ["-DMEV_SEQ_EARLY_LOAD"]}
 
 
 def build(name: str, force: bool = False) -> str:
