@@ -497,30 +497,43 @@ class Handle:
         spawn_route, if given, is [repeat][E].  device=True: every array (a `substeps` entry of
         `out` included) is a device tensor/pointer.  gather: not supported (the library rejects it)."""
         if not device:
-            actions = np.ascontiguousarray(actions, np.float32)
-            if actions.size != self.E * self.N * 2:
-                raise ValueError(f"actions must have {self.E}x{self.N}x2 elements, got {actions.shape}")
-            if spawn_route is not None:
-                spawn_route = np.ascontiguousarray(np.asarray(spawn_route, np.int32))
-                if spawn_route.shape != (int(repeat), self.E):
-                    raise ValueError(f"spawn_route must be [{int(repeat)}][{self.E}], got {spawn_route.shape}")
-            if out is None:
-                out = self.alloc_outputs()
-            if out.get("substeps") is None:
-                out["substeps"] = np.zeros(self.E, np.int32)
+            actions, spawn_route, out = self._window_host(actions, False, int(repeat), spawn_route, out)
         out = out if out is not None else {}
         a = MevRepeatArgs()
-        for k in _OUT_KEYS:
-            setattr(a.step, k, _ptr(out.get(k)))
-        a.step.actions = _ptr(actions)
+        self._fill_step_args(a.step, out, actions, spawn_route, auto_reset, device, gather)
         a.step.dt = float(dt)
-        a.step.spawn_route = _ptr(spawn_route)
-        a.step.flags = ((MEV_DEVICE_PTRS if device else 0) | (MEV_AUTO_RESET if auto_reset else 0) |
-                        (MEV_GATHER_TO_ROOT if gather else 0))
         a.repeat = int(repeat)
         a.substeps = _ptr(out.get("substeps"))
         _check(self._lib.mev_step_repeat(self._h, ctypes.byref(a)))
         return out
+
+    def _window_host(self, actions, plan, n, spawn_route, out):
+        """Host mode of a window of n sub-steps (step_repeat, step_sequence): actions as float32,
+        one held [E][N][2] row or (plan) n rows; spawn_route as [n][E] int32; `out` with the
+        outputs of `step` and `substeps`."""
+        actions = np.ascontiguousarray(actions, np.float32)
+        if plan and (actions.ndim < 2 or actions.size != n * self.E * self.N * 2):
+            raise ValueError(f"actions must be [T][{self.E}][{self.N}][2], got {actions.shape}")
+        if not plan and actions.size != self.E * self.N * 2:
+            raise ValueError(f"actions must have {self.E}x{self.N}x2 elements, got {actions.shape}")
+        if spawn_route is not None:
+            spawn_route = np.ascontiguousarray(np.asarray(spawn_route, np.int32))
+            if spawn_route.shape != (n, self.E):
+                raise ValueError(f"spawn_route must be [{n}][{self.E}], got {spawn_route.shape}")
+        if out is None:
+            out = self.alloc_outputs()
+        if out.get("substeps") is None:
+            out["substeps"] = np.zeros(self.E, np.int32)
+        return actions, spawn_route, out
+
+    @staticmethod
+    def _fill_step_args(a, out, actions, spawn_route, auto_reset, device, gather):
+        for k in _OUT_KEYS:
+            setattr(a, k, _ptr(out.get(k)))
+        a.actions = _ptr(actions)
+        a.spawn_route = _ptr(spawn_route)
+        a.flags = ((MEV_DEVICE_PTRS if device else 0) | (MEV_AUTO_RESET if auto_reset else 0) |
+                   (MEV_GATHER_TO_ROOT if gather else 0))
 
     def step_sequence(self, actions, dt=1.0 / 60.0, out: Optional[dict] = None, spawn_route=None,
                       auto_reset: bool = False, device: bool = False, gather: bool = False, length: Optional[int] = None):
@@ -540,28 +553,13 @@ class Handle:
             length = int(shape[0])
         T = int(length)
         if not device:
-            actions = np.ascontiguousarray(actions, np.float32)
-            if actions.ndim < 2 or actions.size != T * self.E * self.N * 2:
-                raise ValueError(f"actions must be [T][{self.E}][{self.N}][2], got {actions.shape}")
-            if spawn_route is not None:
-                spawn_route = np.ascontiguousarray(np.asarray(spawn_route, np.int32))
-                if spawn_route.shape != (T, self.E):
-                    raise ValueError(f"spawn_route must be [{T}][{self.E}], got {spawn_route.shape}")
-            if out is None:
-                out = self.alloc_outputs()
-            if out.get("substeps") is None:
-                out["substeps"] = np.zeros(self.E, np.int32)
+            actions, spawn_route, out = self._window_host(actions, True, T, spawn_route, out)
             for k, dtype in zip(_SEQ_KEYS, (np.float32, np.uint8, np.uint8)):
                 if out.get(k) is None or out[k].shape != (T, self.E, self.N):
                     out[k] = np.zeros((T, self.E, self.N), dtype)
         out = out if out is not None else {}
         a = MevSequenceArgs()
-        for k in _OUT_KEYS:
-            setattr(a.step, k, _ptr(out.get(k)))
-        a.step.actions = _ptr(actions)
-        a.step.spawn_route = _ptr(spawn_route)
-        a.step.flags = ((MEV_DEVICE_PTRS if device else 0) | (MEV_AUTO_RESET if auto_reset else 0) |
-                        (MEV_GATHER_TO_ROOT if gather else 0))
+        self._fill_step_args(a.step, out, actions, spawn_route, auto_reset, device, gather)
         a.length = T
         dts = None
         if np.ndim(dt) == 0:

@@ -255,6 +255,15 @@ struct mev_handle {
     }
 };
 
+// a scratch buffer of host-mode calls, made (zeroed, freed with the handle) at the first call that wants it
+template <class T>
+static int scratch(mev_handle* h, bool wanted, T** p, size_t n) {
+    if (!wanted || *p) return MEV_OK;
+    const hipError_t err = h->alloc(p, n);
+    if (err == hipSuccess) return MEV_OK;
+    return fail(MEV_E_NOMEM, std::string("device allocation failed: ") + hipGetErrorString(err));
+}
+
 extern "C" {
 
 static int serve_stop(mev_handle* h);  // with mev_step: the resident step server leaves the stream
@@ -963,39 +972,41 @@ int mev_default_traffic_routes(const mev_handle* h, int32_t* routes, int32_t* co
     return MEV_OK;
 }
 
-static mev::Outputs resolve_outputs(mev_handle* h, float* obs, float* rew, uint8_t* done, uint8_t* status, uint8_t* term,
-                                    uint8_t* trunc, int32_t* alive, int32_t* step, bool device) {
+// (the caller's output pointers travel as a mev_step_args: its eight output fields, each optional)
+static mev::Outputs resolve_outputs(mev_handle* h, const mev_step_args& a, bool device) {
     mev::Outputs o = h->internal;
     if (device) {
-        if (obs) o.obs = obs;
-        if (rew) o.rew = rew;
-        if (done) o.done = done;
-        if (status) o.status = status;
-        if (term) o.term = term;
-        if (trunc) o.trunc = trunc;
-        if (alive) o.alive_cnt = alive;
-        if (step) o.step = step;
+        if (a.obs) o.obs = a.obs;
+        if (a.reward) o.rew = a.reward;
+        if (a.done) o.done = a.done;
+        if (a.status) o.status = a.status;
+        if (a.terminated) o.term = a.terminated;
+        if (a.truncated) o.trunc = a.truncated;
+        if (a.agents_alive) o.alive_cnt = a.agents_alive;
+        if (a.step) o.step = a.step;
     }
     return o;
 }
 
-static int copy_out(mev_handle* h, const mev::Outputs& src, float* obs, float* rew, uint8_t* done, uint8_t* status,
-                    uint8_t* term, uint8_t* trunc, int32_t* alive, int32_t* step, hipMemcpyKind kind) {
+static int copy_out(mev_handle* h, const mev::Outputs& src, const mev_step_args& a, hipMemcpyKind kind) {
     const size_t E = size_t(h->cfg.num_envs), EN = E * size_t(h->cfg.num_agents);
     auto cp = [&](void* dst, const void* s, size_t bytes) -> hipError_t {
         if (!dst || dst == s) return hipSuccess;
         return hipMemcpyAsync(dst, s, bytes, kind, h->stream);
     };
-    HIP_TRY(cp(obs, src.obs, EN * size_t(h->D) * sizeof(float)));
-    HIP_TRY(cp(rew, src.rew, EN * sizeof(float)));
-    HIP_TRY(cp(done, src.done, EN));
-    HIP_TRY(cp(status, src.status, EN));
-    HIP_TRY(cp(term, src.term, E));
-    HIP_TRY(cp(trunc, src.trunc, E));
-    HIP_TRY(cp(alive, src.alive_cnt, E * sizeof(int32_t)));
-    HIP_TRY(cp(step, src.step, E * sizeof(int32_t)));
+    HIP_TRY(cp(a.obs, src.obs, EN * size_t(h->D) * sizeof(float)));
+    HIP_TRY(cp(a.reward, src.rew, EN * sizeof(float)));
+    HIP_TRY(cp(a.done, src.done, EN));
+    HIP_TRY(cp(a.status, src.status, EN));
+    HIP_TRY(cp(a.terminated, src.term, E));
+    HIP_TRY(cp(a.truncated, src.trunc, E));
+    HIP_TRY(cp(a.agents_alive, src.alive_cnt, E * sizeof(int32_t)));
+    HIP_TRY(cp(a.step, src.step, E * sizeof(int32_t)));
     return MEV_OK;
 }
+
+// spawn probability, TrafficFlow.cpp:321-322 (host glibc expf, bit-identical to the reference)
+static float spawn_prob(const mev_handle* h, float dt) { return 1.0f - expf(-h->cfg.traffic_density * dt); }
 
 int mev_reset(mev_handle* h, const uint8_t* env_mask, float* obs, uint32_t flags) {
     if (!h) return fail(MEV_E_INVALID, "null handle");
@@ -1349,11 +1360,8 @@ int mev_step(mev_handle* h, const mev_step_args* a) {
             in.spawn_route = h->d_spawn;
         }
     }
-    // spawn probability, TrafficFlow.cpp:321-322 (host glibc expf, bit-identical to the reference)
-    in.spawn_prob = 1.0f - expf(-h->cfg.traffic_density * a->dt);
-    mev::Outputs o = pinned ? h->pin_out
-                            : resolve_outputs(h, a->obs, a->reward, a->done, a->status, a->terminated, a->truncated,
-                                              a->agents_alive, a->step, dev);
+    in.spawn_prob = spawn_prob(h, a->dt);
+    mev::Outputs o = pinned ? h->pin_out : resolve_outputs(h, *a, dev);
     const int slot = int(h->gathers & 1);
     if (gather) {
         // this rank's packed slot: on the root its own row of the gather buffer
@@ -1454,9 +1462,99 @@ int mev_step(mev_handle* h, const mev_step_args* a) {
         cp(a->agents_alive, 8, E_ * sizeof(int32_t));
         cp(a->step, 9, E_ * sizeof(int32_t));
     } else if (!dev) {
-        int r = copy_out(h, o, a->obs, a->reward, a->done, a->status, a->terminated, a->truncated, a->agents_alive,
-                         a->step, hipMemcpyDeviceToHost);
+        int r = copy_out(h, o, *a, hipMemcpyDeviceToHost);
         if (r) return r;
+        HIP_TRY(hipStreamSynchronize(h->stream));
+    }
+    return MEV_OK;
+}
+
+// A window (mev_step_repeat, mev_step_sequence; include/marlenv.h): up to n sub-steps of every env
+// in one launch, one LiDAR cast.  Each entry point checks its own arguments and describes its
+// window; step_window runs it.
+struct WindowArgs {
+    int n;                // sub-steps, 1..MEV_MAX_REPEAT
+    bool plan;            // step.actions is [n][E][N][2], a row per sub-step (else: one held [E][N][2] row)
+    const float* dt_seq;  // optional [n], host (else step.dt in every sub-step)
+    int32_t* substeps;    // optional [E]
+    float* reward_seq;    // optional [n][E][N] rows of the sub-steps' own outputs (a plan's)
+    uint8_t* done_seq;
+    uint8_t* status_seq;
+};
+
+static int step_window(mev_handle* h, const mev_step_args* a, const WindowArgs& w) {
+    static_assert(mev::kMaxSeq == MEV_MAX_REPEAT, "the kernel's by-value dt / spawn_prob rows");
+    HIP_TRY(hipSetDevice(h->cfg.device));
+    if (int r = serve_stop(h)) return r;  // (the server holds the stream)
+    const bool dev = (a->flags & MEV_DEVICE_PTRS) != 0;
+    const int n = w.n;
+    const size_t E = size_t(h->cfg.num_envs), EN = E * size_t(h->cfg.num_agents);
+    // host mode stages its arrays in per-handle buffers sized for MEV_MAX_REPEAT rows
+    const size_t cap = size_t(MEV_MAX_REPEAT);
+    if (!dev && (scratch(h, w.plan, &h->d_act_seq, cap * EN * 2) ||
+                 scratch(h, a->spawn_route != nullptr, &h->d_spawn_rep, cap * E) ||
+                 scratch(h, w.substeps != nullptr, &h->d_substeps, E) ||
+                 scratch(h, w.reward_seq != nullptr, &h->d_rew_seq, cap * EN) ||
+                 scratch(h, w.done_seq != nullptr, &h->d_done_seq, cap * EN) ||
+                 scratch(h, w.status_seq != nullptr, &h->d_status_seq, cap * EN)))
+        return MEV_E_NOMEM;
+    // a held action: one row, staged where mev_step stages it, and no rows for the kernel
+    mev::SeqRows rows{};
+    size_t act_rows = 1;
+    float* d_act = h->d_actions;
+    const mev::SeqRows* krows = nullptr;
+    if (w.plan) {
+        act_rows = size_t(n);
+        d_act = h->d_act_seq;
+        krows = &rows;
+    }
+    // each row's dt and spawn probability (as mev_step), read from the caller's memory now; a
+    // plan's travel by value with the kernel's arguments
+    for (size_t s = 0; s < act_rows; ++s) {
+        rows.dt[s] = w.dt_seq ? w.dt_seq[s] : a->dt;
+        rows.spawn_prob[s] = spawn_prob(h, rows.dt[s]);
+    }
+    mev::StepInputs in{};
+    in.dt = rows.dt[0];
+    in.spawn_prob = rows.spawn_prob[0];
+    in.auto_reset = (a->flags & MEV_AUTO_RESET) ? 1 : 0;
+    in.rng_counter = h->rng_counter;  // sub-step s: + s (k_cars_repeat)
+    h->rng_counter += uint64_t(n);
+    int32_t* d_sub = nullptr;
+    if (dev) {
+        in.actions = a->actions;
+        in.spawn_route = a->spawn_route;
+        d_sub = w.substeps;
+        rows.reward = w.reward_seq;
+        rows.done = w.done_seq;
+        rows.status = w.status_seq;
+    } else {
+        HIP_TRY(hipMemcpyAsync(d_act, a->actions, act_rows * EN * 2 * sizeof(float), hipMemcpyHostToDevice, h->stream));
+        in.actions = d_act;
+        if (a->spawn_route) {
+            HIP_TRY(hipMemcpyAsync(h->d_spawn_rep, a->spawn_route, size_t(n) * E * sizeof(int32_t), hipMemcpyHostToDevice,
+                                   h->stream));
+            in.spawn_route = h->d_spawn_rep;
+        }
+        if (w.substeps) d_sub = h->d_substeps;
+        if (w.reward_seq) rows.reward = h->d_rew_seq;
+        if (w.done_seq) rows.done = h->d_done_seq;
+        if (w.status_seq) rows.status = h->d_status_seq;
+    }
+    const mev::Outputs o = resolve_outputs(h, *a, dev);
+    h->deal_valid = false;  // NPC counts change outside the fused step: the deal restarts
+    HIP_TRY(mev::launch_step_window(h->sp, in, o, n, krows, d_sub, h->stream));
+    h->last = o;
+    if (!dev) {
+        if (int r = copy_out(h, o, *a, hipMemcpyDeviceToHost)) return r;
+        if (w.substeps)
+            HIP_TRY(hipMemcpyAsync(w.substeps, d_sub, E * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+        if (w.reward_seq)
+            HIP_TRY(hipMemcpyAsync(w.reward_seq, rows.reward, size_t(n) * EN * sizeof(float), hipMemcpyDeviceToHost,
+                                   h->stream));
+        if (w.done_seq) HIP_TRY(hipMemcpyAsync(w.done_seq, rows.done, size_t(n) * EN, hipMemcpyDeviceToHost, h->stream));
+        if (w.status_seq)
+            HIP_TRY(hipMemcpyAsync(w.status_seq, rows.status, size_t(n) * EN, hipMemcpyDeviceToHost, h->stream));
         HIP_TRY(hipStreamSynchronize(h->stream));
     }
     return MEV_OK;
@@ -1469,52 +1567,7 @@ int mev_step_repeat(mev_handle* h, const mev_repeat_args* ra) {
     if (ra->repeat < 1 || ra->repeat > MEV_MAX_REPEAT)
         return fail(MEV_E_INVALID, "repeat must be in 1.." + std::to_string(MEV_MAX_REPEAT));
     if (a->flags & MEV_GATHER_TO_ROOT) return fail(MEV_E_INVALID, "mev_step_repeat does not gather (MEV_GATHER_TO_ROOT)");
-    HIP_TRY(hipSetDevice(h->cfg.device));
-    if (int r = serve_stop(h)) return r;  // (the server holds the stream)
-    const bool dev = (a->flags & MEV_DEVICE_PTRS) != 0;
-    const int n = ra->repeat;
-    const size_t E = size_t(h->cfg.num_envs), EN = E * size_t(h->cfg.num_agents);
-    if (!dev) {
-        hipError_t err = hipSuccess;
-        if (a->spawn_route && !h->d_spawn_rep) err = h->alloc(&h->d_spawn_rep, size_t(MEV_MAX_REPEAT) * E);
-        if (err == hipSuccess && ra->substeps && !h->d_substeps) err = h->alloc(&h->d_substeps, E);
-        if (err != hipSuccess) return fail(MEV_E_NOMEM, std::string("device allocation failed: ") + hipGetErrorString(err));
-    }
-    mev::StepInputs in{};
-    in.dt = a->dt;
-    in.auto_reset = (a->flags & MEV_AUTO_RESET) ? 1 : 0;
-    in.rng_counter = h->rng_counter;  // sub-step s: + s (k_cars_repeat)
-    h->rng_counter += uint64_t(n);
-    int32_t* d_sub = nullptr;
-    if (dev) {
-        in.actions = a->actions;
-        in.spawn_route = a->spawn_route;
-        d_sub = ra->substeps;
-    } else {
-        HIP_TRY(hipMemcpyAsync(h->d_actions, a->actions, EN * 2 * sizeof(float), hipMemcpyHostToDevice, h->stream));
-        in.actions = h->d_actions;
-        if (a->spawn_route) {
-            HIP_TRY(hipMemcpyAsync(h->d_spawn_rep, a->spawn_route, size_t(n) * E * sizeof(int32_t), hipMemcpyHostToDevice,
-                                   h->stream));
-            in.spawn_route = h->d_spawn_rep;
-        }
-        if (ra->substeps) d_sub = h->d_substeps;
-    }
-    in.spawn_prob = 1.0f - expf(-h->cfg.traffic_density * a->dt);  // as mev_step
-    const mev::Outputs o = resolve_outputs(h, a->obs, a->reward, a->done, a->status, a->terminated, a->truncated,
-                                           a->agents_alive, a->step, dev);
-    h->deal_valid = false;  // NPC counts change outside the fused step: the deal restarts
-    HIP_TRY(mev::launch_step_repeat(h->sp, in, o, n, d_sub, h->stream));
-    h->last = o;
-    if (!dev) {
-        if (int r = copy_out(h, o, a->obs, a->reward, a->done, a->status, a->terminated, a->truncated, a->agents_alive,
-                             a->step, hipMemcpyDeviceToHost))
-            return r;
-        if (ra->substeps)
-            HIP_TRY(hipMemcpyAsync(ra->substeps, d_sub, E * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(hipStreamSynchronize(h->stream));
-    }
-    return MEV_OK;
+    return step_window(h, a, WindowArgs{ra->repeat, false, nullptr, ra->substeps, nullptr, nullptr, nullptr});
 }
 
 int mev_step_sequence(mev_handle* h, const mev_sequence_args* sa) {
@@ -1524,80 +1577,8 @@ int mev_step_sequence(mev_handle* h, const mev_sequence_args* sa) {
     if (sa->length < 1 || sa->length > MEV_MAX_REPEAT)
         return fail(MEV_E_INVALID, "length must be in 1.." + std::to_string(MEV_MAX_REPEAT));
     if (a->flags & MEV_GATHER_TO_ROOT) return fail(MEV_E_INVALID, "mev_step_sequence does not gather (MEV_GATHER_TO_ROOT)");
-    static_assert(mev::kMaxSeq == MEV_MAX_REPEAT, "the kernel's by-value dt / spawn_prob rows");
-    HIP_TRY(hipSetDevice(h->cfg.device));
-    if (int r = serve_stop(h)) return r;  // (the server holds the stream)
-    const bool dev = (a->flags & MEV_DEVICE_PTRS) != 0;
-    const int n = sa->length;
-    const size_t E = size_t(h->cfg.num_envs), EN = E * size_t(h->cfg.num_agents);
-    if (!dev) {
-        const size_t cap = size_t(MEV_MAX_REPEAT);
-        hipError_t err = hipSuccess;
-        if (!h->d_act_seq) err = h->alloc(&h->d_act_seq, cap * EN * 2);
-        if (err == hipSuccess && a->spawn_route && !h->d_spawn_rep) err = h->alloc(&h->d_spawn_rep, cap * E);
-        if (err == hipSuccess && sa->substeps && !h->d_substeps) err = h->alloc(&h->d_substeps, E);
-        if (err == hipSuccess && sa->reward_seq && !h->d_rew_seq) err = h->alloc(&h->d_rew_seq, cap * EN);
-        if (err == hipSuccess && sa->done_seq && !h->d_done_seq) err = h->alloc(&h->d_done_seq, cap * EN);
-        if (err == hipSuccess && sa->status_seq && !h->d_status_seq) err = h->alloc(&h->d_status_seq, cap * EN);
-        if (err != hipSuccess) return fail(MEV_E_NOMEM, std::string("device allocation failed: ") + hipGetErrorString(err));
-    }
-    mev::StepInputs in{};
-    // dt and the spawn probability (host glibc expf, as mev_step) of every sub-step, read from
-    // the caller's memory now and passed by value with the kernel's arguments
-    mev::SeqRows rows{};
-    for (int s = 0; s < n; ++s) {
-        const float dt = sa->dt_seq ? sa->dt_seq[s] : a->dt;
-        rows.dt[s] = dt;
-        rows.spawn_prob[s] = 1.0f - expf(-h->cfg.traffic_density * dt);
-    }
-    in.dt = rows.dt[0];
-    in.spawn_prob = rows.spawn_prob[0];
-    in.auto_reset = (a->flags & MEV_AUTO_RESET) ? 1 : 0;
-    in.rng_counter = h->rng_counter;  // sub-step s: + s (k_cars_repeat)
-    h->rng_counter += uint64_t(n);
-    int32_t* d_sub = nullptr;
-    if (dev) {
-        in.actions = a->actions;
-        in.spawn_route = a->spawn_route;
-        d_sub = sa->substeps;
-        rows.reward = sa->reward_seq;
-        rows.done = sa->done_seq;
-        rows.status = sa->status_seq;
-    } else {
-        HIP_TRY(hipMemcpyAsync(h->d_act_seq, a->actions, size_t(n) * EN * 2 * sizeof(float), hipMemcpyHostToDevice,
-                               h->stream));
-        in.actions = h->d_act_seq;
-        if (a->spawn_route) {
-            HIP_TRY(hipMemcpyAsync(h->d_spawn_rep, a->spawn_route, size_t(n) * E * sizeof(int32_t), hipMemcpyHostToDevice,
-                                   h->stream));
-            in.spawn_route = h->d_spawn_rep;
-        }
-        if (sa->substeps) d_sub = h->d_substeps;
-        if (sa->reward_seq) rows.reward = h->d_rew_seq;
-        if (sa->done_seq) rows.done = h->d_done_seq;
-        if (sa->status_seq) rows.status = h->d_status_seq;
-    }
-    const mev::Outputs o = resolve_outputs(h, a->obs, a->reward, a->done, a->status, a->terminated, a->truncated,
-                                           a->agents_alive, a->step, dev);
-    h->deal_valid = false;  // NPC counts change outside the fused step: the deal restarts
-    HIP_TRY(mev::launch_step_sequence(h->sp, in, o, n, rows, d_sub, h->stream));
-    h->last = o;
-    if (!dev) {
-        if (int r = copy_out(h, o, a->obs, a->reward, a->done, a->status, a->terminated, a->truncated, a->agents_alive,
-                             a->step, hipMemcpyDeviceToHost))
-            return r;
-        if (sa->substeps)
-            HIP_TRY(hipMemcpyAsync(sa->substeps, d_sub, E * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-        if (sa->reward_seq)
-            HIP_TRY(hipMemcpyAsync(sa->reward_seq, rows.reward, size_t(n) * EN * sizeof(float), hipMemcpyDeviceToHost,
-                                   h->stream));
-        if (sa->done_seq)
-            HIP_TRY(hipMemcpyAsync(sa->done_seq, rows.done, size_t(n) * EN, hipMemcpyDeviceToHost, h->stream));
-        if (sa->status_seq)
-            HIP_TRY(hipMemcpyAsync(sa->status_seq, rows.status, size_t(n) * EN, hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(hipStreamSynchronize(h->stream));
-    }
-    return MEV_OK;
+    return step_window(h, a, WindowArgs{sa->length, true, sa->dt_seq, sa->substeps, sa->reward_seq, sa->done_seq,
+                                    sa->status_seq});
 }
 
 static int sync_internal(mev_handle* h);  // below, with mev_device_outputs
@@ -1611,8 +1592,10 @@ int mev_get_outputs(mev_handle* h, float* obs, float* rew, uint8_t* done, uint8_
     if (h->last.lidar_u8) {  // compact gather row: decoded into the handle's buffers first
         if (int r0 = sync_internal(h)) return r0;
     }
-    int r = copy_out(h, h->last, obs, rew, done, status, term, trunc, alive, step,
-                     dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost);
+    mev_step_args a{};
+    a.obs = obs; a.reward = rew; a.done = done; a.status = status;
+    a.terminated = term; a.truncated = trunc; a.agents_alive = alive; a.step = step;
+    int r = copy_out(h, h->last, a, dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost);
     if (r) return r;
     if (!dev) HIP_TRY(hipStreamSynchronize(h->stream));
     return MEV_OK;
@@ -2075,11 +2058,7 @@ int mev_restore_map(mev_handle* h, const void* src, const int32_t* env_map, uint
             if (env_map[e] < -1 || env_map[e] >= int32_t(E))
                 return fail(MEV_E_RANGE, "env_map[" + std::to_string(e) + "] = " + std::to_string(env_map[e]) +
                                              " is outside [-1, " + std::to_string(E) + ")");
-        if (!h->d_env_map) {
-            const hipError_t err = h->alloc(&h->d_env_map, E);
-            if (err != hipSuccess)
-                return fail(MEV_E_NOMEM, std::string("device allocation failed: ") + hipGetErrorString(err));
-        }
+        if (int r = scratch(h, true, &h->d_env_map, E)) return r;
     }
     // envs the map leaves alone keep their current outputs: bring those into the handle's own
     // buffers, the restore's targets, first (as a masked mev_restore)

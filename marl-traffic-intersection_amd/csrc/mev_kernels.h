@@ -210,19 +210,18 @@ inline StepPlan plan_step(const SimParams& p) { return plan_step(step_shape(p));
 // dp: a device copy of p (k_step reads its parameters through it)
 hipError_t launch_step(const SimParams& p, const SimParams* dp, const StepInputs& in, const Outputs& out,
                        hipStream_t s, const hipEvent_t* ev = nullptr);
-// The frame-skip call: up to `repeat` sub-steps of the car part per env in one launch
-// (k_cars_repeat: the state stays on the CU in between), then one k_lidar cast from the
-// state each env stopped at.  in.spawn_route, if given, is [repeat][E]; sub-step s uses
+// A window (mev_step_repeat, mev_step_sequence): up to n sub-steps of the car part per env in one
+// launch (k_cars_repeat: the state stays on the CU in between), then one k_lidar cast from the
+// state each env stopped at.  in.spawn_route, if given, is [n][E]; sub-step s uses
 // in.rng_counter + s.  substeps (nullable): [E] sub-steps executed.  Every shape k_cars runs.
-hipError_t launch_step_repeat(const SimParams& p, const StepInputs& in, const Outputs& out, int repeat,
-                              int32_t* substeps, hipStream_t s);
-// The plan-rollout call (mev_step_sequence): launch_step_repeat's loop with an action row, a dt
-// and a spawn probability of its own per sub-step (k_cars_repeat<TRAFFIC, SEQ = true>).
-// in.actions is [length][E][N][2], in.spawn_route (if given) [length][E]; in.dt and
+// rows == nullptr (frame skip): the action in.actions [E][N][2] is held, with in.dt and
+// in.spawn_prob, for every sub-step.
+// rows (a plan rollout, n <= kMaxSeq): an action row, a dt and a spawn probability of its own
+// per sub-step (k_cars_repeat<TRAFFIC, SEQ = true>).  in.actions is [n][E][N][2]; in.dt and
 // in.spawn_prob are not read: sub-step s takes dt[s] and spawn_prob[s], which travel by value
-// in the kernel's argument segment.  reward_seq / done_seq / status_seq (each nullable) are
-// [length][E][N]: row s holds sub-step s's own outputs for the envs that ran it, zero after
-// an env stopped (the wave that stops writes its remaining rows itself).
+// in the kernel's argument segment.  reward / done / status (each nullable) are [n][E][N]: row
+// s holds sub-step s's own outputs for the envs that ran it, zero after an env stopped (the
+// wave that stops writes its remaining rows itself).
 constexpr int kMaxSeq = 64;  // == MEV_MAX_REPEAT
 struct SeqRows {
     float* reward;
@@ -231,8 +230,8 @@ struct SeqRows {
     float dt[kMaxSeq];
     float spawn_prob[kMaxSeq];
 };
-hipError_t launch_step_sequence(const SimParams& p, const StepInputs& in, const Outputs& out, int length,
-                                const SeqRows& rows, int32_t* substeps, hipStream_t s);
+hipError_t launch_step_window(const SimParams& p, const StepInputs& in, const Outputs& out, int n,
+                              const SeqRows* rows, int32_t* substeps, hipStream_t s);
 hipError_t launch_reset(const SimParams& p, const uint8_t* env_mask, const Outputs& out, hipStream_t s,
                         uint64_t rng_counter);
 // recompute the observation rows from the current state with LiDAR = max (after set_state)

@@ -3882,20 +3882,26 @@ __global__ __launch_bounds__(WAVE) void k_reset(SimParams p, const uint8_t* mask
         obs_exact_pass<TRAFFIC, TRAFFIC>(p, m, dl, el, nl, ncnt, out.obs + (size_t)e * N * p.D, (size_t)p.D);
 }
 
-// repeat > 0: the frame-skip call's looping car kernel in k_cars' place (rows: its plan-rollout form)
+// a window's sub-steps (launch_step_window): n, the [E] sub-step counts, the plan's rows (null: a held action)
+struct Window {
+    int n;
+    int32_t* substeps;
+    const SeqRows* rows;
+};
+
+// w: the window's looping car kernel in k_cars' place
 static hipError_t launch_part(const SimParams& p, const StepInputs& in, const Outputs& out, int e0, int e1,
-                              hipStream_t s, const hipEvent_t* ev, int repeat = 0, int32_t* substeps = nullptr,
-                              const SeqRows* rows = nullptr) {
+                              hipStream_t s, const hipEvent_t* ev, const Window* w = nullptr) {
     // k_cars then k_lidar over the envs [e0, e1)
     if (e1 <= e0) return hipSuccess;
     if (ev) (void)hipEventRecord(ev[0], s);
     const unsigned cars_lds = (unsigned)cars_lds_bytes(p.N, cars_k(p), true);
-    if (repeat > 0 && rows) {
-        const SeqArgs sa{RepeatArgs{p, in, out, e0, repeat, substeps}, *rows};
+    if (w && w->rows) {
+        const SeqArgs sa{RepeatArgs{p, in, out, e0, w->n, w->substeps}, *w->rows};
         if (p.traffic) hipLaunchKernelGGL((k_cars_repeat<true, true>), dim3(e1 - e0), dim3(WAVE), cars_lds, s, sa);
         else hipLaunchKernelGGL((k_cars_repeat<false, true>), dim3(e1 - e0), dim3(WAVE), cars_lds, s, sa);
-    } else if (repeat > 0) {
-        const RepeatArgs ra{p, in, out, e0, repeat, substeps};
+    } else if (w) {
+        const RepeatArgs ra{p, in, out, e0, w->n, w->substeps};
         if (p.traffic) hipLaunchKernelGGL(k_cars_repeat<true>, dim3(e1 - e0), dim3(WAVE), cars_lds, s, ra);
         else hipLaunchKernelGGL(k_cars_repeat<false>, dim3(e1 - e0), dim3(WAVE), cars_lds, s, ra);
     } else if (p.traffic) hipLaunchKernelGGL(k_cars<true>, dim3(e1 - e0), dim3(WAVE), cars_lds, s, p, in, out, e0);
@@ -3961,16 +3967,11 @@ hipError_t launch_step(const SimParams& p, const SimParams* dp, const StepInputs
     return e;
 }
 
-hipError_t launch_step_repeat(const SimParams& p, const StepInputs& in, const Outputs& out, int repeat,
-                              int32_t* substeps, hipStream_t s) {
-    if (repeat < 1) return hipErrorInvalidValue;
-    return launch_part(p, in, out, 0, p.E, s, nullptr, repeat, substeps);
-}
-
-hipError_t launch_step_sequence(const SimParams& p, const StepInputs& in, const Outputs& out, int length,
-                                const SeqRows& rows, int32_t* substeps, hipStream_t s) {
-    if (length < 1 || length > kMaxSeq) return hipErrorInvalidValue;
-    return launch_part(p, in, out, 0, p.E, s, nullptr, length, substeps, &rows);
+hipError_t launch_step_window(const SimParams& p, const StepInputs& in, const Outputs& out, int n,
+                              const SeqRows* rows, int32_t* substeps, hipStream_t s) {
+    if (n < 1 || (rows && n > kMaxSeq)) return hipErrorInvalidValue;
+    const Window w{n, substeps, rows};
+    return launch_part(p, in, out, 0, p.E, s, nullptr, &w);
 }
 
 hipError_t launch_serve(const SimParams& p, const SimParams* dp, const ServeArgs& sa, const Outputs& out,

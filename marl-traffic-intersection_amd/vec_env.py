@@ -209,20 +209,11 @@ class VecIntersectionEnv:
         once, and info["substeps"] [E] says how many sub-steps each env ran; spawn_route is then
         [repeat][E]."""
         n = self.frame_skip if repeat is None else int(repeat)
-        o = self._out if n == 1 else self._repeat_out()
+        o = self._out if n == 1 else self._window_out()
         if self.backend == "torch":
-            t = self._torch
             self._bind_stream()
-            a = actions
-            if not (isinstance(a, t.Tensor) and a.is_cuda and a.dtype == t.float32 and a.is_contiguous()):
-                a = t.as_tensor(a, dtype=t.float32, device=o["obs"].device).contiguous()
-            if a.numel() != self.num_envs * self.num_agents * 2:
-                raise ValueError(f"actions must be [{self.num_envs}, {self.num_agents}, 2], got {tuple(a.shape)}")
-            if a.device.index != self.device_index:
-                raise ValueError("actions are on another device")
-            sp = None
-            if spawn_route is not None:
-                sp = t.as_tensor(spawn_route, dtype=t.int32, device=o["obs"].device).contiguous()
+            a = self._actions_tensor(actions, plan=False)
+            sp = self._spawn_tensor(spawn_route)
             if n == 1:
                 self._h.step(a, float(dt), out=o, spawn_route=sp, auto_reset=self.auto_reset, device=True)
             else:
@@ -252,29 +243,17 @@ class VecIntersectionEnv:
         the current stream, zero-copy; the returned tensors are reused by the next call with
         the same T."""
         if self.backend == "torch":
-            t = self._torch
             self._bind_stream()
-            dev = self._out["obs"].device
-            a = actions
-            if not (isinstance(a, t.Tensor) and a.is_cuda and a.dtype == t.float32 and a.is_contiguous()):
-                a = t.as_tensor(a, dtype=t.float32, device=dev).contiguous()
-            if a.dim() < 2 or a.numel() != a.shape[0] * self.num_envs * self.num_agents * 2:
-                raise ValueError(f"actions must be [T, {self.num_envs}, {self.num_agents}, 2], got {tuple(a.shape)}")
-            if a.device.index != self.device_index:
-                raise ValueError("actions are on another device")
+            a = self._actions_tensor(actions, plan=True)
             T = int(a.shape[0])
-            o = self._sequence_out(T)
-            sp = None
-            if spawn_route is not None:
-                sp = t.as_tensor(spawn_route, dtype=t.int32, device=dev).contiguous()
-                if tuple(sp.shape) != (T, self.num_envs):
-                    raise ValueError(f"spawn_route must be [{T}][{self.num_envs}], got {tuple(sp.shape)}")
+            o = self._window_out(T)
+            sp = self._spawn_tensor(spawn_route, T)
             self._h.step_sequence(a, dt, out=o, spawn_route=sp, auto_reset=self.auto_reset, device=True, length=T)
             if copy:
                 o = {k: v.clone() for k, v in o.items()}
         else:
             T = int(np.shape(actions)[0])
-            o = self._sequence_out(T)
+            o = self._window_out(T)
             self._h.step_sequence(actions, dt, out=o, spawn_route=spawn_route, auto_reset=self.auto_reset)
             if copy:
                 o = {k: v.copy() for k, v in o.items()}
@@ -282,32 +261,47 @@ class VecIntersectionEnv:
                                   "status_seq")}
         return o["obs"], o["reward"], o["terminated"], o["truncated"], info
 
-    def _sequence_out(self, T):
-        """The step's output buffers plus substeps and the [T, E, N] per-step rows (kept per T)."""
-        if not 1 <= T <= _capi.MEV_MAX_REPEAT:
+    def _actions_tensor(self, actions, plan):
+        """actions as a contiguous float32 tensor on this env's device: [E, N, 2], or (plan) [T, E, N, 2]."""
+        t = self._torch
+        a = actions
+        if not (isinstance(a, t.Tensor) and a.is_cuda and a.dtype == t.float32 and a.is_contiguous()):
+            a = t.as_tensor(a, dtype=t.float32, device=self._out["obs"].device).contiguous()
+        if (plan and a.dim() < 2) or a.numel() != (a.shape[0] if plan else 1) * self.num_envs * self.num_agents * 2:
+            raise ValueError(f"actions must be [{'T, ' if plan else ''}{self.num_envs}, {self.num_agents}, 2], "
+                             f"got {tuple(a.shape)}")
+        if a.device.index != self.device_index:
+            raise ValueError("actions are on another device")
+        return a
+
+    def _spawn_tensor(self, spawn_route, rows=None):
+        """spawn_route (or None) as a contiguous int32 tensor on this env's device; rows: it must be [rows][E]."""
+        if spawn_route is None:
+            return None
+        sp = self._torch.as_tensor(spawn_route, dtype=self._torch.int32, device=self._out["obs"].device).contiguous()
+        if rows is not None and tuple(sp.shape) != (rows, self.num_envs):
+            raise ValueError(f"spawn_route must be [{rows}][{self.num_envs}], got {tuple(sp.shape)}")
+        return sp
+
+    def _window_out(self, T=None):
+        """The step's output buffers plus substeps (made at the first window) and, for a plan of T
+        rows, the [T, E, N] per-step rows (kept per T)."""
+        if T is not None and not 1 <= T <= _capi.MEV_MAX_REPEAT:
             raise ValueError(f"a plan has 1..{_capi.MEV_MAX_REPEAT} rows, got {T}")
+        def zeros(shape, dtype):
+            if self.backend == "torch":
+                return self._torch.zeros(shape, dtype=getattr(self._torch, dtype), device=self._out["obs"].device)
+            return np.zeros(shape, dtype)
+
+        if self._out_rep is None:
+            self._out_rep = dict(self._out, substeps=zeros(self.num_envs, "int32"))
+        if T is None:
+            return self._out_rep
         if self._out_seq is None or self._out_seq["reward_seq"].shape[0] != T:
             shape = (T, self.num_envs, self.num_agents)
-            sub = self._repeat_out()["substeps"]
-            if self.backend == "torch":
-                t, dev = self._torch, self._out["obs"].device
-                rows = dict(reward_seq=t.zeros(shape, dtype=t.float32, device=dev),
-                            done_seq=t.zeros(shape, dtype=t.uint8, device=dev),
-                            status_seq=t.zeros(shape, dtype=t.uint8, device=dev))
-            else:
-                rows = dict(reward_seq=np.zeros(shape, np.float32), done_seq=np.zeros(shape, np.uint8),
-                            status_seq=np.zeros(shape, np.uint8))
-            self._out_seq = dict(self._out, substeps=sub, **rows)
+            self._out_seq = dict(self._out_rep, reward_seq=zeros(shape, "float32"), done_seq=zeros(shape, "uint8"),
+                                 status_seq=zeros(shape, "uint8"))
         return self._out_seq
-
-    def _repeat_out(self):
-        if self._out_rep is None:
-            if self.backend == "torch":
-                sub = self._torch.zeros(self.num_envs, dtype=self._torch.int32, device=self._out["obs"].device)
-            else:
-                sub = np.zeros(self.num_envs, np.int32)
-            self._out_rep = dict(self._out, substeps=sub)
-        return self._out_rep
 
     def observations(self):
         return self._out["obs"]

@@ -8,26 +8,18 @@ import pytest
 
 import golden_replay as G
 import oracle_replay as R
-import repeat_ref as RR
-import sequence_ref as SR
+import window_ref as RR
+from window_ref import DT, OUT_KEYS
 
 pytestmark = pytest.mark.gpu
 
-DT = SR.DT
-OUT_KEYS = ("obs", "reward", "done", "status", "terminated", "truncated", "agents_alive", "step")
 MAP12 = [3, 3, 3, 0, -1, 11, 5, 5, -1, 0, 7, 3]
 
 
-def _handle(mev, E, N, rays, traffic=False, density=0.5, max_npcs=32, max_steps=2000, use_team=True, seed=7):
-    h = mev.Handle(num_envs=E, num_agents=N, lidar_rays=rays, obs_dim=127, use_team_reward=int(use_team),
-                   max_steps=max_steps, traffic_flow=int(traffic), traffic_density=density, max_npcs=max_npcs,
-                   seed=seed, device=0)
-    routes, ids = RR.ego_routes(h.route_id, E, N)
-    h.set_ego_routes(routes)
-    if traffic:
-        h.set_traffic_routes(ids)
-    h.reset()
-    return h, ids
+def _handle(mev, E, N, rays, traffic=False, use_team=True, **cfg):
+    """A handle (team reward unless said otherwise) on the tests' routes, reset; and its traffic-route ids."""
+    h = RR.handle(mev, E, N, rays, traffic=traffic, use_team=use_team, **cfg)
+    return h, RR.set_routes(h, traffic)[1]
 
 
 def _snap_all(h):
@@ -67,11 +59,11 @@ def _continue(tag, h, meta, src_state, src_dims, before_state, before_dims, env_
     for e, m in enumerate(env_map):
         st, dm, i = (before_state, before_dims, e) if m < 0 else (src_state, src_dims, m)
         oracles.append(R.oracle_from_device_state(meta, st, i, traffic_routes, dm if dims else None))
-    ref = SR.SequenceRef(oracles, np.zeros((E, N), np.int32))
+    ref = RR.WindowRef(oracles, np.zeros((E, N), np.int32))
     rng = np.random.default_rng(seed)
     traffic = traffic_routes is not None
     for t in range(10):
-        A, _, sp = SR.draw(rng, E, N, 1, 0.5, traffic)
+        A, _, sp = RR.draw_plan(rng, E, N, 1, 0.5, traffic)
         out = h.step(A[0], DT, spawn_route=None if sp is None else sp[0])
         ws = ref.step(A, [DT], sp, auto_reset=False)
         st = h.get_state()
@@ -80,12 +72,12 @@ def _continue(tag, h, meta, src_state, src_dims, before_state, before_dims, env_
             R.check_step(f"{tag}: step {t} env {e}", out, e, ws[e])
             R.check_state(f"{tag}: step {t} env {e}", st, e, oracles[e], cd)
     T = 4
-    A, dts, sp = SR.draw(rng, E, N, T, 0.5, traffic)
+    A, dts, sp = RR.draw_plan(rng, E, N, T, 0.5, traffic)
     out = h.step_sequence(A, dts, spawn_route=sp)
     ws = ref.step(A, dts, sp, auto_reset=False)
     st = h.get_state()
     for e in range(E):
-        SR.check_plan(f"{tag}: plan env {e}", out, e, ws[e], T)
+        RR.check_window(f"{tag}: plan env {e}", out, e, ws[e], T)
         R.check_state(f"{tag}: plan env {e}", st, e, oracles[e], h.car_dims() if dims else None)
     ref.close()
 
@@ -193,7 +185,7 @@ def test_planner_fan_out_end_to_end(mev):
     root = _snap_all(h)
     snap = h.snapshot()
     h.restore(snap, env_map=np.zeros(E, np.int32))
-    A, dts, _ = SR.draw(rng, E, N, T, 0.6)
+    A, dts, _ = RR.draw_plan(rng, E, N, T, 0.6)
     A[:, 5] = A[:, 2]  # envs 2, 5 and 7 evaluate the same plan
     A[:, 7] = A[:, 2]
     out = h.step_sequence(A, dts)
@@ -201,8 +193,8 @@ def test_planner_fan_out_end_to_end(mev):
     meta = RR.meta(N, rays, use_team=True)
     for e in range(E):
         o = R.oracle_from_device_state(meta, root[0], 0)
-        w = SR.sequence_step(o, A[:, e], dts)
-        SR.check_plan(f"fan-out env {e}", out, e, w, T)
+        w = RR.window_step(o, A[:, e], dts)
+        RR.check_window(f"fan-out env {e}", out, e, w, T)
         R.check_state(f"fan-out env {e}", st, e, o)
         o.close()
     for e in (5, 7):

@@ -1,5 +1,5 @@
 """mev_step_repeat without a device: the header declares it, the library exports it and refuses
-null arguments, and the reference loop the GPU tests compare against (tests/repeat_ref.py) is,
+null arguments, and the reference loop the GPU tests compare against (tests/window_ref.py) is,
 at repeat = 1, the reference's step as its goldens recorded it."""
 import ctypes
 import os
@@ -10,7 +10,7 @@ import pytest
 
 import golden_replay as G
 import oracle_replay as R
-import repeat_ref as RR
+import window_ref as RR
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -54,7 +54,7 @@ def test_reference_loop_at_repeat_one_is_the_recorded_step(name):
     egos = R.state_from_records(d["init_ego_f"], d["init_ego_i"], G.ego_route_ids(o, d, L, cids))
     o.set_state(egos, [], int(meta.get("init_step", 0)))
     for t in range(int(meta["steps"])):
-        w = RR.repeat_step(o, d["actions"][t], float(meta["dt"]), 1)
+        w = RR.window_step(o, *RR.held(d["actions"][t], float(meta["dt"]), 1))
         assert w["substeps"] == 1
         assert G.bits_equal(w["rew"], d["rew"][t]), f"step {t + 1}: reward"
         assert G.bits_equal(w["obs"][:, :127], d["obs"][t]), f"step {t + 1}: obs"

@@ -1,6 +1,6 @@
 """Frame skip (mev_step_repeat, include/marlenv.h) against the oracle: one call that holds the
 actions for up to `repeat` sub-steps and casts the LiDAR once must equal the reference's step
-looped as its driver loops it (test.py:144-155; tests/repeat_ref.py) -- every output, the
+looped as its driver loops it (test.py:144-155; tests/window_ref.py) -- every output, the
 sub-step count and the full state after every call, bit for bit per env.  Each scenario
 asserts on the oracle side that it reached the cases it is about (dones inside a window,
 windows stopped early, every crash status), so it cannot pass by covering nothing."""
@@ -10,66 +10,14 @@ import pytest
 from conftest import STEP_KERNELS, use_step_kernel
 import golden_replay as G
 import oracle_replay as R
-import repeat_ref as RR
+import window_ref as RR
+from window_ref import DT, OUT_KEYS, handle as _handle, start as _start
 
 pytestmark = pytest.mark.gpu
 
-DT = 1.0 / 60.0
-OUT_KEYS = ("obs", "reward", "done", "status", "terminated", "truncated", "agents_alive", "step")
 
-
-def _handle(mev, E, N, rays, use_team=False, respawn=True, max_steps=2000, traffic=False, density=0.5, max_npcs=32,
-            seed=7):
-    return mev.Handle(num_envs=E, num_agents=N, lidar_rays=rays, obs_dim=127, use_team_reward=int(use_team),
-                      respawn_enabled=int(respawn), max_steps=max_steps, traffic_flow=int(traffic),
-                      traffic_density=density, max_npcs=max_npcs, seed=seed, device=0)
-
-
-def _start(h, meta, traffic=False):
-    """Routes, reset, and the oracles of a handle's envs in the same state."""
-    routes, ids = RR.ego_routes(h.route_id, h.E, h.N)
-    h.set_ego_routes(routes)
-    if traffic:
-        h.set_traffic_routes(ids)
-    h.reset()
-    oracles = []
-    for e in range(h.E):
-        o = R.make_oracle(meta)
-        if traffic:
-            o.set_traffic_routes(ids)
-        o.reset([int(r) for r in routes[e]])
-        oracles.append(o)
-    return RR.RepeatRef(oracles, routes)
-
-
-def _scenario(mev, kernel, E, N, rays, repeat, calls, seed, bias, traffic=False, max_npcs=32, dims=False, **cfg):
-    meta = RR.meta(N, rays, traffic=traffic, **cfg)
-    h = _handle(mev, E, N, rays, traffic=traffic, max_npcs=max_npcs, **cfg)
-    use_step_kernel(mev, h, kernel)
-    ref = _start(h, meta, traffic)
-    if dims:  # per-car sizes, the same on both sides (an auto-reset gives new cars of 54 x 24 again)
-        drng = np.random.default_rng(40)
-        ego = np.stack([drng.uniform(40, 70, (E, N)), drng.uniform(18, 30, (E, N))], -1).astype(np.float32)
-        h.set_car_dims(ego, None)
-        for e, o in enumerate(ref.oracles):
-            egos, npcs, sc = o.get_state()
-            egos["len"], egos["wid"] = ego[e, :, 0], ego[e, :, 1]
-            o.set_state(egos, npcs, sc)
-    rng = np.random.default_rng(seed)
-    for c in range(calls):
-        a, sp = RR.draw(rng, E, N, bias, repeat, traffic)
-        out = h.step_repeat(a, repeat, DT, spawn_route=sp, auto_reset=True)
-        ws = ref.step(a, DT, repeat, sp)
-        st = h.get_state()
-        cd = h.car_dims() if dims else None
-        for e in range(E):
-            RR.check_window(f"call {c} env {e}", out, e, ws[e])
-            R.check_state(f"call {c} env {e}", st, e, ref.oracles[e], cd)
-        if traffic:
-            ref.peak_npcs = max(ref.peak_npcs, max(len(o.get_state()[1]) for o in ref.oracles))
-    h.close()
-    ref.close()
-    return ref
+def _scenario(mev, kernel, repeat, **kw):
+    return RR.scenario(mev, n=repeat, plan=False, prepare=lambda h: use_step_kernel(mev, h, kernel), **kw)
 
 
 @pytest.mark.parametrize("kernel", STEP_KERNELS)
@@ -200,14 +148,14 @@ def test_interplay_with_server_snapshot_and_errors(mev):
     def plain(tag):
         a, _ = RR.draw(rng, E, N, 0.6)
         out = h.step(a, DT, auto_reset=True)
-        ws = ref.step(a, DT, 1)
+        ws = ref.step(*RR.held(a, DT, 1))
         for e in range(E):
             R.check_step(f"{tag} env {e}", out, e, ws[e])
 
     def window(tag):
         a, _ = RR.draw(rng, E, N, 0.6)
         out = h.step_repeat(a, n, DT, auto_reset=True)
-        ws = ref.step(a, DT, n)
+        ws = ref.step(*RR.held(a, DT, n))
         for e in range(E):
             RR.check_window(f"{tag} env {e}", out, e, ws[e])
 
@@ -220,7 +168,7 @@ def test_interplay_with_server_snapshot_and_errors(mev):
     snap = h.snapshot()
     a, _ = RR.draw(rng, E, N, 0.6)
     o1 = {k: v.copy() for k, v in h.step_repeat(a, n, DT, auto_reset=True).items()}
-    ws = ref.step(a, DT, n)
+    ws = ref.step(*RR.held(a, DT, n))
     for e in range(E):
         RR.check_window(f"repeat after snapshot env {e}", o1, e, ws[e])
     g1 = {k: v.copy() for k, v in h.get_outputs().items()}
@@ -260,7 +208,7 @@ def _vec_layer(mev, backend):
             obs, rew, term, trunc = (x.cpu().numpy() for x in (obs, rew, term, trunc))
             info = {k: x.cpu().numpy() for k, x in info.items()}
         out = dict(obs=obs, reward=rew, terminated=term, truncated=trunc, **info)
-        ws = ref.step(a, DT, n)
+        ws = ref.step(*RR.held(a, DT, n))
         for e in range(E):
             RR.check_window(f"{backend} call {c} env {e}", out, e, ws[e])
     assert ref.early_stops >= 4  # (max_steps 10, windows of 3: the fourth window of an episode stops at 1)
@@ -305,7 +253,7 @@ def test_drop_in_env_step_repeat(mev):
         a, _ = RR.draw(rng, E, N, 0.6)
         for e, (d, o) in enumerate(zip(envs, oracles)):
             obs, rew, term, trunc, info = d.step(a[e], DT, repeat=n)
-            w = RR.repeat_step(o, a[e], DT, n)
+            w = RR.window_step(o, *RR.held(a[e], DT, n))
             tag = f"call {c} env {e}"
             assert G.bits_equal(np.asarray(obs, np.float32), w["obs"]), tag
             assert G.bits_equal(np.asarray(rew, np.float32), w["rew"]), tag

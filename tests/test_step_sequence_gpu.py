@@ -1,6 +1,6 @@
 """Plan rollouts (mev_step_sequence, include/marlenv.h) against the oracle: one call that runs a
 different action, dt and spawn decision per sub-step and casts the LiDAR once must equal the
-reference's step looped over the plan (tests/sequence_ref.py) -- every output, the sub-step
+reference's step looped over the plan (tests/window_ref.py) -- every output, the sub-step
 count, every per-step row and the full state after every call, bit for bit per env.  Each
 scenario asserts on the oracle side that it reached the cases it is about (dones inside a plan,
 plans stopped early, every crash status), so it cannot pass by covering nothing.  The actions
@@ -11,67 +11,16 @@ import pytest
 
 import golden_replay as G
 import oracle_replay as R
-import repeat_ref as RR
-import sequence_ref as SR
+import window_ref as RR
+from window_ref import DT, OUT_KEYS, handle as _handle, start as _start
 
 pytestmark = pytest.mark.gpu
 
-DT = SR.DT
-OUT_KEYS = ("obs", "reward", "done", "status", "terminated", "truncated", "agents_alive", "step")
 SEQ_KEYS = ("reward_seq", "done_seq", "status_seq")
 
 
-def _handle(mev, E, N, rays, use_team=False, respawn=True, max_steps=2000, traffic=False, density=0.5, max_npcs=32,
-            seed=7):
-    return mev.Handle(num_envs=E, num_agents=N, lidar_rays=rays, obs_dim=127, use_team_reward=int(use_team),
-                      respawn_enabled=int(respawn), max_steps=max_steps, traffic_flow=int(traffic),
-                      traffic_density=density, max_npcs=max_npcs, seed=seed, device=0)
-
-
-def _start(h, meta, traffic=False):
-    """Routes, reset, and the oracles of a handle's envs in the same state."""
-    routes, ids = RR.ego_routes(h.route_id, h.E, h.N)
-    h.set_ego_routes(routes)
-    if traffic:
-        h.set_traffic_routes(ids)
-    h.reset()
-    oracles = []
-    for e in range(h.E):
-        o = R.make_oracle(meta)
-        if traffic:
-            o.set_traffic_routes(ids)
-        o.reset([int(r) for r in routes[e]])
-        oracles.append(o)
-    return SR.SequenceRef(oracles, routes)
-
-
-def _scenario(mev, E, N, rays, T, calls, seed, bias, traffic=False, max_npcs=32, dims=False, **cfg):
-    meta = RR.meta(N, rays, traffic=traffic, **cfg)
-    h = _handle(mev, E, N, rays, traffic=traffic, max_npcs=max_npcs, **cfg)
-    ref = _start(h, meta, traffic)
-    if dims:  # per-car sizes, the same on both sides (an auto-reset gives new cars of 54 x 24 again)
-        drng = np.random.default_rng(40)
-        ego = np.stack([drng.uniform(40, 70, (E, N)), drng.uniform(18, 30, (E, N))], -1).astype(np.float32)
-        h.set_car_dims(ego, None)
-        for e, o in enumerate(ref.oracles):
-            egos, npcs, sc = o.get_state()
-            egos["len"], egos["wid"] = ego[e, :, 0], ego[e, :, 1]
-            o.set_state(egos, npcs, sc)
-    rng = np.random.default_rng(seed)
-    for c in range(calls):
-        A, dts, sp = SR.draw(rng, E, N, T, bias, traffic)
-        out = h.step_sequence(A, dts, spawn_route=sp, auto_reset=True)
-        ws = ref.step(A, dts, sp)
-        st = h.get_state()
-        cd = h.car_dims() if dims else None
-        for e in range(E):
-            SR.check_plan(f"call {c} env {e}", out, e, ws[e], T)
-            R.check_state(f"call {c} env {e}", st, e, ref.oracles[e], cd)
-        if traffic:
-            ref.peak_npcs = max(ref.peak_npcs, max(len(o.get_state()[1]) for o in ref.oracles))
-    h.close()
-    ref.close()
-    return ref
+def _scenario(mev, T, **kw):
+    return RR.scenario(mev, n=T, plan=True, **kw)
 
 
 def test_respawn_on_team_reward(mev):
@@ -194,7 +143,7 @@ def test_philox_and_per_step_dt_equal_single_steps(mev):
     A_h, B_h = hs
     rng = np.random.default_rng(6)
     for c in range(6):
-        A, dts, _ = SR.draw(rng, E, N, T, 0.5)
+        A, dts, _ = RR.draw_plan(rng, E, N, T, 0.5)
         oa = A_h.step_sequence(A, dts, auto_reset=True)
         acc = any_done = None
         latched = np.zeros((E, N), np.uint8)
@@ -239,11 +188,11 @@ def test_interplay_with_server_snapshot_and_errors(mev):
             R.check_step(f"{tag} env {e}", out, e, ws[e])
 
     def plan(tag):
-        A, dts, _ = SR.draw(rng, E, N, T, 0.6)
+        A, dts, _ = RR.draw_plan(rng, E, N, T, 0.6)
         out = h.step_sequence(A, dts, auto_reset=True)
         ws = ref.step(A, dts)
         for e in range(E):
-            SR.check_plan(f"{tag} env {e}", out, e, ws[e], T)
+            RR.check_window(f"{tag} env {e}", out, e, ws[e], T)
 
     plain("served step")
     assert h.serve_stats()["steps"] == 1 and h.serve_stats()["running"]
@@ -252,11 +201,11 @@ def test_interplay_with_server_snapshot_and_errors(mev):
     plain("step after the plan")
     # snapshot, plan, restore, the same plan again
     snap = h.snapshot()
-    A, dts, _ = SR.draw(rng, E, N, T, 0.6)
+    A, dts, _ = RR.draw_plan(rng, E, N, T, 0.6)
     o1 = {k: v.copy() for k, v in h.step_sequence(A, dts, auto_reset=True).items()}
     ws = ref.step(A, dts)
     for e in range(E):
-        SR.check_plan(f"plan after snapshot env {e}", o1, e, ws[e], T)
+        RR.check_window(f"plan after snapshot env {e}", o1, e, ws[e], T)
     g1 = {k: v.copy() for k, v in h.get_outputs().items()}
     for k in OUT_KEYS:
         assert G.bits_equal(g1[k], o1[k]), k  # (the call's outputs are the handle's last outputs)
@@ -288,6 +237,58 @@ def test_interplay_with_server_snapshot_and_errors(mev):
     ref.close()
 
 
+MIXED = dict(E=5, N=2, rays=16, calls=24, seed=4, cfg=dict(traffic=True, density=5.0, max_steps=9))
+
+
+def _mixed_calls(rng, E, N, calls):
+    """The calls of test_both_calls_on_one_handle, cycling a plan of 3 rows with a dt per row, a
+    frame-skip window of 4, a single step and a plan of 6 rows with one dt: (call, rows or None,
+    A [n][E][N][2], dts [n], sp [n][E]), the host call's arguments of a held window being A[0], dts[0]."""
+    for c in range(calls):
+        T = (3, None, None, 6)[c % 4]
+        if T:
+            A, dts, sp = RR.draw_plan(rng, E, N, T, 0.5, True)
+            if T == 6:
+                dts = [DT] * T
+        else:
+            n = (0, 4, 1, 0)[c % 4]
+            a, sp = RR.draw(rng, E, N, 0.5, n, True)
+            A, dts = RR.held(a, DT, n)
+        yield c, T, A, dts, sp
+
+
+def test_both_calls_on_one_handle(mev):
+    """mev_step_sequence, mev_step_repeat and mev_step in turn on one host-mode traffic handle: the
+    staging buffers of actions, spawn routes, sub-step counts and rows are the state the calls share,
+    so every output, substeps, the rows and the full state are checked after every call.  (On the
+    oracle alone: 30 windows stop early, all at max_steps = 9, and an env holds up to 3 NPCs.)"""
+    E, N, rays, cfg = MIXED["E"], MIXED["N"], MIXED["rays"], MIXED["cfg"]
+    h = _handle(mev, E, N, rays, max_npcs=32, **cfg)
+    ref = _start(h, RR.meta(N, rays, **cfg), traffic=True)
+    for c, T, A, dts, sp in _mixed_calls(np.random.default_rng(MIXED["seed"]), E, N, MIXED["calls"]):
+        n = len(A)
+        if T:
+            out = h.step_sequence(A, dts if T == 3 else DT, spawn_route=sp, auto_reset=True)
+        elif n > 1:
+            out = h.step_repeat(A[0], n, DT, spawn_route=sp, auto_reset=True)
+        else:
+            out = h.step(A[0], DT, spawn_route=sp[0], auto_reset=True)
+        ws = ref.step(A, dts, sp)
+        st = h.get_state()
+        for e in range(E):
+            tag = f"call {c} ({'plan' if T else 'held'}, {n}) env {e}"
+            if T or n > 1:
+                RR.check_window(tag, out, e, ws[e], T)
+            else:
+                R.check_step(tag, out, e, ws[e])
+            R.check_state(tag, st, e, ref.oracles[e])
+        ref.peak_npcs = max(ref.peak_npcs, max(len(o.get_state()[1]) for o in ref.oracles))
+    print("early stops", ref.early_stops, "peak NPCs", ref.peak_npcs, "resets", ref.resets)
+    assert ref.early_stops >= 5 and ref.peak_npcs >= 2
+    h.close()
+    ref.close()
+
+
 def _vec_layer(mev, backend):
     import pkgload
     pkgload.load()
@@ -298,7 +299,7 @@ def _vec_layer(mev, backend):
     ref = _start(v.handle, meta)
     rng = np.random.default_rng(9)
     for c in range(15):
-        A, dts, _ = SR.draw(rng, E, N, T, 0.6)
+        A, dts, _ = RR.draw_plan(rng, E, N, T, 0.6)
         obs, rew, term, trunc, info = v.step_sequence(A, dt=dts)
         if backend == "torch":
             obs, rew, term, trunc = (x.cpu().numpy() for x in (obs, rew, term, trunc))
@@ -306,7 +307,7 @@ def _vec_layer(mev, backend):
         out = dict(obs=obs, reward=rew, terminated=term, truncated=trunc, **info)
         ws = ref.step(A, dts)
         for e in range(E):
-            SR.check_plan(f"{backend} call {c} env {e}", out, e, ws[e], T)
+            RR.check_window(f"{backend} call {c} env {e}", out, e, ws[e], T)
     assert ref.early_stops >= 4  # (max_steps 10, plans of 3: the fourth plan of an episode stops at 1)
     v.close()
     ref.close()
