@@ -305,6 +305,73 @@ typedef struct {
 } mev_sequence_args;
 int mev_step_sequence(mev_handle* h, const mev_sequence_args* args);
 
+/* Plan evaluation: score C candidate plans from the LIVE batch and leave the handle untouched -- what
+ * a sampling planner (CEM, MPPI, tree search) does every iteration.  Candidate c starts from a private
+ * copy of live env r = roots[c] (ego state, NPC slots and count, step counter, car sizes) and runs
+ * exactly mev_step_sequence's loop without MEV_AUTO_RESET (a root whose last step ended is stepped on
+ * from its stored state, as mev_step does without the flag), with actions[s] = row s - 1 of actions
+ * ([T][C][N][2]) and dt_s = dt_seq ? dt_seq[s - 1] : dt.  C is independent of num_envs; any number of
+ * candidates may share a root.  Everything read of the starting state is env r's, everything written is
+ * indexed by c:
+ *
+ *   g = 1.0f; ret[i] = 0.0f
+ *   for s = 1..T:
+ *       r = IntersectionEnv::step(actions[s], dt_s)          on the copy
+ *       reward_seq[s-1][c][i] = r.rew[i];  done_seq[s-1][c][i] = r.done[i];  status_seq[s-1][c][i] = r.status[i]
+ *       ret[i] = ret[i] + g * r.rew[i];  g = g * gamma       (f32, in this order, no FMA)
+ *       k = s;  if r.terminated or r.truncated: break
+ *   returns[c][i] = ret[i];  substeps[c] = k;  terminated[c], truncated[c] = sub-step k's flags
+ *   rows s >= k of reward_seq / done_seq / status_seq = 0.0f / 0 / 0  (written by the call itself)
+ *
+ * The *_seq rows are defined exactly as for mev_step_sequence (team mix and bonuses included).
+ * spawn_route, if given, is [T][C]: sub-step s takes spawn_route[s-1][c].  Without it the Philox spawner
+ * is keyed by the candidate index c in the env's place, with the handle's counter + (s - 1) and the
+ * probability 1 - expf(-density * dt_s) computed on the host; the handle's counter is NOT advanced.  So
+ * with C == num_envs the call equals mev_restore_map(roots) followed by mev_step_sequence on a handle
+ * with the same counter, bit for bit.  dt_seq is ALWAYS a host pointer, read before the call returns.
+ * The handle is untouched: state and car sizes, last outputs (mev_get_outputs, DLPack), the Philox
+ * counter, the NPC diagnostics and a snapshot's bytes are what they were; the one side effect is that
+ * a resident step server is stopped first, as by every non-step call.
+ * No leaf observation is returned and no LiDAR is cast, on purpose: the LiDAR hand-off tables are
+ * per-env scratch sized by num_envs, and a cast per candidate is the cost this call exists to avoid.  A
+ * planner that wants the leaf observation of the winning plan runs that one plan through
+ * mev_step_sequence.
+ * Errors (MEV_E_INVALID, the handle untouched): null actions or roots, no output pointer at all,
+ * candidates outside 1..MEV_MAX_CANDIDATES, length outside 1..MEV_MAX_REPEAT, any flag other than
+ * MEV_DEVICE_PTRS.  Host pointers: a root outside [0, E) -> MEV_E_RANGE; the arrays are staged in a
+ * per-handle device buffer that grows to the largest call seen, and the call is synchronous.  Device
+ * pointers: such a root makes its candidate a no-op with defined outputs -- all its rows, returns,
+ * substeps and flags zero (the kernel never reads outside the state arrays) -- and the call does not
+ * synchronise.  Launched on the runtime-layout path (any N <= 64, <= 64 NPC slots, per-car sizes, any
+ * beam list); not counted by mev_kernel_timing.
+ * Measured (python tools/bench_evaluate.py -> profiles/evaluate_sweep.json): at 4096 envs x 8 agents
+ * x 64 beams, device pointers, C = 4096 candidates (64 per root), every output: 35.4 us per call at T = 4 against
+ * 154.7 us for mev_restore_map + mev_step_sequence (4.37x), 20.7 against 137.6 us at T = 2 (6.66x), 64.1 against
+ * 189.1 us at T = 8 (2.95x), 124.1 against 260.1 us at T = 16 (2.10x); the pair's closing mev_restore is another
+ * 117.4-118.5 us.  A further sub-step costs 7.4 us (the pair: 8.7).  C = 16384 from the same handle: 122.1 us at
+ * T = 4, 0.0075 us per candidate (0.0086 at C = 4096).  One-ego traffic (4096 x 1 x 64, density 0.5) gains too:
+ * 91.0 against 220.1 us at T = 4 (2.42x), 388.1 against 595.3 us at T = 16 (1.53x).  No measured shape loses. */
+#define MEV_MAX_CANDIDATES (1 << 20)
+typedef struct {
+    const float*   actions;     /* [length][candidates][N][2]: row s = action of sub-step s+1        */
+    const int32_t* roots;       /* [candidates]: the LIVE env each candidate starts from, 0..E-1     */
+    const int32_t* spawn_route; /* optional [length][candidates], as mev_step_sequence's             */
+    int32_t candidates;         /* C, 1..MEV_MAX_CANDIDATES; independent of num_envs                 */
+    int32_t length;             /* T, 1..MEV_MAX_REPEAT                                              */
+    float   dt;                 /* used when dt_seq is NULL                                          */
+    const float* dt_seq;        /* optional [length]; ALWAYS host, read before the call returns      */
+    float   gamma;              /* discount of `returns`                                             */
+    float*   returns;           /* optional [C][N]                                                   */
+    float*   reward_seq;        /* optional [length][C][N]                                           */
+    uint8_t* done_seq;          /* optional [length][C][N]                                           */
+    uint8_t* status_seq;        /* optional [length][C][N]                                           */
+    int32_t* substeps;          /* optional [C]                                                      */
+    uint8_t* terminated;        /* optional [C]: flags of the sub-step the candidate stopped at      */
+    uint8_t* truncated;         /* optional [C]                                                      */
+    uint32_t flags;             /* MEV_DEVICE_PTRS only                                              */
+} mev_evaluate_args;
+int mev_evaluate_plans(mev_handle* h, const mev_evaluate_args* args);
+
 /* Outputs of the last step / reset, from the handle's own device buffers.
  * Lifetime: after a step that wrote caller-owned output buffers (device
  * pointers in mev_step_args), this call, mev_device_outputs and

@@ -50,6 +50,7 @@ EXPORTED = (
     "mev_gather_wait", "mev_output_dlpack", "mev_packed_layout2", "mev_set_gather_format", "mev_lidar_decode_table",
     "mev_unpack_gathered", "mev_add_route", "mev_add_route_n", "mev_set_car_dims", "mev_get_car_dims", "mev_car_dims_active",
     "mev_set_beam_angles", "mev_get_beam_angles", "mev_decode_errors", "mev_step_sequence", "mev_restore_map",
+    "mev_evaluate_plans",
 )
 
 
@@ -88,6 +89,23 @@ class MevSequenceArgs(ctypes.Structure):  # mev_sequence_args
 
 
 _SEQ_KEYS = ("reward_seq", "done_seq", "status_seq")
+
+MEV_MAX_CANDIDATES = 1 << 20
+
+
+class MevEvaluateArgs(ctypes.Structure):  # mev_evaluate_args
+    _fields_ = [("actions", _vp), ("roots", _vp), ("spawn_route", _vp), ("candidates", ctypes.c_int32),
+                ("length", ctypes.c_int32), ("dt", ctypes.c_float), ("dt_seq", ctypes.POINTER(ctypes.c_float)),
+                ("gamma", ctypes.c_float), ("returns", _vp), ("reward_seq", _vp), ("done_seq", _vp),
+                ("status_seq", _vp), ("substeps", _vp), ("terminated", _vp), ("truncated", _vp),
+                ("flags", ctypes.c_uint32)]
+
+
+# outputs of evaluate_plans: (key, dtype, shape of (T, C, N))
+_EVAL_OUTS = (("returns", np.float32, lambda T, C, N: (C, N)), ("reward_seq", np.float32, lambda T, C, N: (T, C, N)),
+              ("done_seq", np.uint8, lambda T, C, N: (T, C, N)), ("status_seq", np.uint8, lambda T, C, N: (T, C, N)),
+              ("substeps", np.int32, lambda T, C, N: (C,)), ("terminated", np.uint8, lambda T, C, N: (C,)),
+              ("truncated", np.uint8, lambda T, C, N: (C,)))
 
 
 # (name, dtype, per) — per: "ego" [E*N], "npc" [E*K], "env" [E]; order == struct mev_state
@@ -153,6 +171,7 @@ def load_library(variant: str = None):
     L.mev_step_repeat.argtypes = [_vp, ctypes.POINTER(MevRepeatArgs)]
     L.mev_step_sequence.argtypes = [_vp, ctypes.POINTER(MevSequenceArgs)]
     L.mev_restore_map.argtypes = [_vp, _vp, _vp, ctypes.c_uint32]
+    L.mev_evaluate_plans.argtypes = [_vp, ctypes.POINTER(MevEvaluateArgs)]
     L.mev_get_outputs.argtypes = [_vp] + [_vp] * 8 + [ctypes.c_uint32]
     L.mev_get_state.argtypes = [_vp, ctypes.POINTER(MevState)]
     L.mev_set_state.argtypes = [_vp, ctypes.POINTER(MevState)]
@@ -574,6 +593,67 @@ class Handle:
             setattr(a, k, _ptr(out.get(k)))
         a.substeps = _ptr(out.get("substeps"))
         _check(self._lib.mev_step_sequence(self._h, ctypes.byref(a)))
+        return out
+
+    def evaluate_plans(self, actions, roots, dt=1.0 / 60.0, gamma: float = 1.0, spawn_route=None,
+                       out: Optional[dict] = None, device: bool = False, candidates: Optional[int] = None,
+                       length: Optional[int] = None, flags: int = 0):
+        """Score candidate plans from the live batch (mev_evaluate_plans); the handle stays as it is.
+        actions [T][C][N][2], roots [C] (the live env each candidate starts from), dt a float or T
+        floats (always host values), spawn_route optional [T][C].  Returns `returns` [C][N] (the
+        discounted f32 return), `reward_seq`, `done_seq`, `status_seq` [T][C][N] (zero after a
+        candidate stopped), `substeps`, `terminated`, `truncated` [C].  No observation, no LiDAR.
+        device=True: every array is a device tensor/pointer, only the outputs present in `out` are
+        written, and C, T are roots.shape[0], actions.shape[0] (or `candidates` / `length` for raw
+        pointers).  flags: further bits for the call's flags word (the library refuses them)."""
+        N = self.N
+        if device:
+            if length is None:
+                length = getattr(actions, "shape", (None,))[0]
+            if candidates is None:
+                candidates = getattr(roots, "shape", (None,))[0]
+            if length is None or candidates is None:
+                raise ValueError("evaluate_plans needs actions [T][C][N][2] and roots [C] (or length=T, candidates=C)")
+            T, C = int(length), int(candidates)
+            out = out if out is not None else {}
+        else:
+            actions = np.ascontiguousarray(actions, np.float32)
+            roots = np.ascontiguousarray(roots, np.int32)
+            if roots.ndim != 1:
+                raise ValueError(f"roots must be [C], got {roots.shape}")
+            C = int(roots.shape[0]) if candidates is None else int(candidates)
+            T = (int(actions.shape[0]) if actions.ndim else 0) if length is None else int(length)
+            if roots.shape != (C,):
+                raise ValueError(f"roots must be [{C}], got {roots.shape}")
+            if actions.shape != (T, C, N, 2):
+                raise ValueError(f"actions must be [{T}][{C}][{N}][2], got {actions.shape}")
+            if spawn_route is not None:
+                spawn_route = np.ascontiguousarray(np.asarray(spawn_route, np.int32))
+                if spawn_route.shape != (T, C):
+                    raise ValueError(f"spawn_route must be [{T}][{C}], got {spawn_route.shape}")
+            out = out if out is not None else {}
+            if not out:
+                for k, dtype, shape in _EVAL_OUTS:
+                    out[k] = np.zeros(shape(T, C, N), dtype)
+            for k, dtype, shape in _EVAL_OUTS:
+                if out.get(k) is not None and (out[k].shape != shape(T, C, N) or out[k].dtype != dtype):
+                    raise ValueError(f"{k} must be {np.dtype(dtype).name} {list(shape(T, C, N))}, got {out[k].shape}")
+        a = MevEvaluateArgs()
+        a.actions, a.roots, a.spawn_route = _ptr(actions), _ptr(roots), _ptr(spawn_route)
+        a.candidates, a.length, a.gamma = C, T, float(gamma)
+        dts = None
+        if np.ndim(dt) == 0:
+            a.dt = float(dt)
+        else:
+            dts = np.ascontiguousarray(dt, np.float32).reshape(-1)
+            if dts.size != T:
+                raise ValueError(f"dt must be a float or {T} floats, got {dts.size}")
+            a.dt = float(dts[0]) if T else 0.0
+            a.dt_seq = dts.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
+        for k, _, _ in _EVAL_OUTS:
+            setattr(a, k, _ptr(out.get(k)))
+        a.flags = (MEV_DEVICE_PTRS if device else 0) | int(flags)
+        _check(self._lib.mev_evaluate_plans(self._h, ctypes.byref(a)))
         return out
 
     # -- multi-GPU gather (mev_comm_*) -------------------------------------

@@ -105,6 +105,8 @@ struct mev_handle {
     uint8_t* d_done_seq = nullptr;   // [MEV_MAX_REPEAT][E][N]
     uint8_t* d_status_seq = nullptr; // [MEV_MAX_REPEAT][E][N]
     int32_t* d_env_map = nullptr;    // [E] env map of a host-mode mev_restore_map
+    uint8_t* d_eval = nullptr;       // every array of a host-mode mev_evaluate_plans, grown to the largest call seen
+    size_t eval_cap = 0;
     uint8_t* d_mask = nullptr;
     float* d_paths = nullptr;
     int32_t* d_rlen = nullptr;  // [route_cap] each path's own length (RouteTab::len)
@@ -250,6 +252,7 @@ struct mev_handle {
         if (serve_stream) (void)hipStreamDestroy(serve_stream);
         if (gs_pin) (void)hipHostFree(gs_pin);
         if (d_snap_stage) (void)hipFree(d_snap_stage);
+        if (d_eval) (void)hipFree(d_eval);
         for (void* p : allocs) (void)hipFree(p);
         if (own_stream) (void)hipStreamDestroy(own_stream);
     }
@@ -1579,6 +1582,104 @@ int mev_step_sequence(mev_handle* h, const mev_sequence_args* sa) {
     if (a->flags & MEV_GATHER_TO_ROOT) return fail(MEV_E_INVALID, "mev_step_sequence does not gather (MEV_GATHER_TO_ROOT)");
     return step_window(h, a, WindowArgs{sa->length, true, sa->dt_seq, sa->substeps, sa->reward_seq, sa->done_seq,
                                     sa->status_seq});
+}
+
+// mev_evaluate_plans (include/marlenv.h): the plan rollout's loop over C candidates that start from
+// copies of live envs, nothing of the handle written.  Host mode stages every array in one device
+// block of the handle that grows to the largest call seen.
+int mev_evaluate_plans(mev_handle* h, const mev_evaluate_args* ea) {
+    if (!h || !ea) return fail(MEV_E_INVALID, "null argument");
+    if (!ea->actions || !ea->roots) return fail(MEV_E_INVALID, "actions and roots required");
+    if (ea->candidates < 1 || ea->candidates > MEV_MAX_CANDIDATES)
+        return fail(MEV_E_INVALID, "candidates must be in 1.." + std::to_string(MEV_MAX_CANDIDATES));
+    if (ea->length < 1 || ea->length > MEV_MAX_REPEAT)
+        return fail(MEV_E_INVALID, "length must be in 1.." + std::to_string(MEV_MAX_REPEAT));
+    if (ea->flags & ~uint32_t(MEV_DEVICE_PTRS)) return fail(MEV_E_INVALID, "mev_evaluate_plans takes MEV_DEVICE_PTRS only");
+    if (!ea->returns && !ea->reward_seq && !ea->done_seq && !ea->status_seq && !ea->substeps && !ea->terminated &&
+        !ea->truncated)
+        return fail(MEV_E_INVALID, "mev_evaluate_plans needs at least one output");
+    const bool dev = (ea->flags & MEV_DEVICE_PTRS) != 0;
+    const size_t C = size_t(ea->candidates), T = size_t(ea->length), N = size_t(h->cfg.num_agents), CN = C * N;
+    if (!dev)
+        for (size_t c = 0; c < C; ++c)
+            if (ea->roots[c] < 0 || ea->roots[c] >= h->cfg.num_envs)
+                return fail(MEV_E_RANGE, "roots[" + std::to_string(c) + "] = " + std::to_string(ea->roots[c]) +
+                                             " is outside [0, " + std::to_string(h->cfg.num_envs) + ")");
+    HIP_TRY(hipSetDevice(h->cfg.device));
+    if (int r = serve_stop(h)) return r;  // (the server holds the stream)
+    mev::SeqRows rows{};
+    for (size_t s = 0; s < T; ++s) {  // read from the caller's memory now; by value with the kernel's arguments
+        rows.dt[s] = ea->dt_seq ? ea->dt_seq[s] : ea->dt;
+        rows.spawn_prob[s] = spawn_prob(h, rows.dt[s]);
+    }
+    mev::StepInputs in{};
+    in.dt = rows.dt[0];
+    in.spawn_prob = rows.spawn_prob[0];
+    in.rng_counter = h->rng_counter;  // sub-step s: + s; the handle's counter stays
+    mev::EvalOutputs eo{ea->gamma, ea->returns, ea->substeps, ea->terminated, ea->truncated};
+    const int32_t* d_roots = ea->roots;
+    if (dev) {
+        in.actions = ea->actions;
+        in.spawn_route = ea->spawn_route;
+        rows.reward = ea->reward_seq;
+        rows.done = ea->done_seq;
+        rows.status = ea->status_seq;
+    } else {
+        // the staging block: every array of this call, each at a 256-byte boundary
+        size_t off = 0;
+        auto take = [&off](bool wanted, size_t bytes) {
+            const size_t at = off;
+            if (wanted) off += (bytes + 255) & ~size_t(255);
+            return at;
+        };
+        const size_t o_act = take(true, T * CN * 2 * sizeof(float)), o_roots = take(true, C * sizeof(int32_t));
+        const size_t o_spawn = take(ea->spawn_route != nullptr, T * C * sizeof(int32_t));
+        const size_t o_ret = take(ea->returns != nullptr, CN * sizeof(float));
+        const size_t o_rew = take(ea->reward_seq != nullptr, T * CN * sizeof(float));
+        const size_t o_done = take(ea->done_seq != nullptr, T * CN), o_status = take(ea->status_seq != nullptr, T * CN);
+        const size_t o_sub = take(ea->substeps != nullptr, C * sizeof(int32_t));
+        const size_t o_term = take(ea->terminated != nullptr, C), o_trunc = take(ea->truncated != nullptr, C);
+        if (off > h->eval_cap) {
+            HIP_TRY(hipStreamSynchronize(h->stream));
+            if (h->d_eval) (void)hipFree(h->d_eval);
+            h->d_eval = nullptr;
+            h->eval_cap = 0;
+            const hipError_t err = hipMalloc(reinterpret_cast<void**>(&h->d_eval), off);
+            if (err != hipSuccess) return fail(MEV_E_NOMEM, std::string("device allocation failed: ") + hipGetErrorString(err));
+            h->eval_cap = off;
+        }
+        uint8_t* b = h->d_eval;
+        HIP_TRY(hipMemcpyAsync(b + o_act, ea->actions, T * CN * 2 * sizeof(float), hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(hipMemcpyAsync(b + o_roots, ea->roots, C * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+        in.actions = reinterpret_cast<const float*>(b + o_act);
+        d_roots = reinterpret_cast<const int32_t*>(b + o_roots);
+        if (ea->spawn_route) {
+            HIP_TRY(hipMemcpyAsync(b + o_spawn, ea->spawn_route, T * C * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+            in.spawn_route = reinterpret_cast<const int32_t*>(b + o_spawn);
+        }
+        if (ea->returns) eo.returns = reinterpret_cast<float*>(b + o_ret);
+        if (ea->reward_seq) rows.reward = reinterpret_cast<float*>(b + o_rew);
+        if (ea->done_seq) rows.done = b + o_done;
+        if (ea->status_seq) rows.status = b + o_status;
+        if (ea->substeps) eo.substeps = reinterpret_cast<int32_t*>(b + o_sub);
+        if (ea->terminated) eo.terminated = b + o_term;
+        if (ea->truncated) eo.truncated = b + o_trunc;
+    }
+    HIP_TRY(mev::launch_evaluate(h->sp, in, int(C), d_roots, rows, int(T), eo, h->stream));
+    if (!dev) {
+        auto back = [h](void* dst, const void* src, size_t bytes) {
+            return dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream) : hipSuccess;
+        };
+        HIP_TRY(back(ea->returns, eo.returns, CN * sizeof(float)));
+        HIP_TRY(back(ea->reward_seq, rows.reward, T * CN * sizeof(float)));
+        HIP_TRY(back(ea->done_seq, rows.done, T * CN));
+        HIP_TRY(back(ea->status_seq, rows.status, T * CN));
+        HIP_TRY(back(ea->substeps, eo.substeps, C * sizeof(int32_t)));
+        HIP_TRY(back(ea->terminated, eo.terminated, C));
+        HIP_TRY(back(ea->truncated, eo.truncated, C));
+        HIP_TRY(hipStreamSynchronize(h->stream));
+    }
+    return MEV_OK;
 }
 
 static int sync_internal(mev_handle* h);  // below, with mev_device_outputs

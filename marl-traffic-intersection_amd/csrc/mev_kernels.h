@@ -232,6 +232,22 @@ struct SeqRows {
 };
 hipError_t launch_step_window(const SimParams& p, const StepInputs& in, const Outputs& out, int n,
                               const SeqRows* rows, int32_t* substeps, hipStream_t s);
+// Plan evaluation (mev_evaluate_plans): C candidates, candidate c rolled through a plan of n
+// sub-steps from a private copy of the live env roots[c] (k_cars_repeat<TRAFFIC, true, EVAL =
+// true>), and nothing of p's state, outputs or diagnostics written: one launch of C single-wave
+// workgroups, no k_lidar.  in.actions is [n][C][N][2], in.spawn_route, if given, [n][C]; the
+// Philox spawner is keyed by c with in.rng_counter + s; in.auto_reset is not read (never a
+// reset).  rows as for launch_step_window with [n][C][N] arrays.  A root outside [0, p.E) makes
+// its candidate's outputs zero.  Every shape k_cars runs.
+struct EvalOutputs {
+    float gamma;          // discount of returns
+    float* returns;       // [C][N] (each nullable)
+    int32_t* substeps;    // [C]
+    uint8_t* terminated;  // [C] flags of the sub-step the candidate stopped at
+    uint8_t* truncated;   // [C]
+};
+hipError_t launch_evaluate(const SimParams& p, const StepInputs& in, int C, const int32_t* roots, const SeqRows& rows,
+                           int n, const EvalOutputs& outs, hipStream_t s);
 hipError_t launch_reset(const SimParams& p, const uint8_t* env_mask, const Outputs& out, hipStream_t s,
                         uint64_t rng_counter);
 // recompute the observation rows from the current state with LiDAR = max (after set_state)

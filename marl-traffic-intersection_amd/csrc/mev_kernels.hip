@@ -574,7 +574,10 @@ __device__ __forceinline__ void npc_writeback(const SimParams& p, int e, const N
 
 // The NPC state goes back to HBM at the end of the phase (measured against a
 // write-back at the end of k_step: config 4 33.1 vs 33.4 us, r3_ab_deferwb.txt).
-template <class NL>
+// EVAL (mev_evaluate_plans): e is the candidate's index, in the env's place for the spawn decision
+// (spawn_route[e], the Philox key); nothing is stored to the handle's memory -- neither the
+// survivors (the next sub-step reads them from nl) nor the diagnostics counters.
+template <class NL, bool EVAL = false>
 __device__ int npc_phase(const SimParams& p, const StepInputs& in, int e, int cnt, NL& nl, int lane,
                           const float* ego_x, const float* ego_y, const NpcRegs& nr) {
     const int K = p.K;
@@ -647,7 +650,7 @@ __device__ int npc_phase(const SimParams& p, const StepInputs& in, int e, int cn
                     if constexpr (NL::kDims) { nl.len[cnt] = CAR_LENGTH; nl.wid[cnt] = CAR_WIDTH; }  // a new Car
                 }
                 ++cnt;
-            } else if (lane == 0) {
+            } else if (!EVAL && lane == 0) {
                 atomicAdd(p.overflow, 1ull);
             }
         }
@@ -1027,7 +1030,7 @@ __device__ int npc_phase(const SimParams& p, const StepInputs& in, int e, int cn
         if (diff) {
             const int ks = __builtin_ctzll(diff);
             move_all(nl.thr_b, 1ull << ks);  // its inputs were the sequential ones
-            if (lane == 0) atomicAdd(p.overflow + 1, (unsigned long long)(cnt - ks - 1));  // diagnostics
+            if (!EVAL && lane == 0) atomicAdd(p.overflow + 1, (unsigned long long)(cnt - ks - 1));  // diagnostics
             done_m = alive_k & ((ks == 63 ? ~0ull : ((2ull << ks) - 1ull)));
             kseq = ks + 1;
         }
@@ -1151,14 +1154,14 @@ __device__ int npc_phase(const SimParams& p, const StepInputs& in, int e, int cn
         wave_lds_sync();
     }
     // store back + corners of the survivors (for ego-NPC SAT)
-    npc_writeback(p, e, nl, newcnt, lane);
+    if constexpr (!EVAL) npc_writeback(p, e, nl, newcnt, lane);
     if (lane < newcnt)
         car_corners_d(nl.x[lane], nl.y[lane], nl.c[lane], nl.s[lane], npc_len(nl, lane, dims),
                       npc_wid(nl, lane, dims), nl.cx[lane], nl.cy[lane]);
     wave_lds_sync();
 #ifdef MEV_STAMPS_N
     NT(7);  // collisions, erase, store
-    if (lane == 0)
+    if (!EVAL && lane == 0)
         for (int q = 0; q < 8; ++q) p.debug[e * 8 + q] = nt_acc[q];
 #endif
     return newcnt;
@@ -1510,6 +1513,7 @@ struct CarsCtx {
     bool do_reset;  // the env was auto-reset at the start of this step
     int ncnt;       // NPCs alive after the traffic phase
     bool ended;     // (set by cars_post, PK == 1) terminated or truncated this step
+    bool term, trunc;  // (set by cars_post, EVAL) the two flags themselves
 };
 
 // What a frame-skip call (k_cars_repeat) keeps in the wave from one sub-step to the next
@@ -1525,6 +1529,9 @@ struct RepCarry {
     float rew;
     uint8_t any_done, latched;
     int32_t* substeps;  // [E] sub-steps executed (nullable)
+    // EVAL (mev_evaluate_plans): the discount of the next sub-step and the discounted return so
+    // far, lane = agent; gamma is set from the kernel's arguments in every sub-step
+    float g, ret, gamma;
 };
 
 // A plan-rollout call (k_cars_repeat<TRAFFIC, SEQ = true>) carries nothing more in registers:
@@ -1737,13 +1744,19 @@ __device__ __forceinline__ void ego_phase1(const SimParams& p, const StepInputs&
 // NPCs are the survivors in nl, the counters come in rc; the obstacle table and candidate
 // masks stay in LDS (cars_post publishes them in the sub-step the env stops at).
 // WC: the reference's world at compile time (StepWorld / StepRows; k_step's rows with it).
+// EVAL (mev_evaluate_plans, k_cars_repeat<TRAFFIC, true, true>): e is a candidate's index, not an
+// env's.  The first sub-step loads the state of the live env src_e (the env's counters, every ego
+// field, the car sizes, the NPC slots) and never resets it; the actions, the spawn decision and
+// everything written are the candidate's (index e).  No LiDAR follows, so the part ends after the
+// respawns: no obstacle table, no candidate masks.
 template <bool TRAFFIC, bool FUSED, class NL, int PK = 1, bool EARLY = false, bool ESPLIT = false, bool DIMS = false,
-          bool TSC = false, int NC = 0, bool REP = false, bool WC = false, bool SEQ = false>
+          bool TSC = false, int NC = 0, bool REP = false, bool WC = false, bool SEQ = false, bool EVAL = false>
 __device__ __forceinline__ CarsCtx cars_pre(const SimParams& p, const StepInputs& in, const Outputs& out, const int e,
                                             const CarsLDS& el, NL* nl, int npc_cls = kDealClasses - 1,
-                                            const RepCarry* rc = nullptr) {
+                                            const RepCarry* rc = nullptr, const int src_e = 0) {
     static_assert(!REP || (!FUSED && PK == 1 && !EARLY && !ESPLIT && !TSC && NC == 0), "frame skip: k_cars' layout");
     static_assert(!SEQ || REP, "plan rollout: the frame-skip loop");
+    static_assert(!EVAL || SEQ, "plan evaluation: the plan rollout's loop");
     static_assert(!ESPLIT || FUSED, "early split: k_step");
     static_assert(PK == 1 || (FUSED && !TRAFFIC), "several envs per wave: k_step without traffic");
     static_assert(!DIMS || (PK == 1 && !EARLY && !ESPLIT), "per-car sizes: the runtime-layout kernels");
@@ -1796,22 +1809,26 @@ __device__ __forceinline__ CarsCtx cars_pre(const SimParams& p, const StepInputs
     static_assert(!EARLY || (FUSED && !TRAFFIC), "LDS path windows: k_step without traffic");
     constexpr bool early = EARLY;
     if (!cont) {
-        const uint8_t pending_b = ldu(gmem(p.pending_reset), (uint32_t)ee);
-        const int step_prev = ldu(gmem(p.step_count), (uint32_t)ee);
-        const int npcs_prev = TRAFFIC ? gmem(p.npc.count)[e] : 0;
+        // where the state comes from: the lane's own env and agent, or (EVAL) the candidate's root
+        const int se = EVAL ? src_e : e;
+        const uint32_t use = (uint32_t)(EVAL ? src_e : ee);
+        const uint32_t us = EVAL ? (uint32_t)(src_e * NE + il) : ug;
+        const uint8_t pending_b = ldu(gmem(p.pending_reset), use);  // (EVAL: read, then ignored)
+        const int step_prev = ldu(gmem(p.step_count), use);
+        const int npcs_prev = TRAFFIC ? gmem(p.npc.count)[se] : 0;
         const float a0 = ldu(gmem(in.actions), 2 * ug), a1 = ldu(gmem(in.actions), 2 * ug + 1);
-        const int route_l = ldu(egoi(p, EF_ROUTE), ug);
-        const float x0 = ldu(egof(p, EF_X), ug), y0 = ldu(egof(p, EF_Y), ug), v0 = ldu(egof(p, EF_V), ug);
-        const float h0 = ldu(egof(p, EF_H), ug), acc0 = ldu(egof(p, EF_ACC), ug), steer0 = ldu(egof(p, EF_STEER), ug);
-        const float pd0 = ldu(egof(p, EF_PREV_DIST), ug), pa00 = ldu(egof(p, EF_PA0), ug), pa10 = ldu(egof(p, EF_PA1), ug);
-        const float sx0 = ldu(egof(p, EF_SX), ug), sy0 = ldu(egof(p, EF_SY), ug), sv0 = ldu(egof(p, EF_SV), ug);
-        const float sh0 = ldu(egof(p, EF_SH), ug);
-        const int pidx_l = ldu(egoi(p, EF_PIDX), ug), intent_l = ldu(egoi(p, EF_INTENT), ug);
-        const uint8_t alive_l = ldu(gmem(p.ego.alive), ug);
+        const int route_l = ldu(egoi(p, EF_ROUTE), us);
+        const float x0 = ldu(egof(p, EF_X), us), y0 = ldu(egof(p, EF_Y), us), v0 = ldu(egof(p, EF_V), us);
+        const float h0 = ldu(egof(p, EF_H), us), acc0 = ldu(egof(p, EF_ACC), us), steer0 = ldu(egof(p, EF_STEER), us);
+        const float pd0 = ldu(egof(p, EF_PREV_DIST), us), pa00 = ldu(egof(p, EF_PA0), us), pa10 = ldu(egof(p, EF_PA1), us);
+        const float sx0 = ldu(egof(p, EF_SX), us), sy0 = ldu(egof(p, EF_SY), us), sv0 = ldu(egof(p, EF_SV), us);
+        const float sh0 = ldu(egof(p, EF_SH), us);
+        const int pidx_l = ldu(egoi(p, EF_PIDX), us), intent_l = ldu(egoi(p, EF_INTENT), us);
+        const uint8_t alive_l = ldu(gmem(p.ego.alive), us);
         float len_l = CAR_LENGTH, wid_l = CAR_WIDTH;
         if constexpr (DIMS) {
-            len_l = ldu(gmem(p.ego_dim), 2 * ug);
-            wid_l = ldu(gmem(p.ego_dim), 2 * ug + 1);
+            len_l = ldu(gmem(p.ego_dim), 2 * us);
+            wid_l = ldu(gmem(p.ego_dim), 2 * us + 1);
         }
         // phase 1's first pass in group layout (lane (grp, sub): agent grp), without
         // traffic (there the NPC phase runs in between, and the window registers would
@@ -1847,14 +1864,14 @@ __device__ __forceinline__ CarsCtx cars_pre(const SimParams& p, const StepInputs
         }
         // in flight with the ego loads; only the slots the env's deal class says are filled (the
         // class is its NPC count after the previous step; the last class and no deal: every slot)
-        if constexpr (TRAFFIC) nreg = npc_load<DIMS>(p, e, tid, npc_cls < kDealClasses - 1 ? npc_cls : p.K);
+        if constexpr (TRAFFIC) nreg = npc_load<DIMS>(p, se, tid, npc_cls < kDealClasses - 1 ? npc_cls : p.K);
         // every load above is issued before any of their values is used (a use scheduled
         // between them would put a wait for the first loads in front of the rest)
         __builtin_amdgcn_sched_barrier(0);
         static_assert(!TSC || (TRAFFIC && ESPLIT && PK == 1 && !DIMS), "TSC: the traffic early split's car waves");
         const bool pending = pending_b != 0;
         gpend = gpend_b != 0;
-        do_reset = in.auto_reset && pending;
+        do_reset = !EVAL && in.auto_reset && pending;  // (EVAL: stepped on from the stored state)
         const int prev_step = do_reset ? 0 : step_prev;
         prev_npcs = TRAFFIC ? (do_reset ? 0 : npcs_prev) : 0;
         if (TSC && tid == 0) {  // the start-of-step position (the spawn after an auto-reset) for the NPC spawn test
@@ -1975,7 +1992,7 @@ __device__ __forceinline__ CarsCtx cars_pre(const SimParams& p, const StepInputs
                          reinterpret_cast<const float*>(el.envw + 1), nreg);
         __syncthreads();  // barrier H: the LiDAR wave has run this env's ego through phase 1
     } else if constexpr (TRAFFIC) {
-        ncnt = npc_phase(p, in, e, prev_npcs, *nl, tid, el.x, el.y, nreg);
+        ncnt = npc_phase<NL, EVAL>(p, in, e, prev_npcs, *nl, tid, el.x, el.y, nreg);
     }
 
     if (TRAFFIC && FUSED) {
@@ -2097,6 +2114,8 @@ __device__ __forceinline__ CarsCtx cars_pre(const SimParams& p, const StepInputs
         if (tid == 0) el.envw[6] = (int)(unsigned)m;
     }
     wave_lds_sync();
+    // (no LiDAR casts a candidate: neither its obstacle table nor its candidate masks are built)
+    if constexpr (EVAL) return CarsCtx{step_no, false, ncnt, false};
 
     STAMP(4);
     // ---- LiDAR obstacle table (:374-388): every ego (alive or not), then NPCs,
@@ -2224,12 +2243,17 @@ __device__ __forceinline__ unsigned long long ts_ego_phase(const SimParams& p, c
 // flags, the state, the obstacle table / candidate masks and the observation head.
 // WCP1 > 0: plain observation rows of 31 + WCP1 columns, every one a LiDAR slot, at compile time
 // (StepWorld / StepRows; k_step's rows with the reference's world).
+// EVAL (mev_evaluate_plans): nothing is stored -- the candidate's state is a private copy, the
+// handle's outputs, flags, state, LiDAR hand-off and observation rows stay as they are.  The
+// sub-step's reward goes into the car LDS for the kernel's row stores (as SEQ) and into the
+// discounted return of the carry; the flags go back in cx, and the body ends there.
 template <bool TRAFFIC, bool FUSED, class NL, int PK = 1, bool DIMS = false, int NC = 0, bool REP = false,
-          int WCP1 = 0, bool SEQ = false>
+          int WCP1 = 0, bool SEQ = false, bool EVAL = false>
 __device__ __forceinline__ void cars_post(const SimParams& p, const Outputs& out, const int e, const CarsLDS& el,
                                           const NL* nl, CarsCtx& cx, RepCarry* rc = nullptr) {
     static_assert(!REP || (!FUSED && PK == 1 && NC == 0), "frame skip: k_cars' layout");
     static_assert(!SEQ || REP, "plan rollout: the frame-skip loop");
+    static_assert(!EVAL || SEQ, "plan evaluation: the plan rollout's loop");
     using RW = StepRows<(WCP1 > 0), WCP1>;
     static_assert(WCP1 == 0 || (!TRAFFIC && FUSED && !DIMS), "constant rows: the compile-time layout's head writes");
     const int tid = threadIdx.x & (WAVE - 1);
@@ -2302,6 +2326,14 @@ __device__ __forceinline__ void cars_post(const SimParams& p, const Outputs& out
             // per-step rows after cars_post, where nothing else is live (stored from here, the
             // 128-VGPR instantiation spilled 5 registers to scratch).  Nothing below reads el.rew.
             if (in_env) el.rew[i] = rew_i;
+        }
+        if constexpr (EVAL) {
+            // ret = ret + g * r; g = g * gamma, in sub-step order (f32, no FMA: -ffp-contract=off)
+            rc->ret = rc->ret + rc->g * rew_i;
+            rc->g = rc->g * rc->gamma;
+            cx.term = terminated;
+            cx.trunc = truncated;
+            return;
         }
         if constexpr (REP) {
             // acc = r (first sub-step) or acc + r, in sub-step order; the latest done's status
@@ -2524,43 +2556,82 @@ struct SeqArgs {
     SeqRows rows;
 };
 static_assert(sizeof(SeqArgs) <= 4096, "the kernel argument segment");
+// EVAL (mev_evaluate_plans, a planner's scoring pass): workgroup = candidate c, not env.  The
+// first sub-step loads the state of the live env roots[c] (cars_pre's src_e; candidates of one
+// root read the same lines: L2), the plan rollout's loop runs on that private copy, and nothing
+// is written back: no state, no handle outputs, no LiDAR hand-off, no observation head, no NPC
+// survivors, no diagnostics (cars_pre / cars_post / npc_phase with EVAL).  The rows are the
+// candidates' -- actions [n][C][N][2], spawn_route [n][C], reward / done / status [n][C][N] --
+// and the Philox spawner is keyed by c.  Per agent the carry holds the discount and the
+// discounted return (ret += g * r; g *= gamma, f32 in sub-step order); the sub-step a candidate
+// stops at stores returns[c][i], substeps[c] and the two flags.  A root outside [0, E) makes the
+// candidate a no-op whose every output is zero; the state arrays are never read for it.
+struct EvalOuts {
+    const int32_t* roots;  // [C] the live env each candidate starts from
+    int32_t C;
+    float gamma;
+    float* returns;        // [C][N] (nullable, as the next three)
+    int32_t* substeps;     // [C]
+    uint8_t* term;         // [C]
+    uint8_t* trunc;        // [C]
+};
+struct EvalArgs {
+    SeqArgs s;
+    EvalOuts ev;
+};
+static_assert(sizeof(EvalArgs) <= 4096, "the kernel argument segment");
 // (four waves per SIMD, as k_step: 4096 envs are one round of single-wave workgroups on 256 CUs;
 // with the NPC phase 128 VGPRs would spill to scratch: two)
-template <bool TRAFFIC, bool SEQ = false>
+template <bool TRAFFIC, bool SEQ = false, bool EVAL = false>
 __global__ __launch_bounds__(WAVE, TRAFFIC ? 2 : 4) void k_cars_repeat(
-    typename std::conditional<SEQ, SeqArgs, RepeatArgs>::type args) {
+    typename std::conditional<EVAL, EvalArgs, typename std::conditional<SEQ, SeqArgs, RepeatArgs>::type>::type args) {
+    static_assert(!EVAL || SEQ, "plan evaluation: the plan rollout's loop");
     extern __shared__ __align__(16) unsigned char cars_lds[];
     __shared__ typename std::conditional<TRAFFIC, NpcLDS, char>::type nl_storage;
     NpcLDS* nl = nullptr;
     if constexpr (TRAFFIC) nl = &nl_storage;
     int repeat;
-    if constexpr (SEQ) repeat = args.r.repeat;
+    if constexpr (EVAL) repeat = args.s.r.repeat;
+    else if constexpr (SEQ) repeat = args.r.repeat;
     else repeat = args.repeat;
-    RepCarry rc{0, repeat, 0, 0, false, 0.0f, 0, 0, nullptr};
-    for (int s = 0; s < repeat; ++s) {
+    RepCarry rc{0, repeat, 0, 0, false, 0.0f, 0, 0, nullptr, 1.0f, 0.0f, 1.0f};
+    int src = 0;       // EVAL: the candidate's root (wave-uniform)
+    bool bad = false;  // EVAL: a root outside [0, E): no sub-step runs
+    if constexpr (EVAL) {
+        const int c = xcd_env((int)blockIdx.x, (int)gridDim.x);
+        src = __builtin_amdgcn_readfirstlane(args.ev.roots[c]);
+        bad = (unsigned)src >= (unsigned)args.s.r.p.E;
+    }
+    for (int s = 0; s < (bad ? 0 : repeat); ++s) {
         typedef const __attribute__((address_space(4))) RepeatArgs CArgs;
         CArgs* ka = (CArgs*)__builtin_amdgcn_kernarg_segment_ptr();  // (args: the first and only argument)
         asm volatile("" : "+s"(ka));
         const RepeatArgs& a = *(const RepeatArgs*)ka;
         const SimParams& p = a.p;
-        const int e = a.e_begin + xcd_env((int)blockIdx.x, (int)gridDim.x);
+        const int e = a.e_begin + xcd_env((int)blockIdx.x, (int)gridDim.x);  // (EVAL: the candidate, e_begin = 0)
         const CarsLDS el = carve_cars_lds(cars_lds, p.N, cars_k(p), true);
         StepInputs in = a.in;
-        if (in.spawn_route) in.spawn_route += (size_t)s * p.E;
+        int rowE = p.E;  // envs (EVAL: candidates) per row of the per-step arrays
+        if constexpr (EVAL) {
+            const EvalOuts& ev = reinterpret_cast<const EvalArgs*>(&a)->ev;
+            rowE = ev.C;
+            rc.gamma = ev.gamma;
+        }
+        if (in.spawn_route) in.spawn_route += (size_t)s * rowE;
         in.rng_counter += (uint64_t)s;
         rc.s = s;
         rc.substeps = a.substeps;
         if constexpr (SEQ) {
             const SeqRows& q = reinterpret_cast<const SeqArgs*>(&a)->rows;
-            in.actions += 2 * (size_t)s * ((size_t)p.E * p.N);
+            in.actions += 2 * (size_t)s * ((size_t)rowE * p.N);
             in.dt = q.dt[s];
             in.spawn_prob = q.spawn_prob[s];
         }
-        CarsCtx cx = cars_pre<TRAFFIC, false, NpcLDS, 1, false, false, true, false, 0, true, false, SEQ>(
-            p, in, a.out, e, el, nl, kDealClasses - 1, &rc);
+        CarsCtx cx = cars_pre<TRAFFIC, false, NpcLDS, 1, false, false, true, false, 0, true, false, SEQ, EVAL>(
+            p, in, a.out, e, el, nl, kDealClasses - 1, &rc, src);
         wave_lds_sync();
         if (s == 0) rc.first_reset = cx.do_reset;
-        cars_post<TRAFFIC, false, NpcLDS, 1, true, 0, true, 0, SEQ>(p, a.out, e, el, nl, cx, &rc);
+        cars_post<TRAFFIC, false, NpcLDS, 1, true, 0, true, 0, SEQ, EVAL>(p, a.out, e, el, nl, cx, &rc);
         if constexpr (SEQ) {
             // row s of the per-step arrays from the car LDS (cars_post left the final reward in
             // el.rew; a lane reads back what it wrote).  (Experiment build: in a sub-step that goes
@@ -2570,7 +2641,7 @@ __global__ __launch_bounds__(WAVE, TRAFFIC ? 2 : 4) void k_cars_repeat(
             const bool lane_on = tid < p.N;
             const int il = lane_on ? tid : 0;
             const uint32_t g = (uint32_t)(e * p.N + il);
-            const size_t en = (size_t)p.E * p.N, row = (size_t)s * en;
+            const size_t en = (size_t)rowE * p.N, row = (size_t)s * en;
             const bool more = kSeqEarlyLoad && !cx.ended && s + 1 < repeat;  // (wave-uniform; row s + 1 < length)
             float na0 = 0.0f, na1 = 0.0f;
             if (more) {
@@ -2587,6 +2658,18 @@ __global__ __launch_bounds__(WAVE, TRAFFIC ? 2 : 4) void k_cars_repeat(
                 el.a0[il] = na0;
                 el.a1[il] = na1;
             }
+            if constexpr (EVAL) {
+                // the sub-step the candidate stops at: its return (lane = agent), count and flags
+                if (cx.ended || s + 1 == repeat) {
+                    const EvalOuts& ev = reinterpret_cast<const EvalArgs*>(&a)->ev;
+                    if (lane_on && ev.returns) gmem(ev.returns)[g] = rc.ret;
+                    if (tid == 0) {
+                        if (ev.substeps) gmem(ev.substeps)[e] = s + 1;
+                        if (ev.term) gmem(ev.term)[e] = cx.term;
+                        if (ev.trunc) gmem(ev.trunc)[e] = cx.trunc;
+                    }
+                }
+            }
         }
         if (cx.ended) break;
         rc.step_prev = cx.step_no;
@@ -2601,13 +2684,25 @@ __global__ __launch_bounds__(WAVE, TRAFFIC ? 2 : 4) void k_cars_repeat(
         const SeqArgs& a = *(const SeqArgs*)ka;
         const int N = a.r.p.N, tid = threadIdx.x & (WAVE - 1);
         const int e = a.r.e_begin + xcd_env((int)blockIdx.x, (int)gridDim.x);
-        const size_t en = (size_t)a.r.p.E * N;
+        size_t en = (size_t)a.r.p.E * N;
+        if constexpr (EVAL) en = (size_t)reinterpret_cast<const EvalArgs*>(&a)->ev.C * N;
         if (tid < N) {
-            for (int z = rc.s + 1; z < repeat; ++z) {
+            for (int z = bad ? 0 : rc.s + 1; z < repeat; ++z) {
                 const size_t g = (size_t)z * en + (size_t)e * N + tid;
                 if (a.rows.reward) gmem(a.rows.reward)[g] = 0.0f;
                 if (a.rows.done) gmem(a.rows.done)[g] = 0;
                 if (a.rows.status) gmem(a.rows.status)[g] = 0;
+            }
+        }
+        if constexpr (EVAL) {
+            if (bad) {  // a candidate without a root: every output defined, all zero
+                const EvalOuts& ev = reinterpret_cast<const EvalArgs*>(&a)->ev;
+                if (tid < N && ev.returns) gmem(ev.returns)[(size_t)e * N + tid] = 0.0f;
+                if (tid == 0) {
+                    if (ev.substeps) gmem(ev.substeps)[e] = 0;
+                    if (ev.term) gmem(ev.term)[e] = 0;
+                    if (ev.trunc) gmem(ev.trunc)[e] = 0;
+                }
             }
         }
     }
@@ -3972,6 +4067,18 @@ hipError_t launch_step_window(const SimParams& p, const StepInputs& in, const Ou
     if (n < 1 || (rows && n > kMaxSeq)) return hipErrorInvalidValue;
     const Window w{n, substeps, rows};
     return launch_part(p, in, out, 0, p.E, s, nullptr, &w);
+}
+
+hipError_t launch_evaluate(const SimParams& p, const StepInputs& in, int C, const int32_t* roots, const SeqRows& rows,
+                           int n, const EvalOutputs& outs, hipStream_t s) {
+    if (n < 1 || n > kMaxSeq || C < 1 || !roots) return hipErrorInvalidValue;
+    // the window's car kernel over the candidates, and nothing after it: no k_lidar
+    const unsigned cars_lds = (unsigned)cars_lds_bytes(p.N, cars_k(p), true);
+    const EvalArgs ea{SeqArgs{RepeatArgs{p, in, Outputs{}, 0, n, nullptr}, rows},
+                      EvalOuts{roots, C, outs.gamma, outs.returns, outs.substeps, outs.terminated, outs.truncated}};
+    if (p.traffic) hipLaunchKernelGGL((k_cars_repeat<true, true, true>), dim3(C), dim3(WAVE), cars_lds, s, ea);
+    else hipLaunchKernelGGL((k_cars_repeat<false, true, true>), dim3(C), dim3(WAVE), cars_lds, s, ea);
+    return hipGetLastError();
 }
 
 hipError_t launch_serve(const SimParams& p, const SimParams* dp, const ServeArgs& sa, const Outputs& out,

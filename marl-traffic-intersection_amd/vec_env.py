@@ -99,6 +99,7 @@ class VecIntersectionEnv:
             self._out = self._h.alloc_outputs()
         self._out_rep = None  # the same buffers plus `substeps`, made at the first frame-skip step
         self._out_seq = None  # ... plus the per-step rows of a plan rollout (step_sequence), per plan length
+        self._out_eval = {}   # (T, C) -> the outputs of evaluate_plans
 
     # ----------------------------------------------------------------- utils
     @property
@@ -260,6 +261,63 @@ class VecIntersectionEnv:
         info = {k: o[k] for k in ("done", "status", "agents_alive", "step", "substeps", "reward_seq", "done_seq",
                                   "status_seq")}
         return o["obs"], o["reward"], o["terminated"], o["truncated"], info
+
+    def evaluate_plans(self, actions, roots, dt=1.0 / 60.0, gamma: float = 1.0, spawn_route=None, copy: bool = False):
+        """Score C candidate plans from the live batch without touching it (Handle.evaluate_plans):
+        actions [T, C, N, 2], roots [C] (the live env each candidate starts from; C is free of
+        num_envs) -> dict of returns [C, N] (discounted by gamma, f32), reward_seq / done_seq /
+        status_seq [T, C, N] (zero after a candidate stopped), substeps / terminated / truncated [C].
+        No observation and no LiDAR: run the winner through `step_sequence` for its leaf.  The env's
+        state, last outputs and random stream stay as they are.  spawn_route, if given, is [T][C].
+        torch: stream-ordered on the current stream, zero-copy; the returned tensors are cached per
+        (T, C) and reused by the next call of that shape."""
+        if self.backend == "torch":
+            t = self._torch
+            self._bind_stream()
+            dev = self._out["obs"].device
+            a = actions
+            if not (isinstance(a, t.Tensor) and a.is_cuda and a.dtype == t.float32 and a.is_contiguous()):
+                a = t.as_tensor(a, dtype=t.float32, device=dev).contiguous()
+            r = roots
+            if not (isinstance(r, t.Tensor) and r.is_cuda and r.dtype == t.int32 and r.is_contiguous()):
+                r = t.as_tensor(r, dtype=t.int32, device=dev).contiguous()
+            if r.dim() != 1 or a.dim() != 4 or tuple(a.shape[1:]) != (r.shape[0], self.num_agents, 2):
+                raise ValueError(f"actions must be [T, C, {self.num_agents}, 2] and roots [C], got {tuple(a.shape)} "
+                                 f"and {tuple(r.shape)}")
+            if a.device.index != self.device_index or r.device.index != self.device_index:
+                raise ValueError("actions or roots are on another device")
+            T, C = int(a.shape[0]), int(r.shape[0])
+            o = self._eval_out(T, C)
+            sp = None
+            if spawn_route is not None:
+                sp = t.as_tensor(spawn_route, dtype=t.int32, device=dev).contiguous()
+                if tuple(sp.shape) != (T, C):
+                    raise ValueError(f"spawn_route must be [{T}][{C}], got {tuple(sp.shape)}")
+            self._h.evaluate_plans(a, r, dt, gamma, spawn_route=sp, out=o, device=True, candidates=C, length=T)
+            return {k: v.clone() for k, v in o.items()} if copy else o
+        shape = np.shape(actions)
+        if len(shape) != 4:
+            raise ValueError(f"actions must be [T, C, {self.num_agents}, 2], got {shape}")
+        o = self._eval_out(int(shape[0]), int(shape[1]))
+        self._h.evaluate_plans(actions, roots, dt, gamma, spawn_route=spawn_route, out=o)
+        return {k: v.copy() for k, v in o.items()} if copy else o
+
+    def _eval_out(self, T, C):
+        """The output buffers of evaluate_plans, kept per (T, C)."""
+        if not 1 <= T <= _capi.MEV_MAX_REPEAT or not 1 <= C <= _capi.MEV_MAX_CANDIDATES:
+            raise ValueError(f"a call has 1..{_capi.MEV_MAX_REPEAT} rows and 1..{_capi.MEV_MAX_CANDIDATES} candidates, "
+                             f"got {T} and {C}")
+        o = self._out_eval.get((T, C))
+        if o is None:
+            o = {}
+            for k, dtype, shape in _capi._EVAL_OUTS:
+                if self.backend == "torch":
+                    o[k] = self._torch.zeros(shape(T, C, self.num_agents), dtype=getattr(self._torch, np.dtype(dtype).name),
+                                             device=self._out["obs"].device)
+                else:
+                    o[k] = np.zeros(shape(T, C, self.num_agents), dtype)
+            self._out_eval[(T, C)] = o
+        return o
 
     def _actions_tensor(self, actions, plan):
         """actions as a contiguous float32 tensor on this env's device: [E, N, 2], or (plan) [T, E, N, 2]."""
