@@ -335,7 +335,7 @@ int mev_step_sequence(mev_handle* h, const mev_sequence_args* args);
  * No leaf observation is returned and no LiDAR is cast, on purpose: the LiDAR hand-off tables are
  * per-env scratch sized by num_envs, and a cast per candidate is the cost this call exists to avoid.  A
  * planner that wants the leaf observation of the winning plan runs that one plan through
- * mev_step_sequence.
+ * mev_step_sequence; one that wants every candidate's (a value at the leaf) calls mev_evaluate_leaves below.
  * Errors (MEV_E_INVALID, the handle untouched): null actions or roots, no output pointer at all,
  * candidates outside 1..MEV_MAX_CANDIDATES, length outside 1..MEV_MAX_REPEAT, any flag other than
  * MEV_DEVICE_PTRS.  Host pointers: a root outside [0, E) -> MEV_E_RANGE; the arrays are staged in a
@@ -371,6 +371,53 @@ typedef struct {
     uint32_t flags;             /* MEV_DEVICE_PTRS only                                              */
 } mev_evaluate_args;
 int mev_evaluate_plans(mev_handle* h, const mev_evaluate_args* args);
+
+/* Plan evaluation with leaf observations: mev_evaluate_plans, and for EVERY candidate the observation
+ * of the state it stopped at -- what a planner that adds a learned value at the leaf needs
+ * (returns + gamma^k * V(obs_leaf): TD-MPC-style MPPI, AlphaZero / MuZero-style search, n-step
+ * bootstrapped critic targets).  Everything mev_evaluate_plans defines holds unchanged and bit for
+ * bit: the *_seq rows, returns, substeps, the flags, the Philox spawner keyed by c, the handle's
+ * counter not advanced, dt_seq ALWAYS a host pointer.  Every output of `eval` is optional here.
+ *
+ *   leaf_obs[c][i][0 .. obs_dim) = the row mev_step_sequence would return in obs for agent i of an env
+ *   holding a copy of live env roots[c], given candidate c's plan without MEV_AUTO_RESET
+ *
+ * i.e. the observation after sub-step k = substeps[c]; the head and the LiDAR block are cast once, from
+ * the state the candidate stopped at, respawns included.  Every float of every row is written by the
+ * call, padding columns beyond 31 + R included: the caller prepares nothing.  With C == num_envs,
+ * leaf_obs equals the obs of mev_restore_map(roots) + mev_step_sequence bit for bit.
+ * The handle is untouched exactly as for mev_evaluate_plans -- state, car sizes, last outputs
+ * (mev_get_outputs, DLPack), Philox counter, NPC diagnostics and a snapshot's bytes -- and its own
+ * LiDAR hand-off tables and output buffers are neither read nor written: the candidates hand their
+ * poses, candidate masks and obstacle boxes to the cast through a per-handle scratch indexed by
+ * candidate.  That scratch only grows, to 64 MiB at the most (33 bytes per agent + 16 per agent and NPC
+ * slot: 904 per candidate at 8 agents and the default 32 slots, 4160 at 64 agents + 64 slots); a call
+ * with more candidates than it holds runs in chunks -- rollout, then cast, per chunk, in stream order --
+ * with the same results.
+ * MEV_LEAF_CHUNK=n in the environment at mev_create fixes the chunk at n candidates (tests).
+ * Errors (MEV_E_INVALID, the handle untouched): null leaf_obs, and everything mev_evaluate_plans
+ * refuses except "no output pointer at all" (leaf_obs is one).  Host pointers: a root outside [0, E) ->
+ * MEV_E_RANGE; leaf_obs is staged through the same per-handle staging block as the other arrays, and
+ * the call is synchronous.  Device pointers: such a root makes its candidate a no-op whose leaf_obs
+ * rows are all zero bits, like its other outputs; other candidates are unaffected; the call does not
+ * synchronise.  Launched on the runtime-layout path, as mev_evaluate_plans (any N <= 64, <= 64 NPC
+ * slots, per-car sizes, any beam list including lists that run without culling); not counted by
+ * mev_kernel_timing.
+ * Measured (python tools/bench_evaluate_leaves.py -> profiles/evaluate_leaves_sweep.json; the method of
+ * mev_evaluate_plans' figures): at 4096 envs x 8 agents x 64 beams, device pointers, C = 4096 candidates (64 per
+ * root), every output: 74.2 us per call at T = 4 against 154.1 us for mev_restore_map + mev_step_sequence in the same
+ * session (2.08x), 55.1 against 135.8 us at T = 2 (2.46x), 110.1 against 189.1 us at T = 8 (1.72x), 183.6 against
+ * 271.4 us at T = 16 (1.48x); the pair's closing mev_restore is another 117.8-141.9 us.  Over mev_evaluate_plans on
+ * the same inputs the leaves cost 34.4 us at T = 2 to 52.8 us at T = 16 (the cast is one k_lidar, about 31 us); a
+ * further sub-step costs 9.2 us against 7.9 us for mev_evaluate_plans (it builds the obstacle table) and 9.7 us for the
+ * pair.  C = 16384 from the same handle: 247.1 us at T = 4, 0.0151 us per candidate (0.0181 at C = 4096).  One-ego
+ * traffic (4096 x 1 x 64, density 0.5): 132.0 against 227.2 us at T = 4 (1.72x), 483.3 against 592.5 us at T = 16
+ * (1.23x).  Every measured shape is below the pair by far more than the blocks' spreads. */
+typedef struct {
+    mev_evaluate_args eval;  /* exactly as mev_evaluate_plans; every output in it is optional here */
+    float* leaf_obs;         /* required, [C][N][obs_dim] */
+} mev_leaf_args;
+int mev_evaluate_leaves(mev_handle* h, const mev_leaf_args* args);
 
 /* Outputs of the last step / reset, from the handle's own device buffers.
  * Lifetime: after a step that wrote caller-owned output buffers (device

@@ -50,7 +50,7 @@ EXPORTED = (
     "mev_gather_wait", "mev_output_dlpack", "mev_packed_layout2", "mev_set_gather_format", "mev_lidar_decode_table",
     "mev_unpack_gathered", "mev_add_route", "mev_add_route_n", "mev_set_car_dims", "mev_get_car_dims", "mev_car_dims_active",
     "mev_set_beam_angles", "mev_get_beam_angles", "mev_decode_errors", "mev_step_sequence", "mev_restore_map",
-    "mev_evaluate_plans",
+    "mev_evaluate_plans", "mev_evaluate_leaves",
 )
 
 
@@ -99,6 +99,10 @@ class MevEvaluateArgs(ctypes.Structure):  # mev_evaluate_args
                 ("gamma", ctypes.c_float), ("returns", _vp), ("reward_seq", _vp), ("done_seq", _vp),
                 ("status_seq", _vp), ("substeps", _vp), ("terminated", _vp), ("truncated", _vp),
                 ("flags", ctypes.c_uint32)]
+
+
+class MevLeafArgs(ctypes.Structure):  # mev_leaf_args
+    _fields_ = [("eval", MevEvaluateArgs), ("leaf_obs", _vp)]
 
 
 # outputs of evaluate_plans: (key, dtype, shape of (T, C, N))
@@ -172,6 +176,7 @@ def load_library(variant: str = None):
     L.mev_step_sequence.argtypes = [_vp, ctypes.POINTER(MevSequenceArgs)]
     L.mev_restore_map.argtypes = [_vp, _vp, _vp, ctypes.c_uint32]
     L.mev_evaluate_plans.argtypes = [_vp, ctypes.POINTER(MevEvaluateArgs)]
+    L.mev_evaluate_leaves.argtypes = [_vp, ctypes.POINTER(MevLeafArgs)]
     L.mev_get_outputs.argtypes = [_vp] + [_vp] * 8 + [ctypes.c_uint32]
     L.mev_get_state.argtypes = [_vp, ctypes.POINTER(MevState)]
     L.mev_set_state.argtypes = [_vp, ctypes.POINTER(MevState)]
@@ -597,7 +602,7 @@ class Handle:
 
     def evaluate_plans(self, actions, roots, dt=1.0 / 60.0, gamma: float = 1.0, spawn_route=None,
                        out: Optional[dict] = None, device: bool = False, candidates: Optional[int] = None,
-                       length: Optional[int] = None, flags: int = 0):
+                       length: Optional[int] = None, flags: int = 0, leaf_obs: bool = False):
         """Score candidate plans from the live batch (mev_evaluate_plans); the handle stays as it is.
         actions [T][C][N][2], roots [C] (the live env each candidate starts from), dt a float or T
         floats (always host values), spawn_route optional [T][C].  Returns `returns` [C][N] (the
@@ -605,7 +610,10 @@ class Handle:
         candidate stopped), `substeps`, `terminated`, `truncated` [C].  No observation, no LiDAR.
         device=True: every array is a device tensor/pointer, only the outputs present in `out` are
         written, and C, T are roots.shape[0], actions.shape[0] (or `candidates` / `length` for raw
-        pointers).  flags: further bits for the call's flags word (the library refuses them)."""
+        pointers).  flags: further bits for the call's flags word (the library refuses them).
+        leaf_obs=True (mev_evaluate_leaves): the result gains `leaf_obs` [C][N][obs_dim], the
+        observation of the state each candidate stopped at (head and LiDAR block; every float
+        written).  In device mode out["leaf_obs"] must be there; the other outputs are optional."""
         N = self.N
         if device:
             if length is None:
@@ -638,7 +646,13 @@ class Handle:
             for k, dtype, shape in _EVAL_OUTS:
                 if out.get(k) is not None and (out[k].shape != shape(T, C, N) or out[k].dtype != dtype):
                     raise ValueError(f"{k} must be {np.dtype(dtype).name} {list(shape(T, C, N))}, got {out[k].shape}")
-        a = MevEvaluateArgs()
+            if leaf_obs:
+                if out.get("leaf_obs") is None:
+                    out["leaf_obs"] = np.zeros((C, N, self.D), np.float32)
+                if out["leaf_obs"].shape != (C, N, self.D) or out["leaf_obs"].dtype != np.float32:
+                    raise ValueError(f"leaf_obs must be float32 {[C, N, self.D]}, got {out['leaf_obs'].shape}")
+        la = MevLeafArgs()
+        a = la.eval
         a.actions, a.roots, a.spawn_route = _ptr(actions), _ptr(roots), _ptr(spawn_route)
         a.candidates, a.length, a.gamma = C, T, float(gamma)
         dts = None
@@ -653,7 +667,11 @@ class Handle:
         for k, _, _ in _EVAL_OUTS:
             setattr(a, k, _ptr(out.get(k)))
         a.flags = (MEV_DEVICE_PTRS if device else 0) | int(flags)
-        _check(self._lib.mev_evaluate_plans(self._h, ctypes.byref(a)))
+        if leaf_obs:
+            la.leaf_obs = _ptr(out.get("leaf_obs"))
+            _check(self._lib.mev_evaluate_leaves(self._h, ctypes.byref(la)))
+        else:
+            _check(self._lib.mev_evaluate_plans(self._h, ctypes.byref(a)))
         return out
 
     # -- multi-GPU gather (mev_comm_*) -------------------------------------

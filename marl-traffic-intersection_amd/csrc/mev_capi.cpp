@@ -107,6 +107,10 @@ struct mev_handle {
     int32_t* d_env_map = nullptr;    // [E] env map of a host-mode mev_restore_map
     uint8_t* d_eval = nullptr;       // every array of a host-mode mev_evaluate_plans, grown to the largest call seen
     size_t eval_cap = 0;
+    // mev_evaluate_leaves: the candidates' LiDAR hand-off (mev::LeafHand), grow-only up to kLeafHandCap
+    uint8_t* d_leaf = nullptr;
+    size_t leaf_cap = 0;
+    int leaf_chunk = 0;  // MEV_LEAF_CHUNK at mev_create: candidates per chunk (0: as many as the cap holds)
     uint8_t* d_mask = nullptr;
     float* d_paths = nullptr;
     int32_t* d_rlen = nullptr;  // [route_cap] each path's own length (RouteTab::len)
@@ -253,6 +257,7 @@ struct mev_handle {
         if (gs_pin) (void)hipHostFree(gs_pin);
         if (d_snap_stage) (void)hipFree(d_snap_stage);
         if (d_eval) (void)hipFree(d_eval);
+        if (d_leaf) (void)hipFree(d_leaf);
         for (void* p : allocs) (void)hipFree(p);
         if (own_stream) (void)hipStreamDestroy(own_stream);
     }
@@ -357,6 +362,9 @@ int mev_create(const mev_config* cfg, mev_handle** out) {
         h->deal_on = !(nd && nd[0] == '1');
         const char* nw = getenv("MEV_NO_WORLD_CONST");
         h->sp.no_world_const = nw && nw[0] == '1';
+        const char* lc = getenv("MEV_LEAF_CHUNK");
+        const long lcv = lc ? strtol(lc, nullptr, 10) : 0;
+        h->leaf_chunk = lcv > 0 && lcv <= MEV_MAX_CANDIDATES ? int(lcv) : 0;
     }
     if (h->cfg.traffic_density < 0.0f) h->cfg.traffic_density = 0.0f;  // configure_traffic (:56-60)
     h->D = D;
@@ -1587,16 +1595,20 @@ int mev_step_sequence(mev_handle* h, const mev_sequence_args* sa) {
 // mev_evaluate_plans (include/marlenv.h): the plan rollout's loop over C candidates that start from
 // copies of live envs, nothing of the handle written.  Host mode stages every array in one device
 // block of the handle that grows to the largest call seen.
-int mev_evaluate_plans(mev_handle* h, const mev_evaluate_args* ea) {
-    if (!h || !ea) return fail(MEV_E_INVALID, "null argument");
+// leaf_obs: mev_evaluate_leaves' [C][N][obs_dim] rows (null: mev_evaluate_plans).  The candidates'
+// LiDAR hand-off lives in a per-handle scratch that only grows, to kLeafHandCap at the most: a call
+// with more candidates than the cap holds (or than MEV_LEAF_CHUNK) goes through in chunks.
+constexpr size_t kLeafHandCap = size_t(64) << 20;
+static int evaluate(mev_handle* h, const mev_evaluate_args* ea, float* leaf_obs, bool leaves) {
+    const char* fn = leaves ? "mev_evaluate_leaves" : "mev_evaluate_plans";
     if (!ea->actions || !ea->roots) return fail(MEV_E_INVALID, "actions and roots required");
     if (ea->candidates < 1 || ea->candidates > MEV_MAX_CANDIDATES)
         return fail(MEV_E_INVALID, "candidates must be in 1.." + std::to_string(MEV_MAX_CANDIDATES));
     if (ea->length < 1 || ea->length > MEV_MAX_REPEAT)
         return fail(MEV_E_INVALID, "length must be in 1.." + std::to_string(MEV_MAX_REPEAT));
-    if (ea->flags & ~uint32_t(MEV_DEVICE_PTRS)) return fail(MEV_E_INVALID, "mev_evaluate_plans takes MEV_DEVICE_PTRS only");
-    if (!ea->returns && !ea->reward_seq && !ea->done_seq && !ea->status_seq && !ea->substeps && !ea->terminated &&
-        !ea->truncated)
+    if (ea->flags & ~uint32_t(MEV_DEVICE_PTRS)) return fail(MEV_E_INVALID, std::string(fn) + " takes MEV_DEVICE_PTRS only");
+    if (!leaves && !ea->returns && !ea->reward_seq && !ea->done_seq && !ea->status_seq && !ea->substeps &&
+        !ea->terminated && !ea->truncated)
         return fail(MEV_E_INVALID, "mev_evaluate_plans needs at least one output");
     const bool dev = (ea->flags & MEV_DEVICE_PTRS) != 0;
     const size_t C = size_t(ea->candidates), T = size_t(ea->length), N = size_t(h->cfg.num_agents), CN = C * N;
@@ -1618,6 +1630,27 @@ int mev_evaluate_plans(mev_handle* h, const mev_evaluate_args* ea) {
     in.rng_counter = h->rng_counter;  // sub-step s: + s; the handle's counter stays
     mev::EvalOutputs eo{ea->gamma, ea->returns, ea->substeps, ea->terminated, ea->truncated};
     const int32_t* d_roots = ea->roots;
+    const size_t obs_bytes = leaves ? CN * size_t(h->sp.D) * sizeof(float) : 0;
+    float* d_leaf_obs = leaf_obs;
+    int chunk = 0;
+    if (leaves) {
+        // candidates per chunk: what the capped scratch holds (at least one), or MEV_LEAF_CHUNK
+        const size_t per = mev::leaf_hand_bytes(h->sp, 1024) / 1024 + 1;
+        size_t fit = kLeafHandCap / per;
+        if (fit < 1) fit = 1;
+        chunk = int(h->leaf_chunk ? size_t(h->leaf_chunk) : fit);
+        if (size_t(chunk) > C) chunk = int(C);
+        const size_t need = mev::leaf_hand_bytes(h->sp, chunk);
+        if (need > h->leaf_cap) {
+            HIP_TRY(hipStreamSynchronize(h->stream));
+            if (h->d_leaf) (void)hipFree(h->d_leaf);
+            h->d_leaf = nullptr;
+            h->leaf_cap = 0;
+            const hipError_t err = hipMalloc(reinterpret_cast<void**>(&h->d_leaf), need);
+            if (err != hipSuccess) return fail(MEV_E_NOMEM, std::string("device allocation failed: ") + hipGetErrorString(err));
+            h->leaf_cap = need;
+        }
+    }
     if (dev) {
         in.actions = ea->actions;
         in.spawn_route = ea->spawn_route;
@@ -1639,6 +1672,7 @@ int mev_evaluate_plans(mev_handle* h, const mev_evaluate_args* ea) {
         const size_t o_done = take(ea->done_seq != nullptr, T * CN), o_status = take(ea->status_seq != nullptr, T * CN);
         const size_t o_sub = take(ea->substeps != nullptr, C * sizeof(int32_t));
         const size_t o_term = take(ea->terminated != nullptr, C), o_trunc = take(ea->truncated != nullptr, C);
+        const size_t o_obs = take(leaves, obs_bytes);
         if (off > h->eval_cap) {
             HIP_TRY(hipStreamSynchronize(h->stream));
             if (h->d_eval) (void)hipFree(h->d_eval);
@@ -1664,8 +1698,13 @@ int mev_evaluate_plans(mev_handle* h, const mev_evaluate_args* ea) {
         if (ea->substeps) eo.substeps = reinterpret_cast<int32_t*>(b + o_sub);
         if (ea->terminated) eo.terminated = b + o_term;
         if (ea->truncated) eo.truncated = b + o_trunc;
+        if (leaves) d_leaf_obs = reinterpret_cast<float*>(b + o_obs);
     }
-    HIP_TRY(mev::launch_evaluate(h->sp, in, int(C), d_roots, rows, int(T), eo, h->stream));
+    if (leaves)
+        HIP_TRY(mev::launch_evaluate_leaves(h->sp, in, int(C), d_roots, rows, int(T), eo, d_leaf_obs, h->d_leaf, chunk,
+                                            h->stream));
+    else
+        HIP_TRY(mev::launch_evaluate(h->sp, in, int(C), d_roots, rows, int(T), eo, h->stream));
     if (!dev) {
         auto back = [h](void* dst, const void* src, size_t bytes) {
             return dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream) : hipSuccess;
@@ -1677,9 +1716,23 @@ int mev_evaluate_plans(mev_handle* h, const mev_evaluate_args* ea) {
         HIP_TRY(back(ea->substeps, eo.substeps, C * sizeof(int32_t)));
         HIP_TRY(back(ea->terminated, eo.terminated, C));
         HIP_TRY(back(ea->truncated, eo.truncated, C));
+        HIP_TRY(back(leaf_obs, d_leaf_obs, obs_bytes));
         HIP_TRY(hipStreamSynchronize(h->stream));
     }
     return MEV_OK;
+}
+
+int mev_evaluate_plans(mev_handle* h, const mev_evaluate_args* ea) {
+    if (!h || !ea) return fail(MEV_E_INVALID, "null argument");
+    return evaluate(h, ea, nullptr, false);
+}
+
+// mev_evaluate_leaves (include/marlenv.h): mev_evaluate_plans, and the observation of the state every
+// candidate stopped at: the car kernel's LEAF mode, then k_lidar over the candidates' hand-off.
+int mev_evaluate_leaves(mev_handle* h, const mev_leaf_args* la) {
+    if (!h || !la) return fail(MEV_E_INVALID, "null argument");
+    if (!la->leaf_obs) return fail(MEV_E_INVALID, "leaf_obs required");
+    return evaluate(h, &la->eval, la->leaf_obs, true);
 }
 
 static int sync_internal(mev_handle* h);  // below, with mev_device_outputs

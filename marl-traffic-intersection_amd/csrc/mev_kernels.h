@@ -248,6 +248,28 @@ struct EvalOutputs {
 };
 hipError_t launch_evaluate(const SimParams& p, const StepInputs& in, int C, const int32_t* roots, const SeqRows& rows,
                            int n, const EvalOutputs& outs, hipStream_t s);
+// Plan evaluation with leaf observations (mev_evaluate_leaves): launch_evaluate's rollout, and
+// leaf_obs [C][N][p.D] = the observation of the state each candidate stopped at
+// (k_cars_repeat<TRAFFIC, true, true, LEAF = true>, then k_lidar).  The sub-step a candidate stops
+// at writes its observation head into leaf_obs row c and publishes a LiDAR hand-off indexed by
+// the candidate -- poses, alive, candidate masks, boxes -- into `hand`, a scratch of the caller's
+// for `chunk` candidates (leaf_hand_bytes); k_lidar then casts the chunk's agents from a SimParams
+// copy whose ego block, alive, ob_box, ob_cand and E describe that scratch and whose rows are
+// leaf_obs.  The candidates go through in chunks of `chunk`, car kernel then cast per chunk, in
+// stream order; roots, actions, rows and outputs stay indexed by the global c.  p's own hand-off
+// tables, state and outputs are neither read (beyond the roots' state) nor written.
+struct LeafHand {
+    float* pose;                  // [4][stride]: x, y, (unused), heading -- the ego block's field order
+    int64_t stride;               // >= chunk * N
+    uint8_t* alive;               // [chunk * N]
+    int4* box;                    // [chunk][ob_stride]
+    unsigned long long* cand;     // [chunk * N][2]
+    int32_t c0;                   // the chunk's first candidate
+};
+size_t leaf_hand_bytes(const SimParams& p, int chunk);
+hipError_t launch_evaluate_leaves(const SimParams& p, const StepInputs& in, int C, const int32_t* roots,
+                                  const SeqRows& rows, int n, const EvalOutputs& outs, float* leaf_obs, uint8_t* hand,
+                                  int chunk, hipStream_t s);
 hipError_t launch_reset(const SimParams& p, const uint8_t* env_mask, const Outputs& out, hipStream_t s,
                         uint64_t rng_counter);
 // recompute the observation rows from the current state with LiDAR = max (after set_state)

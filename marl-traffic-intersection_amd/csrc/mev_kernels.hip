@@ -1749,14 +1749,19 @@ __device__ __forceinline__ void ego_phase1(const SimParams& p, const StepInputs&
 // field, the car sizes, the NPC slots) and never resets it; the actions, the spawn decision and
 // everything written are the candidate's (index e).  No LiDAR follows, so the part ends after the
 // respawns: no obstacle table, no candidate masks.
+// LEAF (mev_evaluate_leaves, k_cars_repeat<TRAFFIC, true, true, true>): EVAL whose candidates are
+// cast afterwards, so the part runs on and builds the obstacle table and candidate masks in LDS
+// every sub-step, as the plan rollout does (cars_post knows the stop).
 template <bool TRAFFIC, bool FUSED, class NL, int PK = 1, bool EARLY = false, bool ESPLIT = false, bool DIMS = false,
-          bool TSC = false, int NC = 0, bool REP = false, bool WC = false, bool SEQ = false, bool EVAL = false>
+          bool TSC = false, int NC = 0, bool REP = false, bool WC = false, bool SEQ = false, bool EVAL = false,
+          bool LEAF = false>
 __device__ __forceinline__ CarsCtx cars_pre(const SimParams& p, const StepInputs& in, const Outputs& out, const int e,
                                             const CarsLDS& el, NL* nl, int npc_cls = kDealClasses - 1,
                                             const RepCarry* rc = nullptr, const int src_e = 0) {
     static_assert(!REP || (!FUSED && PK == 1 && !EARLY && !ESPLIT && !TSC && NC == 0), "frame skip: k_cars' layout");
     static_assert(!SEQ || REP, "plan rollout: the frame-skip loop");
     static_assert(!EVAL || SEQ, "plan evaluation: the plan rollout's loop");
+    static_assert(!LEAF || EVAL, "leaf observations: a plan evaluation");
     static_assert(!ESPLIT || FUSED, "early split: k_step");
     static_assert(PK == 1 || (FUSED && !TRAFFIC), "several envs per wave: k_step without traffic");
     static_assert(!DIMS || (PK == 1 && !EARLY && !ESPLIT), "per-car sizes: the runtime-layout kernels");
@@ -2114,8 +2119,9 @@ __device__ __forceinline__ CarsCtx cars_pre(const SimParams& p, const StepInputs
         if (tid == 0) el.envw[6] = (int)(unsigned)m;
     }
     wave_lds_sync();
-    // (no LiDAR casts a candidate: neither its obstacle table nor its candidate masks are built)
-    if constexpr (EVAL) return CarsCtx{step_no, false, ncnt, false};
+    // (no LiDAR casts a scored candidate: neither its obstacle table nor its candidate masks are built;
+    // LEAF: one does, from the state cars_post finds it stopped at)
+    if constexpr (EVAL && !LEAF) return CarsCtx{step_no, false, ncnt, false};
 
     STAMP(4);
     // ---- LiDAR obstacle table (:374-388): every ego (alive or not), then NPCs,
@@ -2247,13 +2253,20 @@ __device__ __forceinline__ unsigned long long ts_ego_phase(const SimParams& p, c
 // handle's outputs, flags, state, LiDAR hand-off and observation rows stay as they are.  The
 // sub-step's reward goes into the car LDS for the kernel's row stores (as SEQ) and into the
 // discounted return of the carry; the flags go back in cx, and the body ends there.
+// LEAF (mev_evaluate_leaves): EVAL, and the sub-step the candidate stops at goes on to the
+// observation head -- into row e of out.obs, the caller's leaf_obs (e: the candidate) -- and
+// publishes the LiDAR hand-off of that state into the candidates' scratch lf (slot e - lf->c0):
+// per agent the pose, alive and the candidate masks, per candidate the boxes.  Still no state, no
+// handle output, no flag, no NPC survivor and no diagnostic is stored.
 template <bool TRAFFIC, bool FUSED, class NL, int PK = 1, bool DIMS = false, int NC = 0, bool REP = false,
-          int WCP1 = 0, bool SEQ = false, bool EVAL = false>
+          int WCP1 = 0, bool SEQ = false, bool EVAL = false, bool LEAF = false>
 __device__ __forceinline__ void cars_post(const SimParams& p, const Outputs& out, const int e, const CarsLDS& el,
-                                          const NL* nl, CarsCtx& cx, RepCarry* rc = nullptr) {
+                                          const NL* nl, CarsCtx& cx, RepCarry* rc = nullptr,
+                                          const LeafHand* lf = nullptr) {
     static_assert(!REP || (!FUSED && PK == 1 && NC == 0), "frame skip: k_cars' layout");
     static_assert(!SEQ || REP, "plan rollout: the frame-skip loop");
     static_assert(!EVAL || SEQ, "plan evaluation: the plan rollout's loop");
+    static_assert(!LEAF || EVAL, "leaf observations: a plan evaluation");
     using RW = StepRows<(WCP1 > 0), WCP1>;
     static_assert(WCP1 == 0 || (!TRAFFIC && FUSED && !DIMS), "constant rows: the compile-time layout's head writes");
     const int tid = threadIdx.x & (WAVE - 1);
@@ -2333,9 +2346,10 @@ __device__ __forceinline__ void cars_post(const SimParams& p, const Outputs& out
             rc->g = rc->g * rc->gamma;
             cx.term = terminated;
             cx.trunc = truncated;
-            return;
+            if constexpr (!LEAF) return;
+            else if (!cx.ended && rc->s + 1 < rc->n) return;  // (wave-uniform) the plan goes on
         }
-        if constexpr (REP) {
+        if constexpr (REP && !LEAF) {
             // acc = r (first sub-step) or acc + r, in sub-step order; the latest done's status
             rc->rew = rc->s == 0 ? rew_i : rc->rew + rew_i;
             if (done_i) { rc->any_done = 1; rc->latched = st_i; }
@@ -2345,25 +2359,43 @@ __device__ __forceinline__ void cars_post(const SimParams& p, const Outputs& out
             st_o = rc->any_done ? rc->latched : st_i;
             if (tid == 0 && rc->substeps) rc->substeps[e] = rc->s + 1;
         }
-        if (in_env) {
-            const int g = e * NE + i;
-            out.rew[g] = rew_i;
-            out.done[g] = done_o;
-            out.status[g] = st_o;
+        if constexpr (!LEAF) {
+            if (in_env) {
+                const int g = e * NE + i;
+                out.rew[g] = rew_i;
+                out.done[g] = done_o;
+                out.status[g] = st_o;
+            }
+            if (PK > 1 ? tid < npk : tid == 0) {
+                const int ev = e + (PK > 1 ? tid : 0);
+                gmem(p.step_count)[ev] = step_e;
+                out.term[ev] = terminated;
+                out.trunc[ev] = truncated;
+                out.alive_cnt[ev] = alive_cnt;
+                out.step[ev] = step_e;
+                gmem(p.pending_reset)[ev] = (terminated || truncated) ? 1 : 0;
+            }
         }
-        if (PK > 1 ? tid < npk : tid == 0) {
-            const int ev = e + (PK > 1 ? tid : 0);
-            gmem(p.step_count)[ev] = step_e;
-            out.term[ev] = terminated;
-            out.trunc[ev] = truncated;
-            out.alive_cnt[ev] = alive_cnt;
-            out.step[ev] = step_e;
-            gmem(p.pending_reset)[ev] = (terminated || truncated) ? 1 : 0;
+    }
+    if constexpr (LEAF) {
+        // the LiDAR hand-off of the state the candidate stopped at, by candidate: the boxes, then
+        // lane = agent the pose, alive and the candidate masks (cars_pre left all of it in LDS)
+        const int cl = e - lf->c0;  // the candidate's slot in the chunk
+        const int nob = (!TRAFFIC && NE == 1) ? 0 : N + ncnt;
+        for (int o = tid; o < nob; o += WAVE) lf->box[(size_t)cl * p.ob_stride + o] = el.box[o];
+        for (int i = tid; i < N; i += WAVE) {
+            const size_t g = (size_t)cl * NE + i;
+            gmem(lf->pose + lf->stride * EF_X)[g] = el.x[i];
+            gmem(lf->pose + lf->stride * EF_Y)[g] = el.y[i];
+            gmem(lf->pose + lf->stride * EF_H)[g] = el.h[i];
+            gmem(lf->alive)[g] = el.alive[i];
+            gmem(lf->cand)[2 * g] = el.cand[2 * i];
+            gmem(lf->cand)[2 * g + 1] = el.cand[2 * i + 1];
         }
     }
     // ---- the final ego state back to HBM (lane = agent)
-    ego_writeback(p, e, NE, N, el, do_reset, tid, DIMS);
-    if constexpr (REP) {
+    if constexpr (!LEAF) ego_writeback(p, e, NE, N, el, do_reset, tid, DIMS);
+    if constexpr (REP && !LEAF) {
         // the LiDAR hand-off of the state the env stopped at (cars_pre left it in LDS)
         const int nob = (!TRAFFIC && NE == 1) ? 0 : N + ncnt;
         for (int o = tid; o < nob; o += WAVE) p.ob_box[e * p.ob_stride + o] = el.box[o];
@@ -2373,7 +2405,7 @@ __device__ __forceinline__ void cars_post(const SimParams& p, const Outputs& out
             gmem(p.ob_cand)[2 * g + 1] = el.cand[2 * i + 1];
         }
     }
-    if (RW::state(out)) {
+    if (!LEAF && RW::state(out)) {  // (LEAF: float rows only)
         // the state gather format: the post-step state the root rebuilds the head from
         // (launch_decode_state), instead of the head itself
         const size_t n = (size_t)out.state_n;
@@ -2580,24 +2612,47 @@ struct EvalArgs {
     EvalOuts ev;
 };
 static_assert(sizeof(EvalArgs) <= 4096, "the kernel argument segment");
+// LEAF (mev_evaluate_leaves): EVAL over the candidates [e_begin, e_begin + grid) of the call's C --
+// one chunk -- with the observation of the state each candidate stopped at.  Workgroup = candidate
+// c = e_begin + block; roots, actions, rows and outputs are indexed by c as before.  Every
+// sub-step builds the obstacle table and candidate masks in LDS (cars_pre with LEAF); the sub-step
+// the candidate stops at writes its observation head into row c of out.obs (the caller's leaf_obs,
+// out.obs_ld floats per row) and its LiDAR hand-off into slot c - e_begin of the scratch lf
+// (cars_post with LEAF), from which k_lidar casts the chunk afterwards.  A candidate without a root
+// publishes its agents as dead and zeroes its rows' head and padding columns: k_lidar zeroes a dead
+// agent's LiDAR block.  The argument struct begins with EvalArgs.
+struct LeafArgs {
+    EvalArgs e;
+    LeafHand lf;
+};
+static_assert(sizeof(LeafArgs) <= 4096, "the kernel argument segment");
 // (four waves per SIMD, as k_step: 4096 envs are one round of single-wave workgroups on 256 CUs;
 // with the NPC phase 128 VGPRs would spill to scratch: two)
-template <bool TRAFFIC, bool SEQ = false, bool EVAL = false>
+template <bool TRAFFIC, bool SEQ = false, bool EVAL = false, bool LEAF = false>
 __global__ __launch_bounds__(WAVE, TRAFFIC ? 2 : 4) void k_cars_repeat(
-    typename std::conditional<EVAL, EvalArgs, typename std::conditional<SEQ, SeqArgs, RepeatArgs>::type>::type args) {
+    typename std::conditional<
+        LEAF, LeafArgs,
+        typename std::conditional<EVAL, EvalArgs, typename std::conditional<SEQ, SeqArgs, RepeatArgs>::type>::type>::type
+        args) {
     static_assert(!EVAL || SEQ, "plan evaluation: the plan rollout's loop");
+    static_assert(!LEAF || EVAL, "leaf observations: a plan evaluation");
     extern __shared__ __align__(16) unsigned char cars_lds[];
     __shared__ typename std::conditional<TRAFFIC, NpcLDS, char>::type nl_storage;
     NpcLDS* nl = nullptr;
     if constexpr (TRAFFIC) nl = &nl_storage;
     int repeat;
-    if constexpr (EVAL) repeat = args.s.r.repeat;
+    if constexpr (LEAF) repeat = args.e.s.r.repeat;
+    else if constexpr (EVAL) repeat = args.s.r.repeat;
     else if constexpr (SEQ) repeat = args.r.repeat;
     else repeat = args.repeat;
     RepCarry rc{0, repeat, 0, 0, false, 0.0f, 0, 0, nullptr, 1.0f, 0.0f, 1.0f};
     int src = 0;       // EVAL: the candidate's root (wave-uniform)
     bool bad = false;  // EVAL: a root outside [0, E): no sub-step runs
-    if constexpr (EVAL) {
+    if constexpr (LEAF) {
+        const int c = args.e.s.r.e_begin + xcd_env((int)blockIdx.x, (int)gridDim.x);
+        src = __builtin_amdgcn_readfirstlane(args.e.ev.roots[c]);
+        bad = (unsigned)src >= (unsigned)args.e.s.r.p.E;
+    } else if constexpr (EVAL) {
         const int c = xcd_env((int)blockIdx.x, (int)gridDim.x);
         src = __builtin_amdgcn_readfirstlane(args.ev.roots[c]);
         bad = (unsigned)src >= (unsigned)args.s.r.p.E;
@@ -2627,11 +2682,15 @@ __global__ __launch_bounds__(WAVE, TRAFFIC ? 2 : 4) void k_cars_repeat(
             in.dt = q.dt[s];
             in.spawn_prob = q.spawn_prob[s];
         }
-        CarsCtx cx = cars_pre<TRAFFIC, false, NpcLDS, 1, false, false, true, false, 0, true, false, SEQ, EVAL>(
+        CarsCtx cx = cars_pre<TRAFFIC, false, NpcLDS, 1, false, false, true, false, 0, true, false, SEQ, EVAL, LEAF>(
             p, in, a.out, e, el, nl, kDealClasses - 1, &rc, src);
         wave_lds_sync();
         if (s == 0) rc.first_reset = cx.do_reset;
-        cars_post<TRAFFIC, false, NpcLDS, 1, true, 0, true, 0, SEQ, EVAL>(p, a.out, e, el, nl, cx, &rc);
+        if constexpr (LEAF)
+            cars_post<TRAFFIC, false, NpcLDS, 1, true, 0, true, 0, SEQ, EVAL, LEAF>(
+                p, a.out, e, el, nl, cx, &rc, &reinterpret_cast<const LeafArgs*>(&a)->lf);
+        else
+            cars_post<TRAFFIC, false, NpcLDS, 1, true, 0, true, 0, SEQ, EVAL>(p, a.out, e, el, nl, cx, &rc);
         if constexpr (SEQ) {
             // row s of the per-step arrays from the car LDS (cars_post left the final reward in
             // el.rew; a lane reads back what it wrote).  (Experiment build: in a sub-step that goes
@@ -2702,6 +2761,18 @@ __global__ __launch_bounds__(WAVE, TRAFFIC ? 2 : 4) void k_cars_repeat(
                     if (ev.substeps) gmem(ev.substeps)[e] = 0;
                     if (ev.term) gmem(ev.term)[e] = 0;
                     if (ev.trunc) gmem(ev.trunc)[e] = 0;
+                }
+                if constexpr (LEAF) {
+                    // its agents dead in the hand-off (k_lidar zeroes their LiDAR blocks), and the
+                    // head and padding columns of its rows zero: every float of the rows defined
+                    const LeafArgs& la = *reinterpret_cast<const LeafArgs*>(&a);
+                    const Outputs& out = a.r.out;
+                    const int ls = a.r.p.lidar_slots;
+                    if (tid < N) gmem(la.lf.alive)[(size_t)(e - la.lf.c0) * N + tid] = 0;
+                    for (int i = 0; i < N; ++i) {
+                        float* row = out.obs + ((size_t)e * N + i) * out.obs_ld;
+                        for (int cc = tid; cc < out.obs_ld - ls; cc += WAVE) row[cc < OBS_HEAD ? cc : cc + ls] = 0.0f;
+                    }
                 }
             }
         }
@@ -3984,6 +4055,28 @@ struct Window {
     const SeqRows* rows;
 };
 
+// k_lidar over the agents [a_begin, a_end) of p, casting from p's hand-off into out's rows
+static hipError_t launch_lidar(const SimParams& p, const Outputs& out, int a_begin, int a_end, hipStream_t s) {
+    const int na = a_end - a_begin;
+    int G = lidar_group(p.R);
+    // small batches: trade pool size for waves (~4 per SIMD on 256 CUs) so latency is hidden
+    while (G > 1 && na / G < 4096) G = (G + 1) / 2;
+    static const int g_env = [] { const char* v = getenv("MEV_LIDAR_G"); return v ? atoi(v) : 0; }();
+    if (g_env > 0 && g_env <= 64 && (size_t)g_env * p.R <= 1024) G = g_env;  // experiments (tools/kernel_time.py)
+    // LDS: shrink the group, then the waves per block, to stay within 40 KB (64 KB hard) per block
+    int wpb = 4;
+    while (G > 1 && wpb * lidar_layout(G, p.R, lidar_cand_max(p)).bytes > 40 * 1024) G = (G + 1) / 2;
+    const int wave_lds = lidar_layout(G, p.R, lidar_cand_max(p)).bytes;
+    while (wpb > 1 && wpb * wave_lds > 64 * 1024) wpb /= 2;
+    const int groups = (na + G - 1) / G;
+    const unsigned blocks = (unsigned)((groups + wpb - 1) / wpb);
+    if (p.dist_tab)
+        hipLaunchKernelGGL(k_lidar<true>, dim3(blocks), dim3(wpb * WAVE), wpb * wave_lds, s, p, out, G, a_begin, a_end);
+    else
+        hipLaunchKernelGGL(k_lidar<false>, dim3(blocks), dim3(wpb * WAVE), wpb * wave_lds, s, p, out, G, a_begin, a_end);
+    return hipGetLastError();
+}
+
 // w: the window's looping car kernel in k_cars' place
 static hipError_t launch_part(const SimParams& p, const StepInputs& in, const Outputs& out, int e0, int e1,
                               hipStream_t s, const hipEvent_t* ev, const Window* w = nullptr) {
@@ -4004,24 +4097,7 @@ static hipError_t launch_part(const SimParams& p, const StepInputs& in, const Ou
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     if (ev) (void)hipEventRecord(ev[1], s);
-    const int a_begin = e0 * p.N, a_end = e1 * p.N, na = a_end - a_begin;
-    int G = lidar_group(p.R);
-    // small batches: trade pool size for waves (~4 per SIMD on 256 CUs) so latency is hidden
-    while (G > 1 && na / G < 4096) G = (G + 1) / 2;
-    static const int g_env = [] { const char* v = getenv("MEV_LIDAR_G"); return v ? atoi(v) : 0; }();
-    if (g_env > 0 && g_env <= 64 && (size_t)g_env * p.R <= 1024) G = g_env;  // experiments (tools/kernel_time.py)
-    // LDS: shrink the group, then the waves per block, to stay within 40 KB (64 KB hard) per block
-    int wpb = 4;
-    while (G > 1 && wpb * lidar_layout(G, p.R, lidar_cand_max(p)).bytes > 40 * 1024) G = (G + 1) / 2;
-    const int wave_lds = lidar_layout(G, p.R, lidar_cand_max(p)).bytes;
-    while (wpb > 1 && wpb * wave_lds > 64 * 1024) wpb /= 2;
-    const int groups = (na + G - 1) / G;
-    const unsigned blocks = (unsigned)((groups + wpb - 1) / wpb);
-    if (p.dist_tab)
-        hipLaunchKernelGGL(k_lidar<true>, dim3(blocks), dim3(wpb * WAVE), wpb * wave_lds, s, p, out, G, a_begin, a_end);
-    else
-        hipLaunchKernelGGL(k_lidar<false>, dim3(blocks), dim3(wpb * WAVE), wpb * wave_lds, s, p, out, G, a_begin, a_end);
-    e = hipGetLastError();
+    e = launch_lidar(p, out, e0 * p.N, e1 * p.N, s);
     if (ev && e == hipSuccess) (void)hipEventRecord(ev[2], s);
     return e;
 }
@@ -4079,6 +4155,60 @@ hipError_t launch_evaluate(const SimParams& p, const StepInputs& in, int C, cons
     if (p.traffic) hipLaunchKernelGGL((k_cars_repeat<true, true, true>), dim3(C), dim3(WAVE), cars_lds, s, ea);
     else hipLaunchKernelGGL((k_cars_repeat<false, true, true>), dim3(C), dim3(WAVE), cars_lds, s, ea);
     return hipGetLastError();
+}
+
+// the hand-off scratch of `chunk` candidates: each array at a 256-byte boundary
+static size_t leaf_al(size_t b) { return (b + 255) & ~size_t(255); }
+static size_t leaf_stride(const SimParams& p, int chunk) { return leaf_al((size_t)chunk * p.N * sizeof(float)) / sizeof(float); }
+size_t leaf_hand_bytes(const SimParams& p, int chunk) {
+    const size_t cn = (size_t)chunk * p.N;
+    return 4 * leaf_stride(p, chunk) * sizeof(float) + leaf_al(cn * 16) + leaf_al((size_t)chunk * p.ob_stride * sizeof(int4)) +
+           leaf_al(cn);
+}
+
+hipError_t launch_evaluate_leaves(const SimParams& p, const StepInputs& in, int C, const int32_t* roots,
+                                  const SeqRows& rows, int n, const EvalOutputs& outs, float* leaf_obs, uint8_t* hand,
+                                  int chunk, hipStream_t s) {
+    if (n < 1 || n > kMaxSeq || C < 1 || !roots || !leaf_obs || !hand || chunk < 1) return hipErrorInvalidValue;
+    if (chunk > C) chunk = C;
+    const unsigned cars_lds = (unsigned)cars_lds_bytes(p.N, cars_k(p), true);
+    const size_t cn = (size_t)chunk * p.N, S = leaf_stride(p, chunk);
+    LeafHand lf{};
+    lf.pose = reinterpret_cast<float*>(hand);
+    lf.stride = (int64_t)S;
+    lf.cand = reinterpret_cast<unsigned long long*>(hand + 4 * S * sizeof(float));
+    lf.box = reinterpret_cast<int4*>(reinterpret_cast<uint8_t*>(lf.cand) + leaf_al(cn * 16));
+    lf.alive = reinterpret_cast<uint8_t*>(lf.box) + leaf_al((size_t)chunk * p.ob_stride * sizeof(int4));
+    // what k_lidar casts from: the scratch in the place of the ego block and the hand-off tables
+    // (LidarSrcHbm reads x, y, heading, alive, ob_cand, ob_box and the beam list, nothing else of the state)
+    SimParams lp = p;
+    lp.E = chunk;
+    lp.ego = EgoSoA{};
+    lp.ego.x = lf.pose;
+    lp.ego.alive = lf.alive;
+    lp.ego.stride = lf.stride;
+    lp.ob_box = lf.box;
+    lp.ob_cand = lf.cand;
+    Outputs co{};  // the car kernel's rows: leaf_obs by the global candidate
+    co.obs = leaf_obs;
+    co.obs_ld = p.D;
+    for (int c0 = 0; c0 < C; c0 += chunk) {
+        const int nc = C - c0 < chunk ? C - c0 : chunk;
+        lf.c0 = c0;
+        const LeafArgs la{EvalArgs{SeqArgs{RepeatArgs{p, in, co, c0, n, nullptr}, rows},
+                                   EvalOuts{roots, C, outs.gamma, outs.returns, outs.substeps, outs.terminated,
+                                            outs.truncated}},
+                          lf};
+        if (p.traffic) hipLaunchKernelGGL((k_cars_repeat<true, true, true, true>), dim3(nc), dim3(WAVE), cars_lds, s, la);
+        else hipLaunchKernelGGL((k_cars_repeat<false, true, true, true>), dim3(nc), dim3(WAVE), cars_lds, s, la);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+        Outputs lo = co;  // the cast's rows: the chunk's, by the candidate's slot
+        lo.obs = leaf_obs + (size_t)c0 * p.N * p.D;
+        e = launch_lidar(lp, lo, 0, nc * p.N, s);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
 }
 
 hipError_t launch_serve(const SimParams& p, const SimParams* dp, const ServeArgs& sa, const Outputs& out,

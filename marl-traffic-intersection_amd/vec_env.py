@@ -262,7 +262,8 @@ class VecIntersectionEnv:
                                   "status_seq")}
         return o["obs"], o["reward"], o["terminated"], o["truncated"], info
 
-    def evaluate_plans(self, actions, roots, dt=1.0 / 60.0, gamma: float = 1.0, spawn_route=None, copy: bool = False):
+    def evaluate_plans(self, actions, roots, dt=1.0 / 60.0, gamma: float = 1.0, spawn_route=None, copy: bool = False,
+                       leaf_obs: bool = False):
         """Score C candidate plans from the live batch without touching it (Handle.evaluate_plans):
         actions [T, C, N, 2], roots [C] (the live env each candidate starts from; C is free of
         num_envs) -> dict of returns [C, N] (discounted by gamma, f32), reward_seq / done_seq /
@@ -270,7 +271,9 @@ class VecIntersectionEnv:
         No observation and no LiDAR: run the winner through `step_sequence` for its leaf.  The env's
         state, last outputs and random stream stay as they are.  spawn_route, if given, is [T][C].
         torch: stream-ordered on the current stream, zero-copy; the returned tensors are cached per
-        (T, C) and reused by the next call of that shape."""
+        (T, C) and reused by the next call of that shape.
+        leaf_obs=True (mev_evaluate_leaves): the dict gains leaf_obs [C, N, obs_dim], the observation
+        of the state every candidate stopped at -- for planners that add a value at the leaf."""
         if self.backend == "torch":
             t = self._torch
             self._bind_stream()
@@ -287,23 +290,25 @@ class VecIntersectionEnv:
             if a.device.index != self.device_index or r.device.index != self.device_index:
                 raise ValueError("actions or roots are on another device")
             T, C = int(a.shape[0]), int(r.shape[0])
-            o = self._eval_out(T, C)
+            o = self._eval_out(T, C, leaf_obs)
             sp = None
             if spawn_route is not None:
                 sp = t.as_tensor(spawn_route, dtype=t.int32, device=dev).contiguous()
                 if tuple(sp.shape) != (T, C):
                     raise ValueError(f"spawn_route must be [{T}][{C}], got {tuple(sp.shape)}")
-            self._h.evaluate_plans(a, r, dt, gamma, spawn_route=sp, out=o, device=True, candidates=C, length=T)
+            self._h.evaluate_plans(a, r, dt, gamma, spawn_route=sp, out=o, device=True, candidates=C, length=T,
+                                   leaf_obs=leaf_obs)
             return {k: v.clone() for k, v in o.items()} if copy else o
         shape = np.shape(actions)
         if len(shape) != 4:
             raise ValueError(f"actions must be [T, C, {self.num_agents}, 2], got {shape}")
-        o = self._eval_out(int(shape[0]), int(shape[1]))
-        self._h.evaluate_plans(actions, roots, dt, gamma, spawn_route=spawn_route, out=o)
+        o = self._eval_out(int(shape[0]), int(shape[1]), leaf_obs)
+        self._h.evaluate_plans(actions, roots, dt, gamma, spawn_route=spawn_route, out=o, leaf_obs=leaf_obs)
         return {k: v.copy() for k, v in o.items()} if copy else o
 
-    def _eval_out(self, T, C):
-        """The output buffers of evaluate_plans, kept per (T, C)."""
+    def _eval_out(self, T, C, leaf=False):
+        """The output buffers of evaluate_plans, kept per (T, C); leaf: with the leaf_obs buffer of
+        that shape (made at the first call that asks for it; the default call's dict never has it)."""
         if not 1 <= T <= _capi.MEV_MAX_REPEAT or not 1 <= C <= _capi.MEV_MAX_CANDIDATES:
             raise ValueError(f"a call has 1..{_capi.MEV_MAX_REPEAT} rows and 1..{_capi.MEV_MAX_CANDIDATES} candidates, "
                              f"got {T} and {C}")
@@ -317,6 +322,16 @@ class VecIntersectionEnv:
                 else:
                     o[k] = np.zeros(shape(T, C, self.num_agents), dtype)
             self._out_eval[(T, C)] = o
+        if leaf:
+            lo = self._out_eval.get((T, C, "leaf"))
+            if lo is None:
+                shape = (C, self.num_agents, int(self._out["obs"].shape[-1]))
+                if self.backend == "torch":
+                    lo = self._torch.zeros(shape, dtype=self._torch.float32, device=self._out["obs"].device)
+                else:
+                    lo = np.zeros(shape, np.float32)
+                self._out_eval[(T, C, "leaf")] = lo
+            o = dict(o, leaf_obs=lo)
         return o
 
     def _actions_tensor(self, actions, plan):
