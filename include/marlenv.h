@@ -419,6 +419,94 @@ typedef struct {
 } mev_leaf_args;
 int mev_evaluate_leaves(mev_handle* h, const mev_leaf_args* args);
 
+/* State pools: complete env states kept on the device OUTSIDE the live batch, so that a search can
+ * expand nodes that are not the root (mev_expand_plans below).  A pool has 1..MEV_MAX_POOL_SLOTS
+ * slots and belongs to the handle it was created from; mev_destroy releases the handle's remaining
+ * pools (their pointers are dead afterwards).  A slot holds one env's whole simulator state as
+ * structure-of-arrays over slots in the handle's own field layout: every ego field of mev_state, the
+ * NPC slots and count, the step counter and the car sizes of egos and NPCs -- no outputs, no LiDAR
+ * hand-off, no pending-reset flag.  Each slot has a valid byte that starts at 0; storing into the
+ * slot sets it to 1.  mev_set_car_dims clears the valid bytes of all the handle's pools, on the
+ * handle's stream (whether the per-car-size regime applies is a property of the whole handle, and a
+ * slot stored before must not be read under another); nothing else invalidates a slot.  Pools are
+ * not part of snapshots, mev_get_outputs or DLPack.  mev_pool_create: MEV_E_INVALID for a slot count
+ * out of range, MEV_E_NOMEM when the allocation fails (about 76 N + 48 max_npcs + 9 bytes per slot).
+ *
+ * mev_pool_capture copies live env envs[i] into slot slots[i], i < count, without stepping: a tree's
+ * root node.  flags: MEV_DEVICE_PTRS only.  Host pointers: an env outside [0, E) or a slot outside
+ * [0, slots) -> MEV_E_RANGE, nothing changed; synchronous.  Device pointers: such a pair is skipped,
+ * and the call does not synchronise.  A slot named twice holds one of the two envs.
+ *
+ * mev_pool_get_state is a host read-back for tests and debugging: the arrays of `out` (each
+ * optional) are [count][N] / [count][max_npcs] / [count] in mev_state's field meaning, row i = slot
+ * slots[i]; ego_dims [count][N][2] and npc_dims [count][max_npcs][2] in mev_get_car_dims' layout;
+ * valid [count].  slots is a host pointer (an entry out of range -> MEV_E_RANGE).  It synchronises
+ * the handle's stream.  NPC slots at or beyond a slot's npc_count hold unspecified values. */
+typedef struct mev_pool mev_pool;
+#define MEV_MAX_POOL_SLOTS (1 << 20)
+int mev_pool_create(mev_handle* h, int32_t slots, mev_pool** out);
+int mev_pool_destroy(mev_pool* pool);
+int mev_pool_slots(const mev_pool* pool, int32_t* slots);
+int mev_pool_capture(mev_handle* h, mev_pool* pool, const int32_t* envs, const int32_t* slots, int32_t count,
+                     uint32_t flags);
+int mev_pool_get_state(mev_pool* pool, const int32_t* slots, int32_t count, const mev_state* out, float* ego_dims,
+                       float* npc_dims, uint8_t* valid);
+
+/* Plan expansion: mev_evaluate_plans (with leaf_obs: mev_evaluate_leaves) whose candidates may START
+ * from a slot of a pool and whose STOP STATE is kept in one -- the node expansion of a tree search
+ * below depth one (AlphaZero / MuZero-style search, beam search, multi-level MPPI).  Everything the
+ * two calls define holds bit for bit, with two additions.
+ *
+ * Where a candidate starts.  src == NULL: live env roots[c], as before.  Otherwise a private copy of
+ * slot roots[c] of src.  A root outside [0, slots of src), or a slot whose valid byte is 0, is
+ * handled exactly like an out-of-range root of mev_evaluate_plans: MEV_E_RANGE with host pointers; with
+ * device pointers the candidate is a no-op whose every output is zero.  Nothing is stored for it.
+ *
+ * What is kept.  For a candidate that ran, with d = dst_slots[c] in [0, slots of dst): at the sub-step
+ * it stops at (terminated, truncated or the last) slot d of dst receives the state mev_step_sequence
+ * would leave in an env that held a copy of the root and ran this plan without MEV_AUTO_RESET -- every
+ * field mev_get_state and mev_get_car_dims report, the respawns of that sub-step included -- and the
+ * slot's valid byte becomes 1.  dst_slots[c] == -1 (with device pointers: any value out of range)
+ * stores nothing and leaves every slot as it was.
+ *
+ * Philox: sub-step s uses the handle's counter + counter_offset + (s - 1), keyed by c.  Composition:
+ * expanding T1 sub-steps into slot d, then T2 from slot d with counter_offset raised by T1 and the same
+ * candidate index, gives a candidate that did not end in the first part the same rows, flags, stop
+ * state and leaf_obs as one call with the concatenated plan (returns restart at g = 1 per call).
+ *
+ * The live batch, last outputs, Philox counter, NPC diagnostics and a snapshot's bytes are untouched,
+ * exactly as for mev_evaluate_plans.  src == dst is allowed (one tree in one pool); the dst_slots of
+ * the call must then be disjoint from its roots, and dst_slots must never name a slot twice.  Host
+ * pointers: both are checked before anything is launched (MEV_E_INVALID, nothing changed).  Device
+ * pointers: the caller's contract -- the offending slots' contents are unspecified, every access
+ * stays inside the pool.
+ * Errors as mev_evaluate_plans, plus a null dst or dst_slots and a pool of another handle
+ * (MEV_E_INVALID); "no output pointer at all" is not an error here, the pool is an output.  Host
+ * pointers: a dst_slots entry outside [-1, slots of dst) -> MEV_E_RANGE.  Launch path as the two
+ * calls: runtime-layout kernels (any N <= 64, <= 64 NPC slots, per-car sizes, any beam list), a
+ * resident step server stopped first, not counted by mev_kernel_timing, host pointers staged and
+ * synchronous, device pointers unsynchronised; with leaf_obs the same scratch and chunks
+ * (MEV_LEAF_CHUNK honoured).
+ * Measured (python tools/bench_expand.py -> profiles/expand_sweep.json; mev_evaluate_plans' method):
+ * at 4096 envs x 8 agents x 64 beams, device pointers, C = 4096, every output, medians of five blocks -- the second
+ * level of a tree from a pool, one slot per candidate, costs 21.5 / 36.4 / 66.7 us at T = 2 / 4 / 8 (min-max
+ * 21.5-23.1, 36.2-36.6, 66.7-66.9) against 34.7 / 64.1 / 124.3 us (34.2-36.1, 63.9-64.3, 124.1-124.5) for
+ * mev_evaluate_plans at 2T from the live batch, the only other way there that leaves the batch alone; with leaf_obs
+ * 57.0 / 73.9 / 110.1 us against 74.3 / 109.9 / 183.2 us for mev_evaluate_leaves at 2T.  One-ego traffic (4096 x 1 x
+ * 64, density 0.5): 45.2 / 82.7 / 158.0 us against 81.7 / 157.9 / 311.7 us, with leaf_obs 76.2 / 130.6 / 235.1 us
+ * against 125.6 / 229.8 / 437.0 us.  Every measured shape is below the replay by more than the blocks' spreads (at
+ * the least 13.2 us against 1.9 us); no shape loses.  Keeping the stop states costs -1.1 to 3.9 us per call over
+ * the evaluation call on the same inputs (at most 1.4 us without leaf_obs). */
+typedef struct {
+    mev_evaluate_args eval;    /* exactly as mev_evaluate_plans; every output in it optional        */
+    float* leaf_obs;           /* optional [C][N][obs_dim], defined exactly as mev_evaluate_leaves' */
+    const mev_pool* src;       /* NULL: eval.roots are live envs; else slots of src                 */
+    mev_pool* dst;             /* required                                                          */
+    const int32_t* dst_slots;  /* [C]: slot that receives candidate c's stop state; -1: not stored  */
+    uint64_t counter_offset;   /* Philox: sub-step s uses the handle's counter + counter_offset + (s - 1) */
+} mev_expand_args;
+int mev_expand_plans(mev_handle* h, const mev_expand_args* args);
+
 /* Outputs of the last step / reset, from the handle's own device buffers.
  * Lifetime: after a step that wrote caller-owned output buffers (device
  * pointers in mev_step_args), this call, mev_device_outputs and

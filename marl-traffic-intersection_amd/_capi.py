@@ -50,7 +50,8 @@ EXPORTED = (
     "mev_gather_wait", "mev_output_dlpack", "mev_packed_layout2", "mev_set_gather_format", "mev_lidar_decode_table",
     "mev_unpack_gathered", "mev_add_route", "mev_add_route_n", "mev_set_car_dims", "mev_get_car_dims", "mev_car_dims_active",
     "mev_set_beam_angles", "mev_get_beam_angles", "mev_decode_errors", "mev_step_sequence", "mev_restore_map",
-    "mev_evaluate_plans", "mev_evaluate_leaves",
+    "mev_evaluate_plans", "mev_evaluate_leaves", "mev_pool_create", "mev_pool_destroy", "mev_pool_slots",
+    "mev_pool_capture", "mev_pool_get_state", "mev_expand_plans",
 )
 
 
@@ -103,6 +104,14 @@ class MevEvaluateArgs(ctypes.Structure):  # mev_evaluate_args
 
 class MevLeafArgs(ctypes.Structure):  # mev_leaf_args
     _fields_ = [("eval", MevEvaluateArgs), ("leaf_obs", _vp)]
+
+
+MEV_MAX_POOL_SLOTS = 1 << 20
+
+
+class MevExpandArgs(ctypes.Structure):  # mev_expand_args
+    _fields_ = [("eval", MevEvaluateArgs), ("leaf_obs", _vp), ("src", _vp), ("dst", _vp), ("dst_slots", _vp),
+                ("counter_offset", ctypes.c_uint64)]
 
 
 # outputs of evaluate_plans: (key, dtype, shape of (T, C, N))
@@ -177,6 +186,12 @@ def load_library(variant: str = None):
     L.mev_restore_map.argtypes = [_vp, _vp, _vp, ctypes.c_uint32]
     L.mev_evaluate_plans.argtypes = [_vp, ctypes.POINTER(MevEvaluateArgs)]
     L.mev_evaluate_leaves.argtypes = [_vp, ctypes.POINTER(MevLeafArgs)]
+    L.mev_pool_create.argtypes = [_vp, ctypes.c_int32, ctypes.POINTER(_vp)]
+    L.mev_pool_destroy.argtypes = [_vp]
+    L.mev_pool_slots.argtypes = [_vp, i32p]
+    L.mev_pool_capture.argtypes = [_vp, _vp, _vp, _vp, ctypes.c_int32, ctypes.c_uint32]
+    L.mev_pool_get_state.argtypes = [_vp, _vp, ctypes.c_int32, ctypes.POINTER(MevState), _vp, _vp, _vp]
+    L.mev_expand_plans.argtypes = [_vp, ctypes.POINTER(MevExpandArgs)]
     L.mev_get_outputs.argtypes = [_vp] + [_vp] * 8 + [ctypes.c_uint32]
     L.mev_get_state.argtypes = [_vp, ctypes.POINTER(MevState)]
     L.mev_set_state.argtypes = [_vp, ctypes.POINTER(MevState)]
@@ -602,7 +617,7 @@ class Handle:
 
     def evaluate_plans(self, actions, roots, dt=1.0 / 60.0, gamma: float = 1.0, spawn_route=None,
                        out: Optional[dict] = None, device: bool = False, candidates: Optional[int] = None,
-                       length: Optional[int] = None, flags: int = 0, leaf_obs: bool = False):
+                       length: Optional[int] = None, flags: int = 0, leaf_obs: bool = False, _expand=None):
         """Score candidate plans from the live batch (mev_evaluate_plans); the handle stays as it is.
         actions [T][C][N][2], roots [C] (the live env each candidate starts from), dt a float or T
         floats (always host values), spawn_route optional [T][C].  Returns `returns` [C][N] (the
@@ -667,12 +682,42 @@ class Handle:
         for k, _, _ in _EVAL_OUTS:
             setattr(a, k, _ptr(out.get(k)))
         a.flags = (MEV_DEVICE_PTRS if device else 0) | int(flags)
-        if leaf_obs:
+        if _expand is not None:
+            xa = MevExpandArgs()
+            xa.eval = a
+            xa.leaf_obs = _ptr(out.get("leaf_obs")) if leaf_obs else None
+            xa.src, xa.dst, xa.dst_slots, xa.counter_offset = _expand
+            _check(self._lib.mev_expand_plans(self._h, ctypes.byref(xa)))
+        elif leaf_obs:
             la.leaf_obs = _ptr(out.get("leaf_obs"))
             _check(self._lib.mev_evaluate_leaves(self._h, ctypes.byref(la)))
         else:
             _check(self._lib.mev_evaluate_plans(self._h, ctypes.byref(a)))
         return out
+
+    def pool(self, slots: int) -> "Pool":
+        """A state pool of `slots` slots (mev_pool_create): env states kept on the device outside the
+        live batch, filled by Pool.capture and expand_plans, read by expand_plans(src=pool)."""
+        return Pool(self, slots)
+
+    def expand_plans(self, actions, roots, dst: "Pool", dst_slots, src: Optional["Pool"] = None,
+                     counter_offset: int = 0, leaf_obs: bool = False, dt=1.0 / 60.0, gamma: float = 1.0,
+                     spawn_route=None, out: Optional[dict] = None, device: bool = False,
+                     candidates: Optional[int] = None, length: Optional[int] = None, flags: int = 0):
+        """evaluate_plans (leaf_obs=True: with the leaf observations) whose candidates start from the
+        slots roots[c] of pool `src` (None: from live envs) and whose stop states are stored in the
+        slots dst_slots[c] of pool `dst` (-1: not stored) -- mev_expand_plans.  The Philox spawner of
+        sub-step s uses the handle's counter + counter_offset + (s - 1).  Everything else follows
+        evaluate_plans' conventions; in device mode dst_slots is a device array like roots, and an
+        empty `out` is allowed (the pool is an output)."""
+        if not device:
+            dst_slots = np.ascontiguousarray(dst_slots, np.int32)
+            if dst_slots.shape != np.shape(roots):
+                raise ValueError(f"dst_slots must have roots' shape {np.shape(roots)}, got {dst_slots.shape}")
+        xp = (src._p if src is not None else None, dst._p if dst is not None else None, _ptr(dst_slots),
+              int(counter_offset))
+        return self.evaluate_plans(actions, roots, dt, gamma, spawn_route, out, device, candidates, length, flags,
+                                   leaf_obs, _expand=xp)
 
     # -- multi-GPU gather (mev_comm_*) -------------------------------------
     def comm_init(self, unique_id: bytes, world: int, rank: int, root: int = 0, slots: int = 0):
@@ -934,6 +979,67 @@ class Handle:
         v = ctypes.c_int64()
         _check(self._lib.mev_npc_overflow(self._h, ctypes.byref(v)))
         return v.value
+
+
+class Pool:
+    """A state pool of a Handle (mev_pool_create): `slots` env states on the device outside the live
+    batch.  The handle's close() releases it too; close() after that is a no-op."""
+
+    def __init__(self, handle: "Handle", slots: int):
+        self._handle = handle
+        self._lib = handle._lib
+        p = _vp()
+        _check(self._lib.mev_pool_create(handle._h, int(slots), ctypes.byref(p)))
+        self._ptr = p.value
+        n = ctypes.c_int32()
+        _check(self._lib.mev_pool_slots(self._ptr, ctypes.byref(n)))
+        self.slots = n.value
+
+    @property
+    def _p(self):
+        if not self._ptr or not self._handle._h:
+            raise MevError("the pool (or its handle) is closed")
+        return self._ptr
+
+    def close(self):
+        if getattr(self, "_ptr", None) and self._handle._h:  # (a closed handle has released its pools)
+            self._lib.mev_pool_destroy(self._ptr)
+        self._ptr = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def capture(self, envs, slots, device: bool = False, count: Optional[int] = None):
+        """Copy live env envs[i] into slot slots[i] without stepping (mev_pool_capture)."""
+        if not device:
+            envs = np.ascontiguousarray(envs, np.int32).reshape(-1)
+            slots = np.ascontiguousarray(slots, np.int32).reshape(-1)
+            if envs.shape != slots.shape:
+                raise ValueError(f"envs and slots must have one length, got {envs.size} and {slots.size}")
+        n = int(count) if count is not None else int(getattr(envs, "shape", (0,))[0])
+        _check(self._lib.mev_pool_capture(self._handle._h, self._p, _ptr(envs), _ptr(slots), n,
+                                          MEV_DEVICE_PTRS if device else 0))
+
+    def get_state(self, slots):
+        """Host read-back of the given slots (mev_pool_get_state): (state dict as Handle.get_state with
+        rows = the slots, (ego_dims [n][N][2], npc_dims [n][K][2]), valid [n])."""
+        h = self._handle
+        slots = np.ascontiguousarray(slots, np.int32).reshape(-1)
+        n = int(slots.size)
+        shape = {"ego": (n, h.N), "npc": (n, h.K), "env": (n,)}
+        st, arrays = MevState(), {}
+        for name, dt, per in STATE_FIELDS:
+            a = np.zeros(shape[per], dt)
+            arrays[name] = a
+            setattr(st, name, _ptr(a) if a.size else None)
+        ed, nd = np.zeros((n, h.N, 2), np.float32), np.zeros((n, h.K, 2), np.float32)
+        valid = np.zeros(n, np.uint8)
+        _check(self._lib.mev_pool_get_state(self._p, _ptr(slots), n, ctypes.byref(st), _ptr(ed),
+                                            _ptr(nd) if nd.size else None, _ptr(valid)))
+        return arrays, (ed, nd), valid
 
 
 def car_update(kin, throttle: float, steer: float, dt: float):

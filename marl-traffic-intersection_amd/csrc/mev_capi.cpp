@@ -48,6 +48,14 @@ hipError_t dalloc(T** p, size_t n) {
 
 }  // namespace
 
+// A state pool (mev_pool_create): one device block carved into the arrays of mev::PoolState.
+struct mev_pool {
+    mev_handle* h = nullptr;
+    int32_t slots = 0;
+    uint8_t* block = nullptr;
+    mev::PoolState st{};
+};
+
 struct mev_handle {
     mev_config cfg{};
     int D = 0, lidar_slots = 0, P = 0, nroutes = 0;
@@ -246,6 +254,7 @@ struct mev_handle {
     hipEvent_t serve_ev = nullptr;  // orders the server after the handle's stream
     uint8_t* gs_pin = nullptr;  // pinned staging of mev_get_state
     size_t gs_cap = 0;
+    std::vector<mev_pool*> pools;  // the handle's state pools (mev_pool_create), released with it
     ~mev_handle() {
         if (comm_stream) (void)hipStreamSynchronize(comm_stream);
         free_comm();
@@ -258,6 +267,10 @@ struct mev_handle {
         if (d_snap_stage) (void)hipFree(d_snap_stage);
         if (d_eval) (void)hipFree(d_eval);
         if (d_leaf) (void)hipFree(d_leaf);
+        for (mev_pool* q : pools) {
+            if (q->block) (void)hipFree(q->block);
+            delete q;
+        }
         for (void* p : allocs) (void)hipFree(p);
         if (own_stream) (void)hipStreamDestroy(own_stream);
     }
@@ -891,6 +904,8 @@ int mev_set_car_dims(mev_handle* h, const float* ego_dims, const float* npc_dims
     if (int r_ = serve_stop(h)) return r_;  // (the server holds the stream)
     if (ego_dims) HIP_TRY(hipMemcpyAsync(h->sp.ego_dim, ego_dims, EN * 2 * sizeof(float), hipMemcpyHostToDevice, h->stream));
     if (npc_dims && EK) HIP_TRY(hipMemcpyAsync(h->sp.npc_dim, npc_dims, EK * 2 * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    // the pools' slots were stored under the sizes' regime so far: none is valid under the next
+    for (mev_pool* q : h->pools) HIP_TRY(hipMemsetAsync(q->st.valid, 0, size_t(q->slots), h->stream));
     // whether any car differs from 54 x 24: the arrays given, and the device's for the other
     std::vector<float> e(ego_dims ? 0 : EN * 2), k(npc_dims ? 0 : EK * 2);
     if (!e.empty()) HIP_TRY(hipMemcpyAsync(e.data(), h->sp.ego_dim, e.size() * sizeof(float), hipMemcpyDeviceToHost, h->stream));
@@ -1599,26 +1614,62 @@ int mev_step_sequence(mev_handle* h, const mev_sequence_args* sa) {
 // LiDAR hand-off lives in a per-handle scratch that only grows, to kLeafHandCap at the most: a call
 // with more candidates than the cap holds (or than MEV_LEAF_CHUNK) goes through in chunks.
 constexpr size_t kLeafHandCap = size_t(64) << 20;
-static int evaluate(mev_handle* h, const mev_evaluate_args* ea, float* leaf_obs, bool leaves) {
-    const char* fn = leaves ? "mev_evaluate_leaves" : "mev_evaluate_plans";
+// xp: mev_expand_plans' additions (null: the two evaluation calls) -- the candidates' roots are slots
+// of xp->src when that is set, and their stop states go to slots xp->dst_slots of xp->dst.
+static int evaluate(mev_handle* h, const mev_evaluate_args* ea, float* leaf_obs, bool leaves,
+                    const mev_expand_args* xp = nullptr) {
+    const char* fn = xp ? "mev_expand_plans" : leaves ? "mev_evaluate_leaves" : "mev_evaluate_plans";
+    if (xp) {
+        if (!xp->dst || !xp->dst_slots) return fail(MEV_E_INVALID, "dst and dst_slots required");
+        if (xp->dst->h != h || (xp->src && xp->src->h != h)) return fail(MEV_E_INVALID, "the pool belongs to another handle");
+    }
     if (!ea->actions || !ea->roots) return fail(MEV_E_INVALID, "actions and roots required");
     if (ea->candidates < 1 || ea->candidates > MEV_MAX_CANDIDATES)
         return fail(MEV_E_INVALID, "candidates must be in 1.." + std::to_string(MEV_MAX_CANDIDATES));
     if (ea->length < 1 || ea->length > MEV_MAX_REPEAT)
         return fail(MEV_E_INVALID, "length must be in 1.." + std::to_string(MEV_MAX_REPEAT));
     if (ea->flags & ~uint32_t(MEV_DEVICE_PTRS)) return fail(MEV_E_INVALID, std::string(fn) + " takes MEV_DEVICE_PTRS only");
-    if (!leaves && !ea->returns && !ea->reward_seq && !ea->done_seq && !ea->status_seq && !ea->substeps &&
+    if (!xp && !leaves && !ea->returns && !ea->reward_seq && !ea->done_seq && !ea->status_seq && !ea->substeps &&
         !ea->terminated && !ea->truncated)
         return fail(MEV_E_INVALID, "mev_evaluate_plans needs at least one output");
     const bool dev = (ea->flags & MEV_DEVICE_PTRS) != 0;
     const size_t C = size_t(ea->candidates), T = size_t(ea->length), N = size_t(h->cfg.num_agents), CN = C * N;
+    const int32_t n_roots = xp && xp->src ? xp->src->slots : h->cfg.num_envs;  // where a root may point
     if (!dev)
         for (size_t c = 0; c < C; ++c)
-            if (ea->roots[c] < 0 || ea->roots[c] >= h->cfg.num_envs)
+            if (ea->roots[c] < 0 || ea->roots[c] >= n_roots)
                 return fail(MEV_E_RANGE, "roots[" + std::to_string(c) + "] = " + std::to_string(ea->roots[c]) +
-                                             " is outside [0, " + std::to_string(h->cfg.num_envs) + ")");
+                                             " is outside [0, " + std::to_string(n_roots) + ")");
+    if (xp && !dev) {
+        // the slots that receive a state: in range, none twice, and in the roots' own pool none a root
+        // (bitmaps over the pool's slots)
+        const size_t S = size_t(xp->dst->slots);
+        std::vector<bool> taken(S, false);
+        for (size_t c = 0; c < C; ++c) {
+            const int32_t d = xp->dst_slots[c];
+            if (d < -1 || d >= xp->dst->slots)
+                return fail(MEV_E_RANGE, "dst_slots[" + std::to_string(c) + "] = " + std::to_string(d) +
+                                             " is outside [-1, " + std::to_string(S) + ")");
+            if (d < 0) continue;
+            if (taken[size_t(d)]) return fail(MEV_E_INVALID, "dst_slots names slot " + std::to_string(d) + " twice");
+            taken[size_t(d)] = true;
+        }
+        if (xp->src == xp->dst)
+            for (size_t c = 0; c < C; ++c)
+                if (taken[size_t(ea->roots[c])])
+                    return fail(MEV_E_INVALID, "slot " + std::to_string(ea->roots[c]) + " is a root and in dst_slots");
+    }
     HIP_TRY(hipSetDevice(h->cfg.device));
     if (int r = serve_stop(h)) return r;  // (the server holds the stream)
+    if (xp && xp->src && !dev) {  // a root slot nothing was stored in: as a root out of range
+        std::vector<uint8_t> valid(size_t(xp->src->slots));
+        HIP_TRY(hipMemcpyAsync(valid.data(), xp->src->st.valid, valid.size(), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        for (size_t c = 0; c < C; ++c)
+            if (!valid[size_t(ea->roots[c])])
+                return fail(MEV_E_RANGE, "roots[" + std::to_string(c) + "] = " + std::to_string(ea->roots[c]) +
+                                             ": nothing valid is stored in that slot");
+    }
     mev::SeqRows rows{};
     for (size_t s = 0; s < T; ++s) {  // read from the caller's memory now; by value with the kernel's arguments
         rows.dt[s] = ea->dt_seq ? ea->dt_seq[s] : ea->dt;
@@ -1627,9 +1678,10 @@ static int evaluate(mev_handle* h, const mev_evaluate_args* ea, float* leaf_obs,
     mev::StepInputs in{};
     in.dt = rows.dt[0];
     in.spawn_prob = rows.spawn_prob[0];
-    in.rng_counter = h->rng_counter;  // sub-step s: + s; the handle's counter stays
+    in.rng_counter = h->rng_counter + (xp ? xp->counter_offset : 0);  // sub-step s: + s; the handle's counter stays
     mev::EvalOutputs eo{ea->gamma, ea->returns, ea->substeps, ea->terminated, ea->truncated};
     const int32_t* d_roots = ea->roots;
+    const int32_t* d_dst = xp ? xp->dst_slots : nullptr;
     const size_t obs_bytes = leaves ? CN * size_t(h->sp.D) * sizeof(float) : 0;
     float* d_leaf_obs = leaf_obs;
     int chunk = 0;
@@ -1673,6 +1725,7 @@ static int evaluate(mev_handle* h, const mev_evaluate_args* ea, float* leaf_obs,
         const size_t o_sub = take(ea->substeps != nullptr, C * sizeof(int32_t));
         const size_t o_term = take(ea->terminated != nullptr, C), o_trunc = take(ea->truncated != nullptr, C);
         const size_t o_obs = take(leaves, obs_bytes);
+        const size_t o_dst = take(xp != nullptr, C * sizeof(int32_t));
         if (off > h->eval_cap) {
             HIP_TRY(hipStreamSynchronize(h->stream));
             if (h->d_eval) (void)hipFree(h->d_eval);
@@ -1699,8 +1752,15 @@ static int evaluate(mev_handle* h, const mev_evaluate_args* ea, float* leaf_obs,
         if (ea->terminated) eo.terminated = b + o_term;
         if (ea->truncated) eo.truncated = b + o_trunc;
         if (leaves) d_leaf_obs = reinterpret_cast<float*>(b + o_obs);
+        if (xp) {
+            HIP_TRY(hipMemcpyAsync(b + o_dst, xp->dst_slots, C * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+            d_dst = reinterpret_cast<const int32_t*>(b + o_dst);
+        }
     }
-    if (leaves)
+    if (xp)
+        HIP_TRY(mev::launch_expand(h->sp, in, int(C), d_roots, rows, int(T), eo, xp->src ? &xp->src->st : nullptr,
+                                   xp->dst->st, d_dst, leaves ? d_leaf_obs : nullptr, h->d_leaf, chunk, h->stream));
+    else if (leaves)
         HIP_TRY(mev::launch_evaluate_leaves(h->sp, in, int(C), d_roots, rows, int(T), eo, d_leaf_obs, h->d_leaf, chunk,
                                             h->stream));
     else
@@ -1733,6 +1793,187 @@ int mev_evaluate_leaves(mev_handle* h, const mev_leaf_args* la) {
     if (!h || !la) return fail(MEV_E_INVALID, "null argument");
     if (!la->leaf_obs) return fail(MEV_E_INVALID, "leaf_obs required");
     return evaluate(h, &la->eval, la->leaf_obs, true);
+}
+
+// ---- state pools (include/marlenv.h): env states outside the live batch, in the handle's own SoA
+// layout over slots (mev::PoolState), and mev_expand_plans, the plan evaluation that reads and
+// fills them.
+namespace {
+// one device block of `slots` states for h's shape, every array at a 256-byte boundary, all zero
+// (the valid bytes with it); *block is the allocation
+hipError_t pool_alloc(const mev_handle* h, int32_t slots, uint8_t** block, mev::PoolState* st) {
+    const size_t S = size_t(slots), SN = S * size_t(h->cfg.num_agents), SK = S * size_t(h->cfg.max_npcs);
+    auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
+    const size_t es = al(SN * 4) / 4, ns = al(SK * 4) / 4;  // the field strides, in elements
+    size_t off = 0;
+    auto take = [&off, &al](size_t bytes) {
+        const size_t at = off;
+        off += al(bytes ? bytes : 1);
+        return at;
+    };
+    const size_t o_ego = take(es * 4 * mev::EF_COUNT), o_npc = take(ns * 4 * mev::NF_COUNT);
+    const size_t o_ed = take(SN * 8), o_nd = take(SK * 8), o_nc = take(S * 4), o_sc = take(S * 4);
+    const size_t o_ea = take(SN), o_na = take(SK), o_v = take(S);
+    uint8_t* b = nullptr;
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&b), off);
+    if (e != hipSuccess) return e;
+    e = hipMemsetAsync(b, 0, off, h->stream);
+    if (e != hipSuccess) {
+        (void)hipFree(b);
+        return e;
+    }
+    *block = b;
+    *st = mev::PoolState{reinterpret_cast<float*>(b + o_ego), int64_t(es), reinterpret_cast<float*>(b + o_npc),
+                         int64_t(ns), b + o_ea, b + o_na, reinterpret_cast<int32_t*>(b + o_nc),
+                         reinterpret_cast<int32_t*>(b + o_sc), reinterpret_cast<float*>(b + o_ed),
+                         reinterpret_cast<float*>(b + o_nd), b + o_v, slots};
+    return hipSuccess;
+}
+}  // namespace
+
+int mev_pool_create(mev_handle* h, int32_t slots, mev_pool** out) {
+    if (!h || !out) return fail(MEV_E_INVALID, "null argument");
+    *out = nullptr;
+    if (slots < 1 || slots > MEV_MAX_POOL_SLOTS)
+        return fail(MEV_E_INVALID, "slots must be in 1.." + std::to_string(MEV_MAX_POOL_SLOTS));
+    HIP_TRY(hipSetDevice(h->cfg.device));
+    if (int r = serve_stop(h)) return r;  // (the server holds the stream)
+    mev_pool* q = new mev_pool;
+    q->h = h;
+    q->slots = slots;
+    const hipError_t err = pool_alloc(h, slots, &q->block, &q->st);
+    if (err != hipSuccess) {
+        delete q;
+        (void)hipGetLastError();
+        return fail(MEV_E_NOMEM, std::string("device allocation failed: ") + hipGetErrorString(err));
+    }
+    h->pools.push_back(q);
+    *out = q;
+    return MEV_OK;
+}
+
+int mev_pool_destroy(mev_pool* pool) {
+    if (!pool) return MEV_OK;
+    mev_handle* h = pool->h;
+    (void)hipSetDevice(h->cfg.device);
+    (void)serve_stop(h);
+    (void)hipStreamSynchronize(h->stream);  // (calls in flight may still read or fill it)
+    for (size_t i = 0; i < h->pools.size(); ++i)
+        if (h->pools[i] == pool) {
+            h->pools.erase(h->pools.begin() + long(i));
+            break;
+        }
+    if (pool->block) (void)hipFree(pool->block);
+    delete pool;
+    return MEV_OK;
+}
+
+int mev_pool_slots(const mev_pool* pool, int32_t* slots) {
+    if (!pool || !slots) return fail(MEV_E_INVALID, "null argument");
+    *slots = pool->slots;
+    return MEV_OK;
+}
+
+// host index arrays of a pool call into the handle's staging block (grown as mev_evaluate_plans grows it)
+static int pool_stage(mev_handle* h, const int32_t* a, const int32_t* b, size_t count, const int32_t** da,
+                      const int32_t** db) {
+    const size_t each = (count * sizeof(int32_t) + 255) & ~size_t(255), need = 2 * each;
+    if (need > h->eval_cap) {
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        if (h->d_eval) (void)hipFree(h->d_eval);
+        h->d_eval = nullptr;
+        h->eval_cap = 0;
+        const hipError_t err = hipMalloc(reinterpret_cast<void**>(&h->d_eval), need);
+        if (err != hipSuccess) return fail(MEV_E_NOMEM, std::string("device allocation failed: ") + hipGetErrorString(err));
+        h->eval_cap = need;
+    }
+    HIP_TRY(hipMemcpyAsync(h->d_eval, a, count * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    *da = reinterpret_cast<const int32_t*>(h->d_eval);
+    if (b) {
+        HIP_TRY(hipMemcpyAsync(h->d_eval + each, b, count * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+        *db = reinterpret_cast<const int32_t*>(h->d_eval + each);
+    }
+    return MEV_OK;
+}
+
+int mev_pool_capture(mev_handle* h, mev_pool* pool, const int32_t* envs, const int32_t* slots, int32_t count,
+                     uint32_t flags) {
+    if (!h || !pool || !envs || !slots) return fail(MEV_E_INVALID, "null argument");
+    if (pool->h != h) return fail(MEV_E_INVALID, "the pool belongs to another handle");
+    if (count < 1 || count > MEV_MAX_POOL_SLOTS)
+        return fail(MEV_E_INVALID, "count must be in 1.." + std::to_string(MEV_MAX_POOL_SLOTS));
+    if (flags & ~uint32_t(MEV_DEVICE_PTRS)) return fail(MEV_E_INVALID, "mev_pool_capture takes MEV_DEVICE_PTRS only");
+    const bool dev = (flags & MEV_DEVICE_PTRS) != 0;
+    if (!dev)
+        for (int32_t i = 0; i < count; ++i) {
+            if (envs[i] < 0 || envs[i] >= h->cfg.num_envs)
+                return fail(MEV_E_RANGE, "envs[" + std::to_string(i) + "] = " + std::to_string(envs[i]) + " is outside [0, " +
+                                             std::to_string(h->cfg.num_envs) + ")");
+            if (slots[i] < 0 || slots[i] >= pool->slots)
+                return fail(MEV_E_RANGE, "slots[" + std::to_string(i) + "] = " + std::to_string(slots[i]) + " is outside [0, " +
+                                             std::to_string(pool->slots) + ")");
+        }
+    HIP_TRY(hipSetDevice(h->cfg.device));
+    if (int r = serve_stop(h)) return r;  // (the server holds the stream)
+    const int32_t *d_envs = envs, *d_slots = slots;
+    if (!dev)
+        if (int r = pool_stage(h, envs, slots, size_t(count), &d_envs, &d_slots)) return r;
+    HIP_TRY(mev::launch_pool_copy(h->sp, mev::pool_of_live(h->sp), pool->st, d_envs, d_slots, count, h->stream));
+    if (!dev) HIP_TRY(hipStreamSynchronize(h->stream));
+    return MEV_OK;
+}
+
+int mev_pool_get_state(mev_pool* pool, const int32_t* slots, int32_t count, const mev_state* s, float* ego_dims,
+                       float* npc_dims, uint8_t* valid) {
+    if (!pool || !slots || !s) return fail(MEV_E_INVALID, "null argument");
+    if (count < 1 || count > MEV_MAX_POOL_SLOTS)
+        return fail(MEV_E_INVALID, "count must be in 1.." + std::to_string(MEV_MAX_POOL_SLOTS));
+    for (int32_t i = 0; i < count; ++i)
+        if (slots[i] < 0 || slots[i] >= pool->slots)
+            return fail(MEV_E_RANGE, "slots[" + std::to_string(i) + "] = " + std::to_string(slots[i]) + " is outside [0, " +
+                                         std::to_string(pool->slots) + ")");
+    mev_handle* h = pool->h;
+    HIP_TRY(hipSetDevice(h->cfg.device));
+    if (int r = serve_stop(h)) return r;  // (the server holds the stream)
+    // the asked slots gathered into a pool of `count` slots, row i = slot slots[i], then read field by field
+    const int32_t *d_slots = nullptr, *unused = nullptr;
+    if (int r = pool_stage(h, slots, nullptr, size_t(count), &d_slots, &unused)) return r;
+    uint8_t* block = nullptr;
+    mev::PoolState g{};
+    const hipError_t err = pool_alloc(h, count, &block, &g);
+    if (err != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(MEV_E_NOMEM, std::string("device allocation failed: ") + hipGetErrorString(err));
+    }
+    const size_t S = size_t(count), SN = S * size_t(h->cfg.num_agents), SK = S * size_t(h->cfg.max_npcs);
+    hipError_t e = mev::launch_pool_copy(h->sp, pool->st, g, d_slots, nullptr, count, h->stream);
+    auto back = [&](void* dst, const void* src, size_t bytes) {
+        if (e == hipSuccess && dst && bytes) e = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream);
+    };
+    void* const ego4[mev::EF_COUNT] = {s->x, s->y, s->v, s->heading, s->acc, s->steering, s->prev_dist,
+                                      s->prev_a0, s->prev_a1, s->spawn_x, s->spawn_y, s->spawn_v,
+                                      s->spawn_heading, s->path_index, s->route, s->intention};
+    void* const npc4[mev::NF_COUNT] = {s->npc_x, s->npc_y, s->npc_v, s->npc_heading, s->npc_acc,
+                                      s->npc_steering, s->npc_path_index, s->npc_route, s->npc_intention};
+    for (int k = 0; k < mev::EF_COUNT; ++k) back(ego4[k], g.ego + g.ego_stride * k, SN * 4);
+    for (int k = 0; k < mev::NF_COUNT; ++k) back(npc4[k], g.npc + g.npc_stride * k, SK * 4);
+    back(s->alive, g.ego_alive, SN);
+    back(s->npc_alive, g.npc_alive, SK);
+    back(s->npc_count, g.npc_count, S * 4);
+    back(s->step_count, g.step_count, S * 4);
+    back(ego_dims, g.ego_dim, SN * 8);
+    back(npc_dims, g.npc_dim, SK * 8);
+    back(valid, g.valid, S);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    else (void)hipStreamSynchronize(h->stream);
+    (void)hipFree(block);
+    if (e != hipSuccess) return fail(MEV_E_HIP, std::string("mev_pool_get_state: ") + hipGetErrorString(e));
+    return MEV_OK;
+}
+
+int mev_expand_plans(mev_handle* h, const mev_expand_args* xa) {
+    if (!h || !xa) return fail(MEV_E_INVALID, "null argument");
+    return evaluate(h, &xa->eval, xa->leaf_obs, xa->leaf_obs != nullptr, xa);
 }
 
 static int sync_internal(mev_handle* h);  // below, with mev_device_outputs

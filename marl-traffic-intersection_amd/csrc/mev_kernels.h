@@ -270,6 +270,46 @@ size_t leaf_hand_bytes(const SimParams& p, int chunk);
 hipError_t launch_evaluate_leaves(const SimParams& p, const StepInputs& in, int C, const int32_t* roots,
                                   const SeqRows& rows, int n, const EvalOutputs& outs, float* leaf_obs, uint8_t* hand,
                                   int chunk, hipStream_t s);
+// A state pool (mev_pool_create): `slots` complete env states outside the live batch, structure of
+// arrays over slots in the handle's own field layout -- slot d's agent i at d * N + i, its NPC
+// slot k at d * K + k -- so a SimParams copy whose state block points here (pool_view) lets every
+// kernel that loads an env's state load a slot's.  No outputs, LiDAR hand-off or pending-reset
+// flag; per slot a valid byte (0 until a state was stored; cleared by mev_set_car_dims).
+struct PoolState {
+    float* ego;           // [EF_COUNT][ego_stride]: the 4-byte ego fields, EgoField order
+    int64_t ego_stride;   // >= slots * N
+    float* npc;           // [NF_COUNT][npc_stride]: the 4-byte NPC fields, NpcField order
+    int64_t npc_stride;   // >= slots * K
+    uint8_t* ego_alive;   // [slots * N]
+    uint8_t* npc_alive;   // [slots * K]
+    int32_t* npc_count;   // [slots]
+    int32_t* step_count;  // [slots]
+    float* ego_dim;       // [slots * N][2]
+    float* npc_dim;       // [slots * K][2]
+    uint8_t* valid;       // [slots]
+    int32_t slots;
+};
+// the live batch of p as a PoolState of p.E slots without valid bytes (every env counts as valid)
+PoolState pool_of_live(const SimParams& p);
+// p with its state block replaced by the pool's (E = slots; pending_reset, which the plan
+// evaluation reads and ignores, points at the valid bytes): what k_cars_repeat<EVAL> loads from
+SimParams pool_view(const SimParams& p, const PoolState& pool);
+// Gather copy between two state blocks of one shape (mev_pool_capture, mev_pool_get_state): entry
+// i copies slot from[i] of src into slot to[i] of dst (from / to null: i itself), every field of
+// all K NPC slots included; dst's valid byte becomes src's, or 1 when src has none.  A pair with
+// either index out of range is skipped: nothing is accessed outside the blocks.
+hipError_t launch_pool_copy(const SimParams& p, const PoolState& src, const PoolState& dst, const int32_t* from,
+                            const int32_t* to, int count, hipStream_t s);
+// Plan expansion (mev_expand_plans): launch_evaluate (leaf_obs null) or launch_evaluate_leaves,
+// bit for bit, with two additions (k_cars_repeat<..., KEEP = true>).  src (nullable): candidate c
+// starts from slot roots[c] of that pool instead of live env roots[c]; a root out of range or a
+// slot whose valid byte is 0 is a candidate without a root.  dst: the sub-step a candidate that
+// ran stops at stores its whole post-step state -- what the plan rollout would write back to an
+// env -- into slot dst_slots[c] of dst and sets the slot's valid byte; an index outside [0,
+// dst.slots) stores nothing.  src and dst may be one pool when no dst slot of the call is a root.
+hipError_t launch_expand(const SimParams& p, const StepInputs& in, int C, const int32_t* roots, const SeqRows& rows,
+                         int n, const EvalOutputs& outs, const PoolState* src, const PoolState& dst,
+                         const int32_t* dst_slots, float* leaf_obs, uint8_t* hand, int chunk, hipStream_t s);
 hipError_t launch_reset(const SimParams& p, const uint8_t* env_mask, const Outputs& out, hipStream_t s,
                         uint64_t rng_counter);
 // recompute the observation rows from the current state with LiDAR = max (after set_state)

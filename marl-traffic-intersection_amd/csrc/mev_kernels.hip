@@ -1748,7 +1748,8 @@ __device__ __forceinline__ void ego_phase1(const SimParams& p, const StepInputs&
 // env's.  The first sub-step loads the state of the live env src_e (the env's counters, every ego
 // field, the car sizes, the NPC slots) and never resets it; the actions, the spawn decision and
 // everything written are the candidate's (index e).  No LiDAR follows, so the part ends after the
-// respawns: no obstacle table, no candidate masks.
+// respawns: no obstacle table, no candidate masks.  (mev_expand_plans, KEEP: p may be a state pool's
+// view -- pool_view -- and src_e a slot of it; nothing here tells the two apart.)
 // LEAF (mev_evaluate_leaves, k_cars_repeat<TRAFFIC, true, true, true>): EVAL whose candidates are
 // cast afterwards, so the part runs on and builds the obstacle table and candidate masks in LDS
 // every sub-step, as the plan rollout does (cars_post knows the stop).
@@ -2626,29 +2627,119 @@ struct LeafArgs {
     LeafHand lf;
 };
 static_assert(sizeof(LeafArgs) <= 4096, "the kernel argument segment");
+// KEEP (mev_expand_plans): EVAL or LEAF whose candidates may start from a slot of a state pool and
+// whose stop state is kept in one.  The SimParams of the arguments is the source's view (pool_view:
+// its state block, E = its slots), so the first sub-step's loads need nothing new; src_valid
+// (null: live envs) holds the source slots' valid bytes, read next to roots[c]: a root whose byte
+// is 0 is a candidate without a root.  The sub-step a candidate stops at stores, after the
+// candidate's rows and outputs, the state the plan rollout would write back to an env -- every ego
+// field, alive and the sizes from the car LDS (lane = agent), the NPC survivors with their sizes
+// from the NPC LDS (lane = slot, npc_writeback's order), the count, the step counter, and last the
+// valid byte -- into slot dst_slots[c] of dst; an index outside [0, dst.slots) stores nothing.  The
+// argument struct begins with EvalArgs (KeepArgs) or LeafArgs (KeepLeafArgs).
+struct KeepOuts {
+    PoolState dst;
+    const int32_t* dst_slots;  // [C]
+    const uint8_t* src_valid;  // [p.E] (nullable)
+};
+struct KeepArgs {
+    EvalArgs e;
+    KeepOuts k;
+};
+struct KeepLeafArgs {
+    LeafArgs l;
+    KeepOuts k;
+};
+static_assert(sizeof(KeepLeafArgs) <= 4096 && sizeof(KeepArgs) <= 4096, "the kernel argument segment");
+// KEEP: candidate c's stop state into slot dst_slots[c] of k.dst, by every lane of the wave (c, the
+// slot and the root src are wave-uniform).  The values are taken where the next sub-step would read
+// them: cars_pre's respawns were the last writes of the car LDS' state fields (cars_post only reads
+// them), the fields no step without a reset changes still hold the root's values, the NPC phase
+// left its survivors as the prefix of nl, the counters are in cx.  Without traffic no NPC phase
+// runs and the plan rollout leaves the env's NPC slots alone: the root's live prefix is copied.
+template <bool TRAFFIC>
+__device__ __forceinline__ void keep_state(const KeepOuts& k, const SimParams& p, const int c, const int src,
+                                           const CarsLDS& el, const NpcLDS* nl, const CarsCtx& cx, const int tid) {
+    const int d = __builtin_amdgcn_readfirstlane(k.dst_slots[c]);
+    const PoolState& P = k.dst;
+    if ((unsigned)d >= (unsigned)P.slots) return;
+    const int N = p.N, K = p.K;
+    if (tid < N) {
+        const uint32_t g = (uint32_t)(d * N + tid);
+        auto F = [&](int f) { return gmem(P.ego + P.ego_stride * f); };
+        auto I = [&](int f) { return gmem(reinterpret_cast<int32_t*>(P.ego + P.ego_stride * f)); };
+        F(EF_X)[g] = el.x[tid]; F(EF_Y)[g] = el.y[tid]; F(EF_V)[g] = el.v[tid]; F(EF_H)[g] = el.h[tid];
+        F(EF_ACC)[g] = el.acc[tid]; F(EF_STEER)[g] = el.steer[tid]; F(EF_PREV_DIST)[g] = el.prev_dist[tid];
+        F(EF_PA0)[g] = el.pa0[tid]; F(EF_PA1)[g] = el.pa1[tid];
+        F(EF_SX)[g] = el.sx[tid]; F(EF_SY)[g] = el.sy[tid]; F(EF_SV)[g] = el.sv[tid]; F(EF_SH)[g] = el.sh[tid];
+        I(EF_PIDX)[g] = el.pidx[tid]; I(EF_ROUTE)[g] = el.route[tid]; I(EF_INTENT)[g] = el.intent[tid];
+        gmem(P.ego_alive)[g] = el.alive[tid];
+        gmem(P.ego_dim)[2 * g] = el.len[tid];
+        gmem(P.ego_dim)[2 * g + 1] = el.wid[tid];
+    }
+    int cnt = cx.ncnt;
+    if constexpr (!TRAFFIC) cnt = __builtin_amdgcn_readfirstlane(gmem(p.npc.count)[src]);
+    if (tid < cnt && tid < K) {
+        const uint32_t g = (uint32_t)(d * K + tid);
+        auto F = [&](int f) { return gmem(P.npc + P.npc_stride * f); };
+        auto I = [&](int f) { return gmem(reinterpret_cast<int32_t*>(P.npc + P.npc_stride * f)); };
+        if constexpr (TRAFFIC) {
+            F(NF_X)[g] = nl->x[tid]; F(NF_Y)[g] = nl->y[tid]; F(NF_V)[g] = nl->v[tid]; F(NF_H)[g] = nl->h[tid];
+            F(NF_ACC)[g] = nl->acc[tid]; F(NF_STEER)[g] = nl->steer[tid]; I(NF_PIDX)[g] = nl->pidx[tid];
+            I(NF_ROUTE)[g] = nl->route[tid]; I(NF_INTENT)[g] = nl->intent[tid];
+            gmem(P.npc_alive)[g] = 1;
+            gmem(P.npc_dim)[2 * g] = nl->len[tid];
+            gmem(P.npc_dim)[2 * g + 1] = nl->wid[tid];
+        } else {
+            const uint32_t r = (uint32_t)(src * K + tid);
+            for (int f = 0; f < NF_PIDX; ++f) F(f)[g] = npcf(p, f)[r];
+            for (int f = NF_PIDX; f < NF_COUNT; ++f) I(f)[g] = npci(p, f)[r];
+            gmem(P.npc_alive)[g] = gmem(p.npc.alive)[r];
+            gmem(P.npc_dim)[2 * g] = gmem(p.npc_dim)[2 * r];
+            gmem(P.npc_dim)[2 * g + 1] = gmem(p.npc_dim)[2 * r + 1];
+        }
+    }
+    if (tid == 0) {
+        gmem(P.npc_count)[d] = cnt;
+        gmem(P.step_count)[d] = cx.step_no;
+        gmem(P.valid)[d] = 1;
+    }
+}
 // (four waves per SIMD, as k_step: 4096 envs are one round of single-wave workgroups on 256 CUs;
 // with the NPC phase 128 VGPRs would spill to scratch: two)
-template <bool TRAFFIC, bool SEQ = false, bool EVAL = false, bool LEAF = false>
+template <bool TRAFFIC, bool SEQ = false, bool EVAL = false, bool LEAF = false, bool KEEP = false>
 __global__ __launch_bounds__(WAVE, TRAFFIC ? 2 : 4) void k_cars_repeat(
     typename std::conditional<
-        LEAF, LeafArgs,
-        typename std::conditional<EVAL, EvalArgs, typename std::conditional<SEQ, SeqArgs, RepeatArgs>::type>::type>::type
+        KEEP, typename std::conditional<LEAF, KeepLeafArgs, KeepArgs>::type,
+        typename std::conditional<
+            LEAF, LeafArgs,
+            typename std::conditional<EVAL, EvalArgs,
+                                      typename std::conditional<SEQ, SeqArgs, RepeatArgs>::type>::type>::type>::type
         args) {
     static_assert(!EVAL || SEQ, "plan evaluation: the plan rollout's loop");
     static_assert(!LEAF || EVAL, "leaf observations: a plan evaluation");
+    static_assert(!KEEP || EVAL, "kept stop states: a plan evaluation");
     extern __shared__ __align__(16) unsigned char cars_lds[];
     __shared__ typename std::conditional<TRAFFIC, NpcLDS, char>::type nl_storage;
     NpcLDS* nl = nullptr;
     if constexpr (TRAFFIC) nl = &nl_storage;
     int repeat;
-    if constexpr (LEAF) repeat = args.e.s.r.repeat;
+    if constexpr (KEEP) repeat = reinterpret_cast<const RepeatArgs*>(&args)->repeat;
+    else if constexpr (LEAF) repeat = args.e.s.r.repeat;
     else if constexpr (EVAL) repeat = args.s.r.repeat;
     else if constexpr (SEQ) repeat = args.r.repeat;
     else repeat = args.repeat;
     RepCarry rc{0, repeat, 0, 0, false, 0.0f, 0, 0, nullptr, 1.0f, 0.0f, 1.0f};
     int src = 0;       // EVAL: the candidate's root (wave-uniform)
     bool bad = false;  // EVAL: a root outside [0, E): no sub-step runs
-    if constexpr (LEAF) {
+    if constexpr (KEEP) {
+        const EvalArgs& ea = *reinterpret_cast<const EvalArgs*>(&args);
+        const int c = ea.s.r.e_begin + xcd_env((int)blockIdx.x, (int)gridDim.x);  // (without LEAF: e_begin = 0)
+        src = __builtin_amdgcn_readfirstlane(ea.ev.roots[c]);
+        bad = (unsigned)src >= (unsigned)ea.s.r.p.E;
+        // (KEEP: or a source slot nothing was stored in)
+        if (!bad && args.k.src_valid) bad = __builtin_amdgcn_readfirstlane((int)args.k.src_valid[src]) == 0;
+    } else if constexpr (LEAF) {
         const int c = args.e.s.r.e_begin + xcd_env((int)blockIdx.x, (int)gridDim.x);
         src = __builtin_amdgcn_readfirstlane(args.e.ev.roots[c]);
         bad = (unsigned)src >= (unsigned)args.e.s.r.p.E;
@@ -2726,6 +2817,10 @@ __global__ __launch_bounds__(WAVE, TRAFFIC ? 2 : 4) void k_cars_repeat(
                         if (ev.substeps) gmem(ev.substeps)[e] = s + 1;
                         if (ev.term) gmem(ev.term)[e] = cx.term;
                         if (ev.trunc) gmem(ev.trunc)[e] = cx.trunc;
+                    }
+                    if constexpr (KEEP) {
+                        using KA = typename std::conditional<LEAF, KeepLeafArgs, KeepArgs>::type;
+                        keep_state<TRAFFIC>(reinterpret_cast<const KA*>(&a)->k, p, e, src, el, nl, cx, tid);
                     }
                 }
             }
@@ -4209,6 +4304,130 @@ hipError_t launch_evaluate_leaves(const SimParams& p, const StepInputs& in, int 
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
+}
+
+PoolState pool_of_live(const SimParams& p) {
+    return PoolState{p.ego.x, p.ego.stride, p.npc.x, p.npc.stride, p.ego.alive, p.npc.alive, p.npc.count,
+                     p.step_count, p.ego_dim, p.npc_dim, nullptr, p.E};
+}
+
+SimParams pool_view(const SimParams& p, const PoolState& pool) {
+    SimParams q = p;
+    q.E = pool.slots;
+    float** ef[] = {&q.ego.x, &q.ego.y, &q.ego.v, &q.ego.h, &q.ego.acc, &q.ego.steer, &q.ego.prev_dist,
+                    &q.ego.pa0, &q.ego.pa1, &q.ego.sx, &q.ego.sy, &q.ego.sv, &q.ego.sh};
+    for (int k = 0; k < EF_PIDX; ++k) *ef[k] = pool.ego + pool.ego_stride * k;
+    q.ego.pidx = reinterpret_cast<int32_t*>(pool.ego + pool.ego_stride * EF_PIDX);
+    q.ego.route = reinterpret_cast<int32_t*>(pool.ego + pool.ego_stride * EF_ROUTE);
+    q.ego.intent = reinterpret_cast<int32_t*>(pool.ego + pool.ego_stride * EF_INTENT);
+    q.ego.alive = pool.ego_alive;
+    q.ego.stride = pool.ego_stride;
+    float** nf[] = {&q.npc.x, &q.npc.y, &q.npc.v, &q.npc.h, &q.npc.acc, &q.npc.steer};
+    for (int k = 0; k < NF_PIDX; ++k) *nf[k] = pool.npc + pool.npc_stride * k;
+    q.npc.pidx = reinterpret_cast<int32_t*>(pool.npc + pool.npc_stride * NF_PIDX);
+    q.npc.route = reinterpret_cast<int32_t*>(pool.npc + pool.npc_stride * NF_ROUTE);
+    q.npc.intent = reinterpret_cast<int32_t*>(pool.npc + pool.npc_stride * NF_INTENT);
+    q.npc.alive = pool.npc_alive;
+    q.npc.count = pool.npc_count;
+    q.npc.stride = pool.npc_stride;
+    q.step_count = pool.step_count;
+    q.pending_reset = pool.valid;  // (read and ignored by the plan evaluation; never written)
+    q.ego_dim = pool.ego_dim;
+    q.npc_dim = pool.npc_dim;
+    // nothing of an env's own outside the state block belongs to a slot
+    q.ob_box = nullptr;
+    q.ob_cand = nullptr;
+    q.deal_cnt = nullptr;
+    q.deal_order = nullptr;
+    return q;
+}
+
+hipError_t launch_expand(const SimParams& p, const StepInputs& in, int C, const int32_t* roots, const SeqRows& rows,
+                         int n, const EvalOutputs& outs, const PoolState* src, const PoolState& dst,
+                         const int32_t* dst_slots, float* leaf_obs, uint8_t* hand, int chunk, hipStream_t s) {
+    if (n < 1 || n > kMaxSeq || C < 1 || !roots || !dst_slots || dst.slots < 1) return hipErrorInvalidValue;
+    if (leaf_obs && (!hand || chunk < 1)) return hipErrorInvalidValue;
+    const unsigned cars_lds = (unsigned)cars_lds_bytes(p.N, cars_k(p), true);
+    const SimParams sp = src ? pool_view(p, *src) : p;  // what the first sub-step loads from
+    const KeepOuts ko{dst, dst_slots, src ? src->valid : nullptr};
+    const EvalOuts eo{roots, C, outs.gamma, outs.returns, outs.substeps, outs.terminated, outs.truncated};
+    if (!leaf_obs) {
+        const KeepArgs ka{EvalArgs{SeqArgs{RepeatArgs{sp, in, Outputs{}, 0, n, nullptr}, rows}, eo}, ko};
+        if (p.traffic) hipLaunchKernelGGL((k_cars_repeat<true, true, true, false, true>), dim3(C), dim3(WAVE), cars_lds, s, ka);
+        else hipLaunchKernelGGL((k_cars_repeat<false, true, true, false, true>), dim3(C), dim3(WAVE), cars_lds, s, ka);
+        return hipGetLastError();
+    }
+    // with leaf observations: launch_evaluate_leaves' chunks, scratch and cast
+    if (chunk > C) chunk = C;
+    const size_t cn = (size_t)chunk * p.N, S = leaf_stride(p, chunk);
+    LeafHand lf{};
+    lf.pose = reinterpret_cast<float*>(hand);
+    lf.stride = (int64_t)S;
+    lf.cand = reinterpret_cast<unsigned long long*>(hand + 4 * S * sizeof(float));
+    lf.box = reinterpret_cast<int4*>(reinterpret_cast<uint8_t*>(lf.cand) + leaf_al(cn * 16));
+    lf.alive = reinterpret_cast<uint8_t*>(lf.box) + leaf_al((size_t)chunk * p.ob_stride * sizeof(int4));
+    SimParams lp = p;
+    lp.E = chunk;
+    lp.ego = EgoSoA{};
+    lp.ego.x = lf.pose;
+    lp.ego.alive = lf.alive;
+    lp.ego.stride = lf.stride;
+    lp.ob_box = lf.box;
+    lp.ob_cand = lf.cand;
+    Outputs co{};
+    co.obs = leaf_obs;
+    co.obs_ld = p.D;
+    for (int c0 = 0; c0 < C; c0 += chunk) {
+        const int nc = C - c0 < chunk ? C - c0 : chunk;
+        lf.c0 = c0;
+        const KeepLeafArgs la{LeafArgs{EvalArgs{SeqArgs{RepeatArgs{sp, in, co, c0, n, nullptr}, rows}, eo}, lf}, ko};
+        if (p.traffic) hipLaunchKernelGGL((k_cars_repeat<true, true, true, true, true>), dim3(nc), dim3(WAVE), cars_lds, s, la);
+        else hipLaunchKernelGGL((k_cars_repeat<false, true, true, true, true>), dim3(nc), dim3(WAVE), cars_lds, s, la);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+        Outputs lo = co;
+        lo.obs = leaf_obs + (size_t)c0 * p.N * p.D;
+        e = launch_lidar(lp, lo, 0, nc * p.N, s);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+// mev_pool_capture / mev_pool_get_state: block i copies slot from[i] of src into slot to[i] of dst,
+// field by field (lane = agent, then lane = NPC slot, every one of the K), then the counters and
+// the valid byte.  A pair with an index out of range is skipped.
+__global__ __launch_bounds__(WAVE) void k_pool_copy(PoolState src, PoolState dst, const int32_t* from,
+                                                    const int32_t* to, int N, int K) {
+    const int i = blockIdx.x, lane = threadIdx.x;
+    const int a = from ? from[i] : i, b = to ? to[i] : i;
+    if ((unsigned)a >= (unsigned)src.slots || (unsigned)b >= (unsigned)dst.slots) return;
+    for (int j = lane; j < N; j += WAVE) {
+        const size_t s = (size_t)a * N + j, d = (size_t)b * N + j;
+        for (int f = 0; f < EF_COUNT; ++f) dst.ego[dst.ego_stride * f + d] = src.ego[src.ego_stride * f + s];
+        dst.ego_alive[d] = src.ego_alive[s];
+        dst.ego_dim[2 * d] = src.ego_dim[2 * s];
+        dst.ego_dim[2 * d + 1] = src.ego_dim[2 * s + 1];
+    }
+    for (int j = lane; j < K; j += WAVE) {
+        const size_t s = (size_t)a * K + j, d = (size_t)b * K + j;
+        for (int f = 0; f < NF_COUNT; ++f) dst.npc[dst.npc_stride * f + d] = src.npc[src.npc_stride * f + s];
+        dst.npc_alive[d] = src.npc_alive[s];
+        dst.npc_dim[2 * d] = src.npc_dim[2 * s];
+        dst.npc_dim[2 * d + 1] = src.npc_dim[2 * s + 1];
+    }
+    if (lane == 0) {
+        dst.npc_count[b] = src.npc_count[a];
+        dst.step_count[b] = src.step_count[a];
+        dst.valid[b] = src.valid ? src.valid[a] : 1;
+    }
+}
+
+hipError_t launch_pool_copy(const SimParams& p, const PoolState& src, const PoolState& dst, const int32_t* from,
+                            const int32_t* to, int count, hipStream_t s) {
+    if (count < 1) return hipSuccess;
+    if (!dst.valid) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_pool_copy, dim3((unsigned)count), dim3(WAVE), 0, s, src, dst, from, to, p.N, p.K);
+    return hipGetLastError();
 }
 
 hipError_t launch_serve(const SimParams& p, const SimParams* dp, const ServeArgs& sa, const Outputs& out,

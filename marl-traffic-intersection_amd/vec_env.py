@@ -263,7 +263,7 @@ class VecIntersectionEnv:
         return o["obs"], o["reward"], o["terminated"], o["truncated"], info
 
     def evaluate_plans(self, actions, roots, dt=1.0 / 60.0, gamma: float = 1.0, spawn_route=None, copy: bool = False,
-                       leaf_obs: bool = False):
+                       leaf_obs: bool = False, _expand=None):
         """Score C candidate plans from the live batch without touching it (Handle.evaluate_plans):
         actions [T, C, N, 2], roots [C] (the live env each candidate starts from; C is free of
         num_envs) -> dict of returns [C, N] (discounted by gamma, f32), reward_seq / done_seq /
@@ -296,15 +296,40 @@ class VecIntersectionEnv:
                 sp = t.as_tensor(spawn_route, dtype=t.int32, device=dev).contiguous()
                 if tuple(sp.shape) != (T, C):
                     raise ValueError(f"spawn_route must be [{T}][{C}], got {tuple(sp.shape)}")
-            self._h.evaluate_plans(a, r, dt, gamma, spawn_route=sp, out=o, device=True, candidates=C, length=T,
-                                   leaf_obs=leaf_obs)
+            if _expand is not None:
+                d = t.as_tensor(_expand["dst_slots"], dtype=t.int32, device=dev).contiguous()
+                if tuple(d.shape) != (C,):
+                    raise ValueError(f"dst_slots must be [{C}], got {tuple(d.shape)}")
+                self._h.expand_plans(a, r, _expand["dst"], d, _expand["src"], _expand["counter_offset"], leaf_obs, dt,
+                                     gamma, spawn_route=sp, out=o, device=True, candidates=C, length=T)
+            else:
+                self._h.evaluate_plans(a, r, dt, gamma, spawn_route=sp, out=o, device=True, candidates=C, length=T,
+                                       leaf_obs=leaf_obs)
             return {k: v.clone() for k, v in o.items()} if copy else o
         shape = np.shape(actions)
         if len(shape) != 4:
             raise ValueError(f"actions must be [T, C, {self.num_agents}, 2], got {shape}")
         o = self._eval_out(int(shape[0]), int(shape[1]), leaf_obs)
-        self._h.evaluate_plans(actions, roots, dt, gamma, spawn_route=spawn_route, out=o, leaf_obs=leaf_obs)
+        if _expand is not None:
+            self._h.expand_plans(actions, roots, _expand["dst"], _expand["dst_slots"], _expand["src"],
+                                 _expand["counter_offset"], leaf_obs, dt, gamma, spawn_route=spawn_route, out=o)
+        else:
+            self._h.evaluate_plans(actions, roots, dt, gamma, spawn_route=spawn_route, out=o, leaf_obs=leaf_obs)
         return {k: v.copy() for k, v in o.items()} if copy else o
+
+    def make_pool(self, slots: int):
+        """A state pool of `slots` slots on this env's handle (Handle.pool): where expand_plans keeps
+        the states its candidates stop at, and where deeper expansions start from."""
+        return self._h.pool(slots)
+
+    def expand_plans(self, actions, roots, dst, dst_slots, src=None, counter_offset: int = 0, leaf_obs: bool = False,
+                     dt=1.0 / 60.0, gamma: float = 1.0, spawn_route=None, copy: bool = False):
+        """evaluate_plans whose candidates start from slots roots[c] of pool `src` (None: from live
+        envs) and whose stop states go to slots dst_slots[c] of pool `dst` (-1: not stored) --
+        Handle.expand_plans.  The same dict, buffers and stream rules as evaluate_plans; the env's
+        state, last outputs and random stream stay as they are."""
+        return self.evaluate_plans(actions, roots, dt, gamma, spawn_route, copy, leaf_obs,
+                                   _expand=dict(dst=dst, dst_slots=dst_slots, src=src, counter_offset=counter_offset))
 
     def _eval_out(self, T, C, leaf=False):
         """The output buffers of evaluate_plans, kept per (T, C); leaf: with the leaf_obs buffer of
