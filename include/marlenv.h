@@ -507,6 +507,109 @@ typedef struct {
 } mev_expand_args;
 int mev_expand_plans(mev_handle* h, const mev_expand_args* args);
 
+/* Sampled plan evaluation: mev_evaluate_plans (with leaf_obs: mev_evaluate_leaves) whose action rows
+ * are not read from memory -- the sampling half of a CEM / MPPI iteration.  There are `groups` groups
+ * of `samples` candidates; candidate c = g * samples + j starts from live env eval.roots[g] and, for
+ * agent i and sub-step row s (0-based), draws
+ *
+ *   (w0, w1, w2, w3) = Philox4x32-10(key = (lo32(noise_seed), hi32(noise_seed)),
+ *                                    counter = (lo32(noise_counter), hi32(noise_counter), c * 64 + i, s))
+ *   B(w)   = the sum of the four bytes of w                                 (integer, 0..1020)
+ *   eps[0] = ((float)(B(w0) + B(w1)) - 1020.0f) * 0x1.39897ep-8f            (throttle)
+ *   eps[1] = ((float)(B(w2) + B(w3)) - 1020.0f) * 0x1.39897ep-8f            (steer)
+ *   x      = mean[s][g][i][k] + sigma[s][g][i][k] * eps[k]                  (f32: multiply, then add, no FMA)
+ *   action[k] = fminf(fmaxf(x, lo[k]), hi[k])
+ *
+ * The constant is (float)(1 / sqrt(43690)), bits 0x3b9cc4bf: eight uniform bytes have mean 1020 and
+ * variance 43690.  The conversion and the subtraction are exact, so there is one rounded multiply and
+ * the noise is the same bits on the host and the device.  eps is an IRWIN-HALL APPROXIMATION of a unit
+ * Gaussian, not a Gaussian: mean 0, variance 1, kurtosis 2.85, support +-4.88 in 2041 levels.  A caller
+ * who needs another distribution draws the actions itself and calls mev_evaluate_plans.  With
+ * MEV_SAMPLE_MEAN_FIRST candidate j == 0 of every group takes eps = 0.0f in the formula: the (clamped)
+ * mean plan is always among the candidates.
+ * Every output in `eval`, and leaf_obs, is bit for bit what mev_evaluate_plans / mev_evaluate_leaves
+ * return for actions = actions_out and roots[c] = eval.roots[c / samples]; the Philox spawner is keyed
+ * by c with the handle's counter + (s - 1), as before, and the handle is untouched exactly as for
+ * mev_evaluate_plans.  Every element of actions_out is written -- the rows after the sub-step a
+ * candidate stopped at and the rows of a candidate without a root too, still the formula's values -- so
+ * the caller prepares nothing and mev_update_plans reads only defined data.  With leaf_obs the same
+ * scratch and chunks apply (MEV_LEAF_CHUNK honoured; a chunk may cut through a group).
+ * Errors (MEV_E_INVALID, the handle untouched): everything the two evaluation calls refuse, non-NULL
+ * eval.actions, null mean or sigma, candidates != groups * samples, lo[k] > hi[k] or a non-finite
+ * bound, an unknown sample_flags bit; "no output pointer at all" counts leaf_obs and actions_out as
+ * outputs.  Host pointers: a root outside [0, E) -> MEV_E_RANGE; mean, sigma and actions_out go through
+ * the same staging block, and the call is synchronous.  Device pointers: such a root makes all `samples`
+ * candidates of its group the usual all-zero no-ops (their actions_out rows are still the formula's);
+ * no synchronisation.  State pools as source or destination are not part of this call.
+ * Measured (python tools/bench_plan_iteration.py -> profiles/plan_iteration_sweep.json; mev_evaluate_plans'
+ * method): at 4096 envs x 8 agents x 64 beams, device pointers, 64 groups x 64 candidates, every output, medians of
+ * five blocks -- mev_sample_plans + mev_update_plans (softmax) 65.0 us per iteration at T = 4 against 95.1 us for the
+ * same iteration in eager torch around mev_evaluate_plans (98.8 against 123.7 us at T = 8; 4096 groups x 4: 163.3
+ * against 178.5 us at T = 4; one-ego traffic 118.2 against 140.3 us), below it by more than the blocks' spreads at all
+ * five measured shapes.  The call alone costs 3.6 us (T = 4) to 6.8 us (T = 8) more than mev_evaluate_plans on
+ * ready-made actions: drawing is about 0.9 us per sub-step at 4096 candidates, not free. */
+#define MEV_SAMPLE_MEAN_FIRST 0x1u
+typedef struct {
+    mev_evaluate_args eval;   /* as mev_evaluate_plans, except: eval.actions must be NULL; eval.roots is [groups]
+                                 (the live env of group g); eval.candidates must equal groups * samples; every
+                                 output, spawn_route [T][C], dt / dt_seq, gamma and flags as before */
+    float* leaf_obs;          /* optional [C][N][obs_dim], defined exactly as mev_evaluate_leaves' */
+    const float* mean;        /* [length][groups][N][2] */
+    const float* sigma;       /* [length][groups][N][2] */
+    float lo[2], hi[2];       /* clamp per component; lo[k] <= hi[k], finite */
+    int32_t groups, samples;  /* G >= 1, K >= 1, G * K <= MEV_MAX_CANDIDATES */
+    uint64_t noise_seed, noise_counter;
+    float* actions_out;       /* optional [length][C][N][2]: the actions the candidates ran */
+    uint32_t sample_flags;    /* MEV_SAMPLE_MEAN_FIRST */
+} mev_sample_args;
+int mev_sample_plans(mev_handle* h, const mev_sample_args* args);
+
+/* The reduction over each group's candidates: the refit half of a CEM / MPPI iteration.  Candidates
+ * c = g * samples + j; score[c] = scores[c], or with scores NULL the f32 sum of returns[c][i] over
+ * i = 0..N-1 in that order.  Rank within a group: a ranks before b if score_a > score_b; on equal
+ * scores (-0.0f equals +0.0f) the lower j ranks first.  A non-finite score is replaced by -FLT_MAX
+ * before anything else (device pointers); with host pointers it is refused with MEV_E_INVALID.
+ *
+ * MEV_UPDATE_ELITES, exact: with c_0 .. c_{M-1} the first M = elites candidates in rank order, for every
+ * (s, g, i, k), in f32, multiply then add:
+ *   sum = 0;  for r: sum = sum + a[s][c_r][i][k];              mean = sum / (float)M
+ *   q   = 0;  for r: d = a[s][c_r][i][k] - mean;  q = q + d * d
+ *   sigma = sqrtf(q / (float)M)
+ * MEV_UPDATE_SOFTMAX: m = the best score, x_j = (score_j - m) * inv_temperature, w_j = expf(x_j) (the
+ * device's expf, within 1 ulp: the one operation that is not bit-exact against a host), W = the sum of
+ * w_j in j order, mean = (sum_j w_j * a) / W, q = (sum_j w_j * d * d) / W with d = a - mean, sigma =
+ * sqrtf(q), sums in j order.
+ * Both: new_mean = mean, new_sigma = fmaxf(sigma, sigma_min); best[g] = the candidate index c of the
+ * group's first-ranked candidate, best_score[g] its score; order (ELITES) = the elites' c in rank
+ * order; weights (SOFTMAX) = w / W.  new_mean / new_sigma have mev_sample_plans' layout, ready to be its
+ * next input; row 0 of the best candidate (or of new_mean) is an action for mev_step.
+ * The call reads and writes only its arguments: the handle supplies N, the device and the stream; its
+ * state, outputs and counters are untouched (a resident step server is stopped first).  Host pointers
+ * are staged and the call is synchronous; device pointers are not synchronised.
+ * Errors (MEV_E_INVALID): null actions, scores and returns both NULL, no output pointer at all, groups
+ * < 1, samples outside 1..MEV_MAX_SAMPLES, groups * samples > MEV_MAX_CANDIDATES, length outside
+ * 1..MEV_MAX_REPEAT, an unknown mode, elites outside 1..samples (ELITES), inv_temperature negative or
+ * non-finite (SOFTMAX), a NaN sigma_min, any flag other than MEV_DEVICE_PTRS. */
+enum { MEV_UPDATE_ELITES = 0, MEV_UPDATE_SOFTMAX = 1 };
+#define MEV_MAX_SAMPLES 4096
+typedef struct {
+    const float* actions;    /* [length][C][N][2], C = groups * samples (mev_sample_plans' actions_out, or the caller's own) */
+    const float* scores;     /* optional [C]; e.g. returns + gamma^k * V(leaf) computed by the caller */
+    const float* returns;    /* [C][N], used when scores is NULL: score[c] = sum over i = 0..N-1, f32, in that order */
+    int32_t groups, samples, length;   /* samples <= MEV_MAX_SAMPLES, length 1..MEV_MAX_REPEAT */
+    int32_t mode, elites;    /* ELITES: M = elites in 1..samples */
+    float inv_temperature;   /* SOFTMAX: 1 / lambda, finite, >= 0 */
+    float sigma_min;         /* new_sigma = fmaxf(sigma, sigma_min) */
+    float* new_mean;         /* optional [length][groups][N][2] */
+    float* new_sigma;        /* optional [length][groups][N][2] */
+    int32_t* best;           /* optional [groups]: candidate index c of the group's first-ranked candidate */
+    float* best_score;       /* optional [groups] */
+    int32_t* order;          /* optional [groups][M] (ELITES): the elites' c in rank order */
+    float* weights;          /* optional [C] (SOFTMAX): w / W */
+    uint32_t flags;          /* MEV_DEVICE_PTRS */
+} mev_update_args;
+int mev_update_plans(mev_handle* h, const mev_update_args* args);
+
 /* Outputs of the last step / reset, from the handle's own device buffers.
  * Lifetime: after a step that wrote caller-owned output buffers (device
  * pointers in mev_step_args), this call, mev_device_outputs and

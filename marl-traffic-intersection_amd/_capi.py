@@ -51,7 +51,7 @@ EXPORTED = (
     "mev_unpack_gathered", "mev_add_route", "mev_add_route_n", "mev_set_car_dims", "mev_get_car_dims", "mev_car_dims_active",
     "mev_set_beam_angles", "mev_get_beam_angles", "mev_decode_errors", "mev_step_sequence", "mev_restore_map",
     "mev_evaluate_plans", "mev_evaluate_leaves", "mev_pool_create", "mev_pool_destroy", "mev_pool_slots",
-    "mev_pool_capture", "mev_pool_get_state", "mev_expand_plans",
+    "mev_pool_capture", "mev_pool_get_state", "mev_expand_plans", "mev_sample_plans", "mev_update_plans",
 )
 
 
@@ -112,6 +112,26 @@ MEV_MAX_POOL_SLOTS = 1 << 20
 class MevExpandArgs(ctypes.Structure):  # mev_expand_args
     _fields_ = [("eval", MevEvaluateArgs), ("leaf_obs", _vp), ("src", _vp), ("dst", _vp), ("dst_slots", _vp),
                 ("counter_offset", ctypes.c_uint64)]
+
+
+MEV_SAMPLE_MEAN_FIRST = 0x1
+MEV_UPDATE_ELITES, MEV_UPDATE_SOFTMAX = 0, 1
+MEV_MAX_SAMPLES = 4096
+
+
+class MevSampleArgs(ctypes.Structure):  # mev_sample_args
+    _fields_ = [("eval", MevEvaluateArgs), ("leaf_obs", _vp), ("mean", _vp), ("sigma", _vp),
+                ("lo", ctypes.c_float * 2), ("hi", ctypes.c_float * 2), ("groups", ctypes.c_int32),
+                ("samples", ctypes.c_int32), ("noise_seed", ctypes.c_uint64), ("noise_counter", ctypes.c_uint64),
+                ("actions_out", _vp), ("sample_flags", ctypes.c_uint32)]
+
+
+class MevUpdateArgs(ctypes.Structure):  # mev_update_args
+    _fields_ = [("actions", _vp), ("scores", _vp), ("returns", _vp), ("groups", ctypes.c_int32),
+                ("samples", ctypes.c_int32), ("length", ctypes.c_int32), ("mode", ctypes.c_int32),
+                ("elites", ctypes.c_int32), ("inv_temperature", ctypes.c_float), ("sigma_min", ctypes.c_float),
+                ("new_mean", _vp), ("new_sigma", _vp), ("best", _vp), ("best_score", _vp), ("order", _vp),
+                ("weights", _vp), ("flags", ctypes.c_uint32)]
 
 
 # outputs of evaluate_plans: (key, dtype, shape of (T, C, N))
@@ -192,6 +212,8 @@ def load_library(variant: str = None):
     L.mev_pool_capture.argtypes = [_vp, _vp, _vp, _vp, ctypes.c_int32, ctypes.c_uint32]
     L.mev_pool_get_state.argtypes = [_vp, _vp, ctypes.c_int32, ctypes.POINTER(MevState), _vp, _vp, _vp]
     L.mev_expand_plans.argtypes = [_vp, ctypes.POINTER(MevExpandArgs)]
+    L.mev_sample_plans.argtypes = [_vp, ctypes.POINTER(MevSampleArgs)]
+    L.mev_update_plans.argtypes = [_vp, ctypes.POINTER(MevUpdateArgs)]
     L.mev_get_outputs.argtypes = [_vp] + [_vp] * 8 + [ctypes.c_uint32]
     L.mev_get_state.argtypes = [_vp, ctypes.POINTER(MevState)]
     L.mev_set_state.argtypes = [_vp, ctypes.POINTER(MevState)]
@@ -718,6 +740,149 @@ class Handle:
               int(counter_offset))
         return self.evaluate_plans(actions, roots, dt, gamma, spawn_route, out, device, candidates, length, flags,
                                    leaf_obs, _expand=xp)
+
+    def sample_plans(self, mean, sigma, roots, samples: int, dt=1.0 / 60.0, gamma: float = 1.0, lo=(-1.0, -1.0),
+                     hi=(1.0, 1.0), seed: int = 0, counter: int = 0, mean_first: bool = False, leaf_obs: bool = False,
+                     spawn_route=None, out: Optional[dict] = None, device: bool = False, groups: Optional[int] = None,
+                     length: Optional[int] = None, flags: int = 0, sample_flags: Optional[int] = None):
+        """evaluate_plans (leaf_obs=True: with the leaf observations) whose candidates draw their own
+        actions on the device -- mev_sample_plans.  mean, sigma [T][G][N][2], roots [G] (the live env
+        of each group); candidate c = g * samples + j runs clamp(mean + sigma * eps, lo, hi) with eps
+        the Irwin-Hall approximation of a unit Gaussian that include/marlenv.h states, from the
+        Philox stream (seed, counter).  mean_first: candidate j == 0 of every group runs the clamped
+        mean.  Returns evaluate_plans' outputs over C = G * samples candidates plus `actions_out`
+        [T][C][N][2], the actions the candidates ran (every element written).  device=True: every
+        array is a device tensor/pointer and only the outputs present in `out` are written; T and G
+        are mean.shape[0] and roots.shape[0] (or `length` / `groups` for raw pointers)."""
+        N, K = self.N, int(samples)
+        if device:
+            if length is None:
+                length = getattr(mean, "shape", (None,))[0]
+            if groups is None:
+                groups = getattr(roots, "shape", (None,))[0]
+            if length is None or groups is None:
+                raise ValueError("sample_plans needs mean [T][G][N][2] and roots [G] (or length=T, groups=G)")
+            T, G = int(length), int(groups)
+            C = G * K
+            out = out if out is not None else {}
+        else:
+            mean = np.ascontiguousarray(mean, np.float32)
+            sigma = np.ascontiguousarray(sigma, np.float32)
+            roots = np.ascontiguousarray(roots, np.int32)
+            if roots.ndim != 1:
+                raise ValueError(f"roots must be [G], got {roots.shape}")
+            G = int(roots.shape[0]) if groups is None else int(groups)
+            T = (int(mean.shape[0]) if mean.ndim else 0) if length is None else int(length)
+            C = G * K
+            if roots.shape != (G,):
+                raise ValueError(f"roots must be [{G}], got {roots.shape}")
+            if mean.shape != (T, G, N, 2) or sigma.shape != mean.shape:
+                raise ValueError(f"mean and sigma must be [{T}][{G}][{N}][2], got {mean.shape} and {sigma.shape}")
+            if spawn_route is not None:
+                spawn_route = np.ascontiguousarray(np.asarray(spawn_route, np.int32))
+                if spawn_route.shape != (T, C):
+                    raise ValueError(f"spawn_route must be [{T}][{C}], got {spawn_route.shape}")
+            out = out if out is not None else {}
+            if not out:
+                for k, dtype, shape in _EVAL_OUTS:
+                    out[k] = np.zeros(shape(T, C, N), dtype)
+                out["actions_out"] = np.zeros((T, C, N, 2), np.float32)
+            checks = list(_EVAL_OUTS) + [("actions_out", np.float32, lambda T, C, N: (T, C, N, 2))]
+            if leaf_obs:
+                if out.get("leaf_obs") is None:
+                    out["leaf_obs"] = np.zeros((C, N, self.D), np.float32)
+                checks.append(("leaf_obs", np.float32, lambda T, C, N: (C, N, self.D)))
+            for k, dtype, shape in checks:
+                if out.get(k) is not None and (out[k].shape != shape(T, C, N) or out[k].dtype != dtype):
+                    raise ValueError(f"{k} must be {np.dtype(dtype).name} {list(shape(T, C, N))}, got {out[k].shape}")
+        sa = MevSampleArgs()
+        a = sa.eval
+        a.roots, a.spawn_route = _ptr(roots), _ptr(spawn_route)
+        a.candidates, a.length, a.gamma = C, T, float(gamma)
+        dts = None
+        if np.ndim(dt) == 0:
+            a.dt = float(dt)
+        else:
+            dts = np.ascontiguousarray(dt, np.float32).reshape(-1)
+            if dts.size != T:
+                raise ValueError(f"dt must be a float or {T} floats, got {dts.size}")
+            a.dt = float(dts[0]) if T else 0.0
+            a.dt_seq = dts.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
+        for k, _, _ in _EVAL_OUTS:
+            setattr(a, k, _ptr(out.get(k)))
+        a.flags = (MEV_DEVICE_PTRS if device else 0) | int(flags)
+        sa.leaf_obs = _ptr(out.get("leaf_obs")) if leaf_obs else None
+        sa.mean, sa.sigma, sa.actions_out = _ptr(mean), _ptr(sigma), _ptr(out.get("actions_out"))
+        sa.lo = (ctypes.c_float * 2)(*[float(v) for v in lo])
+        sa.hi = (ctypes.c_float * 2)(*[float(v) for v in hi])
+        sa.groups, sa.samples = G, K
+        sa.noise_seed, sa.noise_counter = int(seed) & (2**64 - 1), int(counter) & (2**64 - 1)
+        sa.sample_flags = (MEV_SAMPLE_MEAN_FIRST if mean_first else 0) if sample_flags is None else int(sample_flags)
+        _check(self._lib.mev_sample_plans(self._h, ctypes.byref(sa)))
+        return out
+
+    def update_plans(self, actions, samples: int, scores=None, returns=None, mode: str = "elites",
+                     elites: Optional[int] = None, temperature: float = 1.0, sigma_min: float = 0.0,
+                     out: Optional[dict] = None, device: bool = False, groups: Optional[int] = None,
+                     length: Optional[int] = None, flags: int = 0):
+        """Rank each group's `samples` candidates and refit mean and sigma -- mev_update_plans.
+        actions [T][C][N][2] (C = G * samples), the score of candidate c is scores[c] or the f32 sum
+        of returns[c].  mode "elites": the `elites` best, exact; "softmax": weights
+        exp((score - best) / temperature) (temperature = inf: equal weights).  Returns `new_mean`,
+        `new_sigma` [T][G][N][2] (sigma at least sigma_min), `best`, `best_score` [G] and `order`
+        [G][elites] (elites) or `weights` [C] (softmax).  device=True: device tensors/pointers, only
+        the outputs present in `out` are written, T and C from actions.shape (or `length` / `groups`)."""
+        N, K = self.N, int(samples)
+        if mode not in ("elites", "softmax"):
+            raise ValueError(f"mode must be 'elites' or 'softmax', got {mode!r}")
+        el = mode == "elites"
+        M = int(elites) if elites is not None else max(1, K // 4)
+        if device:
+            shp = getattr(actions, "shape", None)
+            if length is None and shp is not None:
+                length = shp[0]
+            if groups is None and shp is not None:
+                groups = shp[1] // K
+            if length is None or groups is None:
+                raise ValueError("update_plans needs actions [T][C][N][2] (or length=T, groups=G)")
+            T, G = int(length), int(groups)
+            out = out if out is not None else {}
+        else:
+            actions = np.ascontiguousarray(actions, np.float32)
+            if actions.ndim != 4 or actions.shape[2:] != (N, 2) or actions.shape[1] % K:
+                raise ValueError(f"actions must be [T][G * {K}][{N}][2], got {actions.shape}")
+            T, G = int(actions.shape[0]), int(actions.shape[1]) // K
+            C = G * K
+            if scores is not None:
+                scores = np.ascontiguousarray(scores, np.float32)
+                if scores.shape != (C,):
+                    raise ValueError(f"scores must be [{C}], got {scores.shape}")
+            if returns is not None:
+                returns = np.ascontiguousarray(returns, np.float32)
+                if returns.shape != (C, N):
+                    raise ValueError(f"returns must be [{C}][{N}], got {returns.shape}")
+            shapes = {"new_mean": ((T, G, N, 2), np.float32), "new_sigma": ((T, G, N, 2), np.float32),
+                      "best": ((G,), np.int32), "best_score": ((G,), np.float32)}
+            shapes.update({"order": ((G, M), np.int32)} if el else {"weights": ((C,), np.float32)})
+            out = out if out is not None else {}
+            if not out:
+                for k, (shape, dtype) in shapes.items():
+                    out[k] = np.zeros(shape, dtype)
+            for k, (shape, dtype) in shapes.items():
+                if out.get(k) is not None and (out[k].shape != shape or out[k].dtype != dtype):
+                    raise ValueError(f"{k} must be {np.dtype(dtype).name} {list(shape)}, got {out[k].shape}")
+        ua = MevUpdateArgs()
+        ua.actions, ua.scores, ua.returns = _ptr(actions), _ptr(scores), _ptr(returns)
+        ua.groups, ua.samples, ua.length = G, K, T
+        ua.mode, ua.elites = (MEV_UPDATE_ELITES, M) if el else (MEV_UPDATE_SOFTMAX, 0)
+        t = float(temperature)
+        ua.inv_temperature = (0.0 if t == float("inf") else 1.0 / t) if t != 0.0 else float("inf")
+        ua.sigma_min = float(sigma_min)
+        for k in ("new_mean", "new_sigma", "best", "best_score", "order", "weights"):
+            setattr(ua, k, _ptr(out.get(k)))
+        ua.flags = (MEV_DEVICE_PTRS if device else 0) | int(flags)
+        _check(self._lib.mev_update_plans(self._h, ctypes.byref(ua)))
+        return out
 
     # -- multi-GPU gather (mev_comm_*) -------------------------------------
     def comm_init(self, unique_id: bytes, world: int, rank: int, root: int = 0, slots: int = 0):

@@ -11,6 +11,7 @@
 
 #include <atomic>
 #include <chrono>
+#include <cmath>
 #include <mutex>
 #include <cstdio>
 #include <string>
@@ -1616,27 +1617,42 @@ int mev_step_sequence(mev_handle* h, const mev_sequence_args* sa) {
 constexpr size_t kLeafHandCap = size_t(64) << 20;
 // xp: mev_expand_plans' additions (null: the two evaluation calls) -- the candidates' roots are slots
 // of xp->src when that is set, and their stop states go to slots xp->dst_slots of xp->dst.
+// sm: mev_sample_plans' additions (null: the other calls) -- no actions array: the candidates draw
+// their rows from sm->mean / sm->sigma, roots is [groups], and the rows go to sm->actions_out.
 static int evaluate(mev_handle* h, const mev_evaluate_args* ea, float* leaf_obs, bool leaves,
-                    const mev_expand_args* xp = nullptr) {
-    const char* fn = xp ? "mev_expand_plans" : leaves ? "mev_evaluate_leaves" : "mev_evaluate_plans";
+                    const mev_expand_args* xp = nullptr, const mev_sample_args* sm = nullptr) {
+    const char* fn = sm ? "mev_sample_plans" : xp ? "mev_expand_plans" : leaves ? "mev_evaluate_leaves" : "mev_evaluate_plans";
     if (xp) {
         if (!xp->dst || !xp->dst_slots) return fail(MEV_E_INVALID, "dst and dst_slots required");
         if (xp->dst->h != h || (xp->src && xp->src->h != h)) return fail(MEV_E_INVALID, "the pool belongs to another handle");
     }
-    if (!ea->actions || !ea->roots) return fail(MEV_E_INVALID, "actions and roots required");
+    if (sm) {
+        if (ea->actions) return fail(MEV_E_INVALID, "mev_sample_plans draws the actions: eval.actions must be NULL");
+        if (!ea->roots || !sm->mean || !sm->sigma) return fail(MEV_E_INVALID, "roots, mean and sigma required");
+        if (sm->groups < 1 || sm->samples < 1 || int64_t(sm->groups) * sm->samples != int64_t(ea->candidates))
+            return fail(MEV_E_INVALID, "candidates must equal groups * samples (each at least 1)");
+        for (int k = 0; k < 2; ++k)
+            if (!std::isfinite(sm->lo[k]) || !std::isfinite(sm->hi[k]) || sm->lo[k] > sm->hi[k])
+                return fail(MEV_E_INVALID, "lo and hi must be finite with lo[k] <= hi[k]");
+        if (sm->sample_flags & ~uint32_t(MEV_SAMPLE_MEAN_FIRST))
+            return fail(MEV_E_INVALID, "sample_flags takes MEV_SAMPLE_MEAN_FIRST only");
+    } else if (!ea->actions || !ea->roots) {
+        return fail(MEV_E_INVALID, "actions and roots required");
+    }
     if (ea->candidates < 1 || ea->candidates > MEV_MAX_CANDIDATES)
         return fail(MEV_E_INVALID, "candidates must be in 1.." + std::to_string(MEV_MAX_CANDIDATES));
     if (ea->length < 1 || ea->length > MEV_MAX_REPEAT)
         return fail(MEV_E_INVALID, "length must be in 1.." + std::to_string(MEV_MAX_REPEAT));
     if (ea->flags & ~uint32_t(MEV_DEVICE_PTRS)) return fail(MEV_E_INVALID, std::string(fn) + " takes MEV_DEVICE_PTRS only");
-    if (!xp && !leaves && !ea->returns && !ea->reward_seq && !ea->done_seq && !ea->status_seq && !ea->substeps &&
-        !ea->terminated && !ea->truncated)
-        return fail(MEV_E_INVALID, "mev_evaluate_plans needs at least one output");
+    if (!xp && !leaves && !(sm && sm->actions_out) && !ea->returns && !ea->reward_seq && !ea->done_seq &&
+        !ea->status_seq && !ea->substeps && !ea->terminated && !ea->truncated)
+        return fail(MEV_E_INVALID, std::string(fn) + " needs at least one output");
     const bool dev = (ea->flags & MEV_DEVICE_PTRS) != 0;
     const size_t C = size_t(ea->candidates), T = size_t(ea->length), N = size_t(h->cfg.num_agents), CN = C * N;
     const int32_t n_roots = xp && xp->src ? xp->src->slots : h->cfg.num_envs;  // where a root may point
+    const size_t R = sm ? size_t(sm->groups) : C;                              // entries of roots
     if (!dev)
-        for (size_t c = 0; c < C; ++c)
+        for (size_t c = 0; c < R; ++c)
             if (ea->roots[c] < 0 || ea->roots[c] >= n_roots)
                 return fail(MEV_E_RANGE, "roots[" + std::to_string(c) + "] = " + std::to_string(ea->roots[c]) +
                                              " is outside [0, " + std::to_string(n_roots) + ")");
@@ -1703,6 +1719,12 @@ static int evaluate(mev_handle* h, const mev_evaluate_args* ea, float* leaf_obs,
             h->leaf_cap = need;
         }
     }
+    mev::SampleIn si{};  // (sm) the device view of the sampling arguments
+    if (sm)
+        si = mev::SampleIn{sm->mean, sm->sigma, sm->actions_out, {sm->lo[0], sm->lo[1]}, {sm->hi[0], sm->hi[1]},
+                           sm->groups, sm->samples, uint32_t(sm->noise_seed), uint32_t(sm->noise_seed >> 32),
+                           uint32_t(sm->noise_counter), uint32_t(sm->noise_counter >> 32),
+                           (sm->sample_flags & MEV_SAMPLE_MEAN_FIRST) ? 1u : 0u};
     if (dev) {
         in.actions = ea->actions;
         in.spawn_route = ea->spawn_route;
@@ -1717,7 +1739,9 @@ static int evaluate(mev_handle* h, const mev_evaluate_args* ea, float* leaf_obs,
             if (wanted) off += (bytes + 255) & ~size_t(255);
             return at;
         };
-        const size_t o_act = take(true, T * CN * 2 * sizeof(float)), o_roots = take(true, C * sizeof(int32_t));
+        const size_t act_bytes = T * CN * 2 * sizeof(float), ms_bytes = T * R * N * 2 * sizeof(float);
+        const size_t o_act = take(!sm || sm->actions_out, act_bytes), o_roots = take(true, R * sizeof(int32_t));
+        const size_t o_mean = take(sm != nullptr, ms_bytes), o_sigma = take(sm != nullptr, ms_bytes);
         const size_t o_spawn = take(ea->spawn_route != nullptr, T * C * sizeof(int32_t));
         const size_t o_ret = take(ea->returns != nullptr, CN * sizeof(float));
         const size_t o_rew = take(ea->reward_seq != nullptr, T * CN * sizeof(float));
@@ -1736,9 +1760,17 @@ static int evaluate(mev_handle* h, const mev_evaluate_args* ea, float* leaf_obs,
             h->eval_cap = off;
         }
         uint8_t* b = h->d_eval;
-        HIP_TRY(hipMemcpyAsync(b + o_act, ea->actions, T * CN * 2 * sizeof(float), hipMemcpyHostToDevice, h->stream));
-        HIP_TRY(hipMemcpyAsync(b + o_roots, ea->roots, C * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
-        in.actions = reinterpret_cast<const float*>(b + o_act);
+        if (sm) {
+            HIP_TRY(hipMemcpyAsync(b + o_mean, sm->mean, ms_bytes, hipMemcpyHostToDevice, h->stream));
+            HIP_TRY(hipMemcpyAsync(b + o_sigma, sm->sigma, ms_bytes, hipMemcpyHostToDevice, h->stream));
+            si.mean = reinterpret_cast<const float*>(b + o_mean);
+            si.sigma = reinterpret_cast<const float*>(b + o_sigma);
+            if (sm->actions_out) si.actions_out = reinterpret_cast<float*>(b + o_act);
+        } else {
+            HIP_TRY(hipMemcpyAsync(b + o_act, ea->actions, act_bytes, hipMemcpyHostToDevice, h->stream));
+            in.actions = reinterpret_cast<const float*>(b + o_act);
+        }
+        HIP_TRY(hipMemcpyAsync(b + o_roots, ea->roots, R * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
         d_roots = reinterpret_cast<const int32_t*>(b + o_roots);
         if (ea->spawn_route) {
             HIP_TRY(hipMemcpyAsync(b + o_spawn, ea->spawn_route, T * C * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
@@ -1757,7 +1789,10 @@ static int evaluate(mev_handle* h, const mev_evaluate_args* ea, float* leaf_obs,
             d_dst = reinterpret_cast<const int32_t*>(b + o_dst);
         }
     }
-    if (xp)
+    if (sm)
+        HIP_TRY(mev::launch_sample(h->sp, in, d_roots, rows, int(T), eo, si, leaves ? d_leaf_obs : nullptr, h->d_leaf, chunk,
+                                   h->stream));
+    else if (xp)
         HIP_TRY(mev::launch_expand(h->sp, in, int(C), d_roots, rows, int(T), eo, xp->src ? &xp->src->st : nullptr,
                                    xp->dst->st, d_dst, leaves ? d_leaf_obs : nullptr, h->d_leaf, chunk, h->stream));
     else if (leaves)
@@ -1777,6 +1812,7 @@ static int evaluate(mev_handle* h, const mev_evaluate_args* ea, float* leaf_obs,
         HIP_TRY(back(ea->terminated, eo.terminated, C));
         HIP_TRY(back(ea->truncated, eo.truncated, C));
         HIP_TRY(back(leaf_obs, d_leaf_obs, obs_bytes));
+        if (sm) HIP_TRY(back(sm->actions_out, si.actions_out, T * CN * 2 * sizeof(float)));
         HIP_TRY(hipStreamSynchronize(h->stream));
     }
     return MEV_OK;
@@ -1974,6 +2010,105 @@ int mev_pool_get_state(mev_pool* pool, const int32_t* slots, int32_t count, cons
 int mev_expand_plans(mev_handle* h, const mev_expand_args* xa) {
     if (!h || !xa) return fail(MEV_E_INVALID, "null argument");
     return evaluate(h, &xa->eval, xa->leaf_obs, xa->leaf_obs != nullptr, xa);
+}
+
+// mev_sample_plans (include/marlenv.h): the evaluation calls with the actions drawn by the
+// candidates' own waves (the car kernel's SAMPLE mode).
+int mev_sample_plans(mev_handle* h, const mev_sample_args* sa) {
+    if (!h || !sa) return fail(MEV_E_INVALID, "null argument");
+    return evaluate(h, &sa->eval, sa->leaf_obs, sa->leaf_obs != nullptr, nullptr, sa);
+}
+
+// mev_update_plans (include/marlenv.h): the reduction over each group's candidates, k_update_plans.
+// Reads and writes its arguments only; host pointers go through the handle's staging block.
+int mev_update_plans(mev_handle* h, const mev_update_args* ua) {
+    if (!h || !ua) return fail(MEV_E_INVALID, "null argument");
+    if (!ua->actions || (!ua->scores && !ua->returns)) return fail(MEV_E_INVALID, "actions and scores or returns required");
+    if (ua->groups < 1 || ua->samples < 1 || ua->samples > MEV_MAX_SAMPLES ||
+        int64_t(ua->groups) * ua->samples > MEV_MAX_CANDIDATES)
+        return fail(MEV_E_INVALID, "groups >= 1, samples in 1.." + std::to_string(MEV_MAX_SAMPLES) +
+                                       ", groups * samples <= " + std::to_string(MEV_MAX_CANDIDATES));
+    if (ua->length < 1 || ua->length > MEV_MAX_REPEAT)
+        return fail(MEV_E_INVALID, "length must be in 1.." + std::to_string(MEV_MAX_REPEAT));
+    if (ua->flags & ~uint32_t(MEV_DEVICE_PTRS)) return fail(MEV_E_INVALID, "mev_update_plans takes MEV_DEVICE_PTRS only");
+    const bool elites = ua->mode == MEV_UPDATE_ELITES;
+    if (!elites && ua->mode != MEV_UPDATE_SOFTMAX) return fail(MEV_E_INVALID, "mode must be MEV_UPDATE_ELITES or MEV_UPDATE_SOFTMAX");
+    if (elites && (ua->elites < 1 || ua->elites > ua->samples)) return fail(MEV_E_INVALID, "elites must be in 1..samples");
+    if (!elites && !(std::isfinite(ua->inv_temperature) && ua->inv_temperature >= 0.0f))
+        return fail(MEV_E_INVALID, "inv_temperature must be finite and >= 0");
+    if (std::isnan(ua->sigma_min)) return fail(MEV_E_INVALID, "sigma_min must not be NaN");
+    if (!ua->new_mean && !ua->new_sigma && !ua->best && !ua->best_score && !(elites && ua->order) && !(!elites && ua->weights))
+        return fail(MEV_E_INVALID, "mev_update_plans needs at least one output");
+    const bool dev = (ua->flags & MEV_DEVICE_PTRS) != 0;
+    const size_t G = size_t(ua->groups), K = size_t(ua->samples), C = G * K, T = size_t(ua->length);
+    const size_t N = size_t(h->cfg.num_agents), M = size_t(elites ? ua->elites : 0);
+    if (!dev)  // a non-finite score is refused here; with device pointers it ranks last
+        for (size_t c = 0; c < C; ++c) {
+            float sc = 0.0f;
+            if (ua->scores) sc = ua->scores[c];
+            else
+                for (size_t i = 0; i < N; ++i) sc = sc + ua->returns[c * N + i];
+            if (!std::isfinite(sc)) return fail(MEV_E_INVALID, "the score of candidate " + std::to_string(c) + " is not finite");
+        }
+    HIP_TRY(hipSetDevice(h->cfg.device));
+    if (int r = serve_stop(h)) return r;  // (the server holds the stream)
+    mev::UpdateArgs u{ua->actions, ua->scores, ua->returns, ua->groups, ua->samples, ua->length, int32_t(N), ua->mode,
+                      ua->elites, ua->inv_temperature, ua->sigma_min, ua->new_mean, ua->new_sigma, ua->best,
+                      ua->best_score, elites ? ua->order : nullptr, elites ? nullptr : ua->weights};
+    if (dev) {
+        HIP_TRY(mev::launch_update_plans(u, h->stream));
+        return MEV_OK;
+    }
+    // the staging block: every array of this call, each at a 256-byte boundary
+    size_t off = 0;
+    auto take = [&off](bool wanted, size_t bytes) {
+        const size_t at = off;
+        if (wanted) off += (bytes + 255) & ~size_t(255);
+        return at;
+    };
+    const size_t act_bytes = T * C * N * 2 * sizeof(float), ms_bytes = T * G * N * 2 * sizeof(float);
+    const size_t o_act = take(true, act_bytes), o_sc = take(u.scores != nullptr, C * sizeof(float));
+    const size_t o_ret = take(!u.scores, C * N * sizeof(float));
+    const size_t o_mean = take(u.new_mean != nullptr, ms_bytes), o_sigma = take(u.new_sigma != nullptr, ms_bytes);
+    const size_t o_best = take(u.best != nullptr, G * sizeof(int32_t)), o_bs = take(u.best_score != nullptr, G * sizeof(float));
+    const size_t o_ord = take(u.order != nullptr, G * M * sizeof(int32_t)), o_w = take(u.weights != nullptr, C * sizeof(float));
+    if (off > h->eval_cap) {
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        if (h->d_eval) (void)hipFree(h->d_eval);
+        h->d_eval = nullptr;
+        h->eval_cap = 0;
+        const hipError_t err = hipMalloc(reinterpret_cast<void**>(&h->d_eval), off);
+        if (err != hipSuccess) return fail(MEV_E_NOMEM, std::string("device allocation failed: ") + hipGetErrorString(err));
+        h->eval_cap = off;
+    }
+    uint8_t* b = h->d_eval;
+    HIP_TRY(hipMemcpyAsync(b + o_act, ua->actions, act_bytes, hipMemcpyHostToDevice, h->stream));
+    u.actions = reinterpret_cast<const float*>(b + o_act);
+    if (u.scores) {
+        HIP_TRY(hipMemcpyAsync(b + o_sc, ua->scores, C * sizeof(float), hipMemcpyHostToDevice, h->stream));
+        u.scores = reinterpret_cast<const float*>(b + o_sc);
+    } else {
+        HIP_TRY(hipMemcpyAsync(b + o_ret, ua->returns, C * N * sizeof(float), hipMemcpyHostToDevice, h->stream));
+        u.returns = reinterpret_cast<const float*>(b + o_ret);
+    }
+    if (u.new_mean) u.new_mean = reinterpret_cast<float*>(b + o_mean);
+    if (u.new_sigma) u.new_sigma = reinterpret_cast<float*>(b + o_sigma);
+    if (u.best) u.best = reinterpret_cast<int32_t*>(b + o_best);
+    if (u.best_score) u.best_score = reinterpret_cast<float*>(b + o_bs);
+    if (u.order) u.order = reinterpret_cast<int32_t*>(b + o_ord);
+    if (u.weights) u.weights = reinterpret_cast<float*>(b + o_w);
+    HIP_TRY(mev::launch_update_plans(u, h->stream));
+    auto back = [h](void* dst, const void* src, size_t bytes) {
+        return dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream) : hipSuccess;
+    };
+    HIP_TRY(back(ua->new_mean, u.new_mean, ms_bytes));
+    HIP_TRY(back(ua->new_sigma, u.new_sigma, ms_bytes));
+    HIP_TRY(back(ua->best, u.best, G * sizeof(int32_t)));
+    HIP_TRY(back(ua->best_score, u.best_score, G * sizeof(float)));
+    if (elites) HIP_TRY(back(ua->order, u.order, G * M * sizeof(int32_t)));
+    else HIP_TRY(back(ua->weights, u.weights, C * sizeof(float)));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return MEV_OK;
 }
 
 static int sync_internal(mev_handle* h);  // below, with mev_device_outputs

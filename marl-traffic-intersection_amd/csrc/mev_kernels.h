@@ -310,6 +310,46 @@ hipError_t launch_pool_copy(const SimParams& p, const PoolState& src, const Pool
 hipError_t launch_expand(const SimParams& p, const StepInputs& in, int C, const int32_t* roots, const SeqRows& rows,
                          int n, const EvalOutputs& outs, const PoolState* src, const PoolState& dst,
                          const int32_t* dst_slots, float* leaf_obs, uint8_t* hand, int chunk, hipStream_t s);
+// Sampled plan evaluation (mev_sample_plans): launch_evaluate (leaf_obs null) or
+// launch_evaluate_leaves, bit for bit, whose candidates draw their own actions
+// (k_cars_repeat<..., SAMPLE = true>).  in.actions is not read; candidate c = g * samples + j
+// starts from live env roots[g] (roots is [groups], C = groups * samples) and takes, per sub-step
+// row s, agent i, component k, clamp(mean[s][g][i][k] + sigma[s][g][i][k] * eps[k], lo[k], hi[k])
+// with eps from Philox4x32-10 keyed by the noise seed at counter (noise counter, c * 64 + i, s).
+// Every element of actions_out (nullable) is written, for candidates that stop early or have no
+// root as well.
+struct SampleIn {
+    const float* mean;   // [n][groups][N][2]
+    const float* sigma;  // [n][groups][N][2]
+    float* actions_out;  // [n][C][N][2] (nullable)
+    float lo[2], hi[2];
+    int32_t groups, samples;
+    uint32_t seed_lo, seed_hi, ctr_lo, ctr_hi;  // the noise stream: Philox key and counter words 0, 1
+    uint32_t mean_first;                        // candidate j == 0 of every group takes eps = 0
+};
+hipError_t launch_sample(const SimParams& p, const StepInputs& in, const int32_t* roots, const SeqRows& rows, int n,
+                         const EvalOutputs& outs, const SampleIn& sm, float* leaf_obs, uint8_t* hand, int chunk,
+                         hipStream_t s);
+// Refit over candidates (mev_update_plans, k_update_plans): one workgroup per group ranks its
+// `samples` candidates by score (scores[c], or the in-order f32 sum of returns[c][0..N); a
+// non-finite score counts as -FLT_MAX; equal scores: the lower j first) and reduces the action rows
+// to a new mean and sigma per (s, i, k): mode 0 over the first `elites` in rank order, mode 1 with
+// weights expf((score - best) * inv_temperature) in j order.  Every output is nullable.
+struct UpdateArgs {
+    const float* actions;  // [n][C][N][2]
+    const float* scores;   // [C] (nullable)
+    const float* returns;  // [C][N], read when scores is null
+    int32_t groups, samples, n, N;
+    int32_t mode, elites;
+    float inv_temperature, sigma_min;
+    float* new_mean;       // [n][groups][N][2]
+    float* new_sigma;      // [n][groups][N][2]
+    int32_t* best;         // [groups]
+    float* best_score;     // [groups]
+    int32_t* order;        // [groups][elites] (mode 0)
+    float* weights;        // [C] (mode 1)
+};
+hipError_t launch_update_plans(const UpdateArgs& u, hipStream_t s);
 hipError_t launch_reset(const SimParams& p, const uint8_t* env_mask, const Outputs& out, hipStream_t s,
                         uint64_t rng_counter);
 // recompute the observation rows from the current state with LiDAR = max (after set_state)

@@ -13,6 +13,7 @@
 // cpp/Lidar.cpp:16-90 (ray march).  Compiled with -ffp-contract=off.
 #include <type_traits>
 
+#include <cfloat>
 #include <cstdlib>
 
 #include "mev_kernels.h"
@@ -255,6 +256,27 @@ __device__ inline void philox(uint32_t c0, uint32_t c1, uint32_t c2, uint64_t se
     }
     *r0 = x0;
     *r1 = x1;
+}
+
+// Philox4x32-10 with the whole counter and all four words kept (mev_sample_plans' noise): the
+// round function and key bumps of philox() above, which stays as it is (the spawner's kernels).
+__device__ inline void philox4(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
+                               uint32_t* w) {
+    uint32_t x0 = c0, x1 = c1, x2 = c2, x3 = c3;
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint64_t p0 = (uint64_t)0xD2511F53u * x0;
+        const uint64_t p1 = (uint64_t)0xCD9E8D57u * x2;
+        const uint32_t y0 = (uint32_t)(p1 >> 32) ^ x1 ^ k0;
+        const uint32_t y2 = (uint32_t)(p0 >> 32) ^ x3 ^ k1;
+        x1 = (uint32_t)p1;
+        x3 = (uint32_t)p0;
+        x0 = y0;
+        x2 = y2;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    w[0] = x0; w[1] = x1; w[2] = x2; w[3] = x3;
 }
 
 __device__ inline float u01(uint32_t r) { return (float)(r >> 8) * 0x1p-24f; }
@@ -1546,6 +1568,50 @@ constexpr bool kSeqEarlyLoad = true;
 constexpr bool kSeqEarlyLoad = false;
 #endif
 
+// SAMPLE (mev_sample_plans): a plan evaluation whose action rows are not read from memory.  Lane =
+// agent i of candidate c = g * samples + j draws sub-step row s's two floats itself, wherever the
+// plan rollout would load them:
+//   (w0..w3) = Philox4x32-10(key = the noise seed, counter = (the noise counter, c * 64 + i, s))
+//   eps[k]   = ((float)(byte sum of w[2k], w[2k+1]) - 1020.0f) * (float)(1 / sqrt(43690))
+//   a[k]     = fminf(fmaxf(mean[s][g][i][k] + sigma[s][g][i][k] * eps[k], lo[k]), hi[k])
+// -- eight uniform bytes have mean 1020 and variance 43690, so eps is an Irwin-Hall approximation
+// of a unit Gaussian (kurtosis 2.85, support +-4.88) whose conversion and subtraction are exact:
+// one rounded multiply, restated bit for bit on the host (tests/plan_noise_ref.py).  A Box-Muller
+// Gaussian would need glibc's logf restated the way mev_math.h restates sincosf.  mean_first:
+// candidate j == 0 of every group takes eps = 0.  The floats go to row s of actions_out
+// ([n][C][N][2], nullable) as well.  (SampleIn: mev_kernels.h)
+// what a candidate's wave keeps of it: its group and whether it is the group's mean plan
+struct SampleCtx {
+    const SampleIn* in = nullptr;
+    int grp = 0;
+    bool zero = false;
+};
+__device__ __forceinline__ float2 sample_action(const SampleCtx& sc, const int N, const int c, const int i, const int s,
+                                                const bool lane_on) {
+    const SampleIn& sm = *sc.in;
+    uint32_t w[4];
+    philox4(sm.ctr_lo, sm.ctr_hi, (uint32_t)c * 64u + (uint32_t)i, (uint32_t)s, sm.seed_lo, sm.seed_hi, w);
+    const uint32_t b0 = __builtin_amdgcn_sad_u8(w[1], 0u, __builtin_amdgcn_sad_u8(w[0], 0u, 0u));
+    const uint32_t b1 = __builtin_amdgcn_sad_u8(w[3], 0u, __builtin_amdgcn_sad_u8(w[2], 0u, 0u));
+    const float e0 = sc.zero ? 0.0f : ((float)b0 - 1020.0f) * 0x1.39897ep-8f;
+    const float e1 = sc.zero ? 0.0f : ((float)b1 - 1020.0f) * 0x1.39897ep-8f;
+    // (the rows' bases are wave-uniform: SGPR base + one 32-bit lane offset, the global_load saddr form)
+    const size_t mrow = 2 * (((size_t)s * sm.groups + sc.grp) * N);
+    const uint32_t o = 2u * (uint32_t)i;
+    const float m0 = ldu(gmem(sm.mean + mrow), o), m1 = ldu(gmem(sm.mean + mrow), o + 1);
+    const float s0 = ldu(gmem(sm.sigma + mrow), o), s1 = ldu(gmem(sm.sigma + mrow), o + 1);
+    const float x0 = m0 + s0 * e0;
+    const float x1 = m1 + s1 * e1;
+    const float2 a = make_float2(fminf(fmaxf(x0, sm.lo[0]), sm.hi[0]), fminf(fmaxf(x1, sm.lo[1]), sm.hi[1]));
+    if (sm.actions_out && lane_on) {
+        typedef __attribute__((address_space(1))) char gchar;
+        gchar* row = (gchar*)gmem(sm.actions_out + 2 * (((size_t)s * sm.groups * sm.samples + c) * N));
+        *(__attribute__((address_space(1))) float*)(row + o * 4u) = a.x;
+        *(__attribute__((address_space(1))) float*)(row + (o + 1) * 4u) = a.y;
+    }
+    return a;
+}
+
 // Phase 1 of the car part for agent i of el on lane group (grp, sub): kinematics
 // (IntersectionEnv.cpp:151-163), path index, base reward (:15-46), status (:165-290).
 // cars_pre runs it over its agents 8 per pass; the traffic early split's LiDAR wave
@@ -1755,14 +1821,16 @@ __device__ __forceinline__ void ego_phase1(const SimParams& p, const StepInputs&
 // every sub-step, as the plan rollout does (cars_post knows the stop).
 template <bool TRAFFIC, bool FUSED, class NL, int PK = 1, bool EARLY = false, bool ESPLIT = false, bool DIMS = false,
           bool TSC = false, int NC = 0, bool REP = false, bool WC = false, bool SEQ = false, bool EVAL = false,
-          bool LEAF = false>
+          bool LEAF = false, bool SAMPLE = false>
 __device__ __forceinline__ CarsCtx cars_pre(const SimParams& p, const StepInputs& in, const Outputs& out, const int e,
                                             const CarsLDS& el, NL* nl, int npc_cls = kDealClasses - 1,
-                                            const RepCarry* rc = nullptr, const int src_e = 0) {
+                                            const RepCarry* rc = nullptr, const int src_e = 0,
+                                            const SampleCtx& sc = SampleCtx{}) {
     static_assert(!REP || (!FUSED && PK == 1 && !EARLY && !ESPLIT && !TSC && NC == 0), "frame skip: k_cars' layout");
     static_assert(!SEQ || REP, "plan rollout: the frame-skip loop");
     static_assert(!EVAL || SEQ, "plan evaluation: the plan rollout's loop");
     static_assert(!LEAF || EVAL, "leaf observations: a plan evaluation");
+    static_assert(!SAMPLE || EVAL, "sampled actions: a plan evaluation");
     static_assert(!ESPLIT || FUSED, "early split: k_step");
     static_assert(PK == 1 || (FUSED && !TRAFFIC), "several envs per wave: k_step without traffic");
     static_assert(!DIMS || (PK == 1 && !EARLY && !ESPLIT), "per-car sizes: the runtime-layout kernels");
@@ -1814,6 +1882,18 @@ __device__ __forceinline__ CarsCtx cars_pre(const SimParams& p, const StepInputs
     if constexpr (REP) cont = rc->s > 0;
     static_assert(!EARLY || (FUSED && !TRAFFIC), "LDS path windows: k_step without traffic");
     constexpr bool early = EARLY;
+    // SAMPLE: this sub-step's action row is drawn here, once, in the place of both loads below, and goes
+    // straight into el.a0 / el.a1 (the previous sub-step's reads are behind the loop's LDS sync; in the
+    // experiment build the kernel's loop has drawn a later sub-step's already)
+    if constexpr (SAMPLE) {
+        if (!(kSeqEarlyLoad && cont)) {
+            const float2 drawn = sample_action(sc, NE, e, il, rc->s, lane_on);
+            if (lane_on) {
+                el.a0[il] = drawn.x;
+                el.a1[il] = drawn.y;
+            }
+        }
+    }
     if (!cont) {
         // where the state comes from: the lane's own env and agent, or (EVAL) the candidate's root
         const int se = EVAL ? src_e : e;
@@ -1822,7 +1902,11 @@ __device__ __forceinline__ CarsCtx cars_pre(const SimParams& p, const StepInputs
         const uint8_t pending_b = ldu(gmem(p.pending_reset), use);  // (EVAL: read, then ignored)
         const int step_prev = ldu(gmem(p.step_count), use);
         const int npcs_prev = TRAFFIC ? gmem(p.npc.count)[se] : 0;
-        const float a0 = ldu(gmem(in.actions), 2 * ug), a1 = ldu(gmem(in.actions), 2 * ug + 1);
+        float a0, a1;  // (SAMPLE: drawn above, neither loaded nor stored here)
+        if constexpr (!SAMPLE) {
+            a0 = ldu(gmem(in.actions), 2 * ug);
+            a1 = ldu(gmem(in.actions), 2 * ug + 1);
+        }
         const int route_l = ldu(egoi(p, EF_ROUTE), us);
         const float x0 = ldu(egof(p, EF_X), us), y0 = ldu(egof(p, EF_Y), us), v0 = ldu(egof(p, EF_V), us);
         const float h0 = ldu(egof(p, EF_H), us), acc0 = ldu(egof(p, EF_ACC), us), steer0 = ldu(egof(p, EF_STEER), us);
@@ -1891,8 +1975,10 @@ __device__ __forceinline__ CarsCtx cars_pre(const SimParams& p, const StepInputs
             el.envw[1] = __float_as_int(sy_);
         }
         if (!TSC && lane_on) {
-            el.a0[il] = a0;
-            el.a1[il] = a1;
+            if constexpr (!SAMPLE) {
+                el.a0[il] = a0;
+                el.a1[il] = a1;
+            }
             el.route[il] = route_l;
             el.x[il] = x0; el.y[il] = y0; el.v[il] = v0; el.h[il] = h0;
             el.acc[il] = acc0; el.steer[il] = steer0; el.prev_dist[il] = pd0;
@@ -1968,7 +2054,7 @@ __device__ __forceinline__ CarsCtx cars_pre(const SimParams& p, const StepInputs
         // a later sub-step: the counters from the carry, the NPC survivors from nl (lane = slot)
         step_no = rc->step_prev + 1;
         prev_npcs = TRAFFIC ? rc->npcs_prev : 0;
-        if constexpr (SEQ && !kSeqEarlyLoad) {
+        if constexpr (SEQ && !kSeqEarlyLoad && !SAMPLE) {
             // this sub-step's own action row (in.actions is its row), the only ego load of a later
             // sub-step (in the experiment build the kernel's loop has issued it ahead of the previous
             // sub-step's row stores and left it in el.a0 / el.a1)
@@ -2651,6 +2737,20 @@ struct KeepLeafArgs {
     KeepOuts k;
 };
 static_assert(sizeof(KeepLeafArgs) <= 4096 && sizeof(KeepArgs) <= 4096, "the kernel argument segment");
+// SAMPLE (mev_sample_plans): EVAL or LEAF whose candidate c = g * samples + j starts from live env
+// roots[g] (ev.roots is [groups]) and draws its own actions (sample_action; in.actions is null).
+// The wave fills the rows of actions_out after the sub-step it stopped at -- every row of a
+// candidate without a root -- in the epilogue that zeroes the *_seq rows: still the formula's
+// values.  The argument struct begins with EvalArgs (SampleArgs) or LeafArgs (SampleLeafArgs).
+struct SampleArgs {
+    EvalArgs e;
+    SampleIn m;
+};
+struct SampleLeafArgs {
+    LeafArgs l;
+    SampleIn m;
+};
+static_assert(sizeof(SampleLeafArgs) <= 4096 && sizeof(SampleArgs) <= 4096, "the kernel argument segment");
 // KEEP: candidate c's stop state into slot dst_slots[c] of k.dst, by every lane of the wave (c, the
 // slot and the root src are wave-uniform).  The values are taken where the next sub-step would read
 // them: cars_pre's respawns were the last writes of the car LDS' state fields (cars_post only reads
@@ -2707,24 +2807,28 @@ __device__ __forceinline__ void keep_state(const KeepOuts& k, const SimParams& p
 }
 // (four waves per SIMD, as k_step: 4096 envs are one round of single-wave workgroups on 256 CUs;
 // with the NPC phase 128 VGPRs would spill to scratch: two)
-template <bool TRAFFIC, bool SEQ = false, bool EVAL = false, bool LEAF = false, bool KEEP = false>
+template <bool TRAFFIC, bool SEQ = false, bool EVAL = false, bool LEAF = false, bool KEEP = false, bool SAMPLE = false>
 __global__ __launch_bounds__(WAVE, TRAFFIC ? 2 : 4) void k_cars_repeat(
     typename std::conditional<
-        KEEP, typename std::conditional<LEAF, KeepLeafArgs, KeepArgs>::type,
+        SAMPLE, typename std::conditional<LEAF, SampleLeafArgs, SampleArgs>::type,
         typename std::conditional<
-            LEAF, LeafArgs,
-            typename std::conditional<EVAL, EvalArgs,
-                                      typename std::conditional<SEQ, SeqArgs, RepeatArgs>::type>::type>::type>::type
-        args) {
+            KEEP, typename std::conditional<LEAF, KeepLeafArgs, KeepArgs>::type,
+            typename std::conditional<
+                LEAF, LeafArgs,
+                typename std::conditional<EVAL, EvalArgs,
+                                          typename std::conditional<SEQ, SeqArgs, RepeatArgs>::type>::type>::type>::
+            type>::type args) {
     static_assert(!EVAL || SEQ, "plan evaluation: the plan rollout's loop");
     static_assert(!LEAF || EVAL, "leaf observations: a plan evaluation");
     static_assert(!KEEP || EVAL, "kept stop states: a plan evaluation");
+    static_assert(!SAMPLE || (EVAL && !KEEP), "sampled actions: a plan evaluation from the live batch");
+    using SampleA = typename std::conditional<LEAF, SampleLeafArgs, SampleArgs>::type;
     extern __shared__ __align__(16) unsigned char cars_lds[];
     __shared__ typename std::conditional<TRAFFIC, NpcLDS, char>::type nl_storage;
     NpcLDS* nl = nullptr;
     if constexpr (TRAFFIC) nl = &nl_storage;
     int repeat;
-    if constexpr (KEEP) repeat = reinterpret_cast<const RepeatArgs*>(&args)->repeat;
+    if constexpr (KEEP || SAMPLE) repeat = reinterpret_cast<const RepeatArgs*>(&args)->repeat;
     else if constexpr (LEAF) repeat = args.e.s.r.repeat;
     else if constexpr (EVAL) repeat = args.s.r.repeat;
     else if constexpr (SEQ) repeat = args.r.repeat;
@@ -2732,7 +2836,16 @@ __global__ __launch_bounds__(WAVE, TRAFFIC ? 2 : 4) void k_cars_repeat(
     RepCarry rc{0, repeat, 0, 0, false, 0.0f, 0, 0, nullptr, 1.0f, 0.0f, 1.0f};
     int src = 0;       // EVAL: the candidate's root (wave-uniform)
     bool bad = false;  // EVAL: a root outside [0, E): no sub-step runs
-    if constexpr (KEEP) {
+    SampleCtx sc{};    // SAMPLE: the candidate's group (wave-uniform), and whether it runs the group's mean
+    if constexpr (SAMPLE) {
+        const EvalArgs& ea = *reinterpret_cast<const EvalArgs*>(&args);
+        const int c = ea.s.r.e_begin + xcd_env((int)blockIdx.x, (int)gridDim.x);  // (without LEAF: e_begin = 0)
+        const unsigned per = (unsigned)args.m.samples;
+        sc.grp = (int)((unsigned)c / per);
+        sc.zero = args.m.mean_first != 0 && (unsigned)c == (unsigned)sc.grp * per;
+        src = __builtin_amdgcn_readfirstlane(ea.ev.roots[sc.grp]);
+        bad = (unsigned)src >= (unsigned)ea.s.r.p.E;
+    } else if constexpr (KEEP) {
         const EvalArgs& ea = *reinterpret_cast<const EvalArgs*>(&args);
         const int c = ea.s.r.e_begin + xcd_env((int)blockIdx.x, (int)gridDim.x);  // (without LEAF: e_begin = 0)
         src = __builtin_amdgcn_readfirstlane(ea.ev.roots[c]);
@@ -2769,12 +2882,14 @@ __global__ __launch_bounds__(WAVE, TRAFFIC ? 2 : 4) void k_cars_repeat(
         rc.substeps = a.substeps;
         if constexpr (SEQ) {
             const SeqRows& q = reinterpret_cast<const SeqArgs*>(&a)->rows;
-            in.actions += 2 * (size_t)s * ((size_t)rowE * p.N);
+            if constexpr (!SAMPLE) in.actions += 2 * (size_t)s * ((size_t)rowE * p.N);
             in.dt = q.dt[s];
             in.spawn_prob = q.spawn_prob[s];
         }
-        CarsCtx cx = cars_pre<TRAFFIC, false, NpcLDS, 1, false, false, true, false, 0, true, false, SEQ, EVAL, LEAF>(
-            p, in, a.out, e, el, nl, kDealClasses - 1, &rc, src);
+        if constexpr (SAMPLE) sc.in = &reinterpret_cast<const SampleA*>(&a)->m;
+        CarsCtx cx =
+            cars_pre<TRAFFIC, false, NpcLDS, 1, false, false, true, false, 0, true, false, SEQ, EVAL, LEAF, SAMPLE>(
+                p, in, a.out, e, el, nl, kDealClasses - 1, &rc, src, sc);
         wave_lds_sync();
         if (s == 0) rc.first_reset = cx.do_reset;
         if constexpr (LEAF)
@@ -2795,9 +2910,15 @@ __global__ __launch_bounds__(WAVE, TRAFFIC ? 2 : 4) void k_cars_repeat(
             const bool more = kSeqEarlyLoad && !cx.ended && s + 1 < repeat;  // (wave-uniform; row s + 1 < length)
             float na0 = 0.0f, na1 = 0.0f;
             if (more) {
-                const float* nx = a.in.actions + 2 * (row + en);
-                na0 = ldu(gmem(nx), 2 * g);
-                na1 = ldu(gmem(nx), 2 * g + 1);
+                if constexpr (SAMPLE) {
+                    const float2 nx = sample_action(sc, p.N, e, il, s + 1, lane_on);
+                    na0 = nx.x;
+                    na1 = nx.y;
+                } else {
+                    const float* nx = a.in.actions + 2 * (row + en);
+                    na0 = ldu(gmem(nx), 2 * g);
+                    na1 = ldu(gmem(nx), 2 * g + 1);
+                }
             }
             if (lane_on) {
                 if (q.reward) gmem(q.reward + row)[g] = el.rew[il];
@@ -2840,12 +2961,17 @@ __global__ __launch_bounds__(WAVE, TRAFFIC ? 2 : 4) void k_cars_repeat(
         const int e = a.r.e_begin + xcd_env((int)blockIdx.x, (int)gridDim.x);
         size_t en = (size_t)a.r.p.E * N;
         if constexpr (EVAL) en = (size_t)reinterpret_cast<const EvalArgs*>(&a)->ev.C * N;
+        if constexpr (SAMPLE) sc.in = &reinterpret_cast<const SampleA*>(&a)->m;
         if (tid < N) {
             for (int z = bad ? 0 : rc.s + 1; z < repeat; ++z) {
                 const size_t g = (size_t)z * en + (size_t)e * N + tid;
                 if (a.rows.reward) gmem(a.rows.reward)[g] = 0.0f;
                 if (a.rows.done) gmem(a.rows.done)[g] = 0;
                 if (a.rows.status) gmem(a.rows.status)[g] = 0;
+                // SAMPLE: the action rows the candidate never ran are the formula's values all the same
+                if constexpr (SAMPLE) {
+                    if (sc.in->actions_out) (void)sample_action(sc, N, e, tid, z, true);
+                }
             }
         }
         if constexpr (EVAL) {
@@ -4391,6 +4517,172 @@ hipError_t launch_expand(const SimParams& p, const StepInputs& in, int C, const 
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
+}
+
+hipError_t launch_sample(const SimParams& p, const StepInputs& in, const int32_t* roots, const SeqRows& rows, int n,
+                         const EvalOutputs& outs, const SampleIn& sm, float* leaf_obs, uint8_t* hand, int chunk,
+                         hipStream_t s) {
+    if (n < 1 || n > kMaxSeq || sm.groups < 1 || sm.samples < 1 || !roots || !sm.mean || !sm.sigma)
+        return hipErrorInvalidValue;
+    if (leaf_obs && (!hand || chunk < 1)) return hipErrorInvalidValue;
+    const int C = sm.groups * sm.samples;
+    const unsigned cars_lds = (unsigned)cars_lds_bytes(p.N, cars_k(p), true);
+    const EvalOuts eo{roots, C, outs.gamma, outs.returns, outs.substeps, outs.terminated, outs.truncated};
+    if (!leaf_obs) {
+        const SampleArgs sa{EvalArgs{SeqArgs{RepeatArgs{p, in, Outputs{}, 0, n, nullptr}, rows}, eo}, sm};
+        if (p.traffic)
+            hipLaunchKernelGGL((k_cars_repeat<true, true, true, false, false, true>), dim3(C), dim3(WAVE), cars_lds, s, sa);
+        else
+            hipLaunchKernelGGL((k_cars_repeat<false, true, true, false, false, true>), dim3(C), dim3(WAVE), cars_lds, s, sa);
+        return hipGetLastError();
+    }
+    // with leaf observations: launch_evaluate_leaves' chunks, scratch and cast
+    if (chunk > C) chunk = C;
+    const size_t cn = (size_t)chunk * p.N, S = leaf_stride(p, chunk);
+    LeafHand lf{};
+    lf.pose = reinterpret_cast<float*>(hand);
+    lf.stride = (int64_t)S;
+    lf.cand = reinterpret_cast<unsigned long long*>(hand + 4 * S * sizeof(float));
+    lf.box = reinterpret_cast<int4*>(reinterpret_cast<uint8_t*>(lf.cand) + leaf_al(cn * 16));
+    lf.alive = reinterpret_cast<uint8_t*>(lf.box) + leaf_al((size_t)chunk * p.ob_stride * sizeof(int4));
+    SimParams lp = p;
+    lp.E = chunk;
+    lp.ego = EgoSoA{};
+    lp.ego.x = lf.pose;
+    lp.ego.alive = lf.alive;
+    lp.ego.stride = lf.stride;
+    lp.ob_box = lf.box;
+    lp.ob_cand = lf.cand;
+    Outputs co{};
+    co.obs = leaf_obs;
+    co.obs_ld = p.D;
+    for (int c0 = 0; c0 < C; c0 += chunk) {
+        const int nc = C - c0 < chunk ? C - c0 : chunk;
+        lf.c0 = c0;
+        const SampleLeafArgs la{LeafArgs{EvalArgs{SeqArgs{RepeatArgs{p, in, co, c0, n, nullptr}, rows}, eo}, lf}, sm};
+        if (p.traffic)
+            hipLaunchKernelGGL((k_cars_repeat<true, true, true, true, false, true>), dim3(nc), dim3(WAVE), cars_lds, s, la);
+        else
+            hipLaunchKernelGGL((k_cars_repeat<false, true, true, true, false, true>), dim3(nc), dim3(WAVE), cars_lds, s, la);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+        Outputs lo = co;
+        lo.obs = leaf_obs + (size_t)c0 * p.N * p.D;
+        e = launch_lidar(lp, lo, 0, nc * p.N, s);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+// mev_update_plans: workgroup = group g of `samples` candidates c = g * samples + j.  LDS: the
+// scores, the rank order and (mode 1) the weights, 4 bytes each per candidate.
+//  1. key[j] = the score (thread per j), non-finite -> -FLT_MAX.
+//  2. mode 0: rank counting -- j's rank is the number of l that rank before it (key[l] > key[j], or
+//     equal and l < j; -0.0f == +0.0f) -- ord[rank] = j: a permutation, every slot written once.
+//     mode 1 needs the first-ranked candidate only: a per-thread scan and one pass over the threads.
+//  3. thread per (s, i, k): the sums in the stated order (elites in rank order / candidates in j
+//     order), plain f32 multiply-then-add (the file is compiled without contraction), correctly
+//     rounded divide and sqrtf.  mode 1's expf is the device library's (documented within 1 ulp).
+constexpr int kUpdateBlock = 256;
+__global__ __launch_bounds__(kUpdateBlock) void k_update_plans(UpdateArgs u) {
+    extern __shared__ __align__(16) unsigned char upd_lds[];
+    const int K = u.samples, g = blockIdx.x, t = threadIdx.x, N = u.N;
+    float* key = reinterpret_cast<float*>(upd_lds);
+    int* ord = reinterpret_cast<int*>(upd_lds) + K;
+    float* w = reinterpret_cast<float*>(upd_lds) + 2 * (size_t)K;
+    __shared__ float red_key[kUpdateBlock];
+    __shared__ int red_j[kUpdateBlock];
+    const size_t c0 = (size_t)g * K;
+    for (int j = t; j < K; j += kUpdateBlock) {
+        float sc;
+        if (u.scores) {
+            sc = u.scores[c0 + j];
+        } else {
+            sc = 0.0f;
+            for (int i = 0; i < N; ++i) sc = sc + u.returns[(c0 + j) * N + i];
+        }
+        if (!(fabsf(sc) <= FLT_MAX)) sc = -FLT_MAX;
+        key[j] = sc;
+    }
+    __syncthreads();
+    const bool elites = u.mode == 0;
+    const int M = elites ? u.elites : K;
+    if (elites) {
+        for (int j = t; j < K; j += kUpdateBlock) {
+            const float kj = key[j];
+            int rank = 0;
+            for (int l = 0; l < K; ++l) {
+                const float kl = key[l];
+                rank += (kl > kj || (kl == kj && l < j)) ? 1 : 0;
+            }
+            ord[rank] = j;
+        }
+    } else {
+        float bk = -FLT_MAX;
+        int bj = K;
+        for (int j = t; j < K; j += kUpdateBlock) {  // (ascending j: a strict > keeps the lower one)
+            if (bj == K || key[j] > bk) { bk = key[j]; bj = j; }
+        }
+        red_key[t] = bk;
+        red_j[t] = bj;
+        __syncthreads();
+        if (t == 0) {
+            for (int q = 1; q < kUpdateBlock; ++q)
+                if (red_j[q] < K && (red_key[q] > bk || (red_key[q] == bk && red_j[q] < bj))) { bk = red_key[q]; bj = red_j[q]; }
+            ord[0] = bj;
+        }
+    }
+    __syncthreads();
+    const int first = ord[0];
+    const float top = key[first];
+    if (t == 0) {
+        if (u.best) u.best[g] = (int)c0 + first;
+        if (u.best_score) u.best_score[g] = top;
+    }
+    if (elites && u.order)
+        for (int r = t; r < M; r += kUpdateBlock) u.order[(size_t)g * M + r] = (int)c0 + ord[r];
+    float W = 0.0f;
+    if (!elites) {
+        for (int j = t; j < K; j += kUpdateBlock) w[j] = expf((key[j] - top) * u.inv_temperature);
+        __syncthreads();
+        for (int j = 0; j < K; ++j) W = W + w[j];  // (every thread the same in-order sum)
+        if (u.weights)
+            for (int j = t; j < K; j += kUpdateBlock) u.weights[c0 + j] = w[j] / W;
+    }
+    if (!u.new_mean && !u.new_sigma) return;
+    const int per = N * 2, cells = u.n * per;            // (s, i, k) cells of the group
+    const size_t row = (size_t)u.groups * K * per;       // floats per sub-step row of actions
+    for (int q = t; q < cells; q += kUpdateBlock) {
+        const int s = q / per, ik = q - s * per;
+        const float* a = u.actions + (size_t)s * row + c0 * per + ik;  // + j * per: candidate j's element
+        float sum = 0.0f, mean, dev = 0.0f;
+        if (elites) {
+            for (int r = 0; r < M; ++r) sum = sum + a[(size_t)ord[r] * per];
+            mean = sum / (float)M;
+            for (int r = 0; r < M; ++r) {
+                const float d = a[(size_t)ord[r] * per] - mean;
+                dev = dev + d * d;
+            }
+            dev = dev / (float)M;
+        } else {
+            for (int j = 0; j < K; ++j) sum = sum + w[j] * a[(size_t)j * per];
+            mean = sum / W;
+            for (int j = 0; j < K; ++j) {
+                const float d = a[(size_t)j * per] - mean;
+                dev = dev + w[j] * d * d;
+            }
+            dev = dev / W;
+        }
+        const size_t o = ((size_t)s * u.groups + g) * per + ik;
+        if (u.new_mean) u.new_mean[o] = mean;
+        if (u.new_sigma) u.new_sigma[o] = fmaxf(sqrtf(dev), u.sigma_min);
+    }
+}
+
+hipError_t launch_update_plans(const UpdateArgs& u, hipStream_t s) {
+    if (u.groups < 1 || u.samples < 1 || u.n < 1 || !u.actions || (!u.scores && !u.returns)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_update_plans, dim3((unsigned)u.groups), dim3(kUpdateBlock), 3 * (size_t)u.samples * 4, s, u);
+    return hipGetLastError();
 }
 
 // mev_pool_capture / mev_pool_get_state: block i copies slot from[i] of src into slot to[i] of dst,

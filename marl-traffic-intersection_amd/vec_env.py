@@ -331,6 +331,96 @@ class VecIntersectionEnv:
         return self.evaluate_plans(actions, roots, dt, gamma, spawn_route, copy, leaf_obs,
                                    _expand=dict(dst=dst, dst_slots=dst_slots, src=src, counter_offset=counter_offset))
 
+    def _dev_tensor(self, x, dtype):
+        """x as a contiguous tensor of `dtype` on this env's device (torch backend)."""
+        t = self._torch
+        if isinstance(x, t.Tensor) and x.is_cuda and x.dtype == dtype and x.is_contiguous():
+            if x.device.index != self.device_index:
+                raise ValueError("an argument is on another device")
+            return x
+        return t.as_tensor(x, dtype=dtype, device=self._out["obs"].device).contiguous()
+
+    def sample_plans(self, mean, sigma, roots, samples: int, dt=1.0 / 60.0, gamma: float = 1.0, lo=(-1.0, -1.0),
+                     hi=(1.0, 1.0), seed: int = 0, counter: int = 0, mean_first: bool = False, leaf_obs: bool = False,
+                     spawn_route=None, copy: bool = False):
+        """evaluate_plans whose C = G * samples candidates draw their own actions on the device
+        (Handle.sample_plans): mean, sigma [T, G, N, 2], roots [G] -> evaluate_plans' dict plus
+        actions_out [T, C, N, 2], the clamped actions the candidates ran.  The noise is the stated
+        Irwin-Hall approximation of a unit Gaussian from the Philox stream (seed, counter): pass a
+        new counter per iteration.  The same buffers (kept per (T, C)) and stream rules as
+        evaluate_plans; the env's state, last outputs and random stream stay as they are."""
+        K, N = int(samples), self.num_agents
+        if self.backend == "torch":
+            t = self._torch
+            self._bind_stream()
+            m, s, r = self._dev_tensor(mean, t.float32), self._dev_tensor(sigma, t.float32), self._dev_tensor(roots, t.int32)
+            if r.dim() != 1 or m.dim() != 4 or tuple(m.shape[1:]) != (r.shape[0], N, 2) or s.shape != m.shape:
+                raise ValueError(f"mean and sigma must be [T, G, {N}, 2] and roots [G], got {tuple(m.shape)}, "
+                                 f"{tuple(s.shape)} and {tuple(r.shape)}")
+            T, G = int(m.shape[0]), int(r.shape[0])
+            o = self._sample_out(T, G * K, leaf_obs)
+            sp = None
+            if spawn_route is not None:
+                sp = self._dev_tensor(spawn_route, t.int32)
+                if tuple(sp.shape) != (T, G * K):
+                    raise ValueError(f"spawn_route must be [{T}][{G * K}], got {tuple(sp.shape)}")
+            self._h.sample_plans(m, s, r, K, dt, gamma, lo, hi, seed, counter, mean_first, leaf_obs, sp, out=o,
+                                 device=True, groups=G, length=T)
+            return {k: v.clone() for k, v in o.items()} if copy else o
+        shape = np.shape(mean)
+        if len(shape) != 4:
+            raise ValueError(f"mean must be [T, G, {N}, 2], got {shape}")
+        o = self._sample_out(int(shape[0]), int(shape[1]) * K, leaf_obs)
+        self._h.sample_plans(mean, sigma, roots, K, dt, gamma, lo, hi, seed, counter, mean_first, leaf_obs, spawn_route,
+                             out=o)
+        return {k: v.copy() for k, v in o.items()} if copy else o
+
+    def _sample_out(self, T, C, leaf):
+        """evaluate_plans' buffers of (T, C) with the actions_out buffer of that shape beside them."""
+        o = self._eval_out(T, C, leaf)
+        ao = self._out_eval.get((T, C, "actions"))
+        if ao is None:
+            shape = (T, C, self.num_agents, 2)
+            if self.backend == "torch":
+                ao = self._torch.zeros(shape, dtype=self._torch.float32, device=self._out["obs"].device)
+            else:
+                ao = np.zeros(shape, np.float32)
+            self._out_eval[(T, C, "actions")] = ao
+        return dict(o, actions_out=ao)
+
+    def update_plans(self, actions, samples: int, scores=None, returns=None, mode: str = "elites", elites=None,
+                     temperature: float = 1.0, sigma_min: float = 0.0):
+        """Rank each group's candidates and refit the sampling distribution (Handle.update_plans):
+        actions [T, G * samples, N, 2] (sample_plans' actions_out), scores [C] or returns [C, N] ->
+        dict of new_mean / new_sigma [T, G, N, 2] (the next sample_plans' input), best / best_score
+        [G] and order [G, elites] ("elites") or weights [C] ("softmax").  Fresh arrays every call;
+        torch: stream-ordered on the current stream, no synchronisation."""
+        K, N = int(samples), self.num_agents
+        if self.backend != "torch":
+            return self._h.update_plans(actions, K, scores, returns, mode, elites, temperature, sigma_min)
+        t = self._torch
+        self._bind_stream()
+        a = self._dev_tensor(actions, t.float32)
+        if a.dim() != 4 or tuple(a.shape[2:]) != (N, 2) or a.shape[1] % K:
+            raise ValueError(f"actions must be [T, G * {K}, {N}, 2], got {tuple(a.shape)}")
+        T, C = int(a.shape[0]), int(a.shape[1])
+        G = C // K
+        sc = None if scores is None else self._dev_tensor(scores, t.float32)
+        rt = None if returns is None else self._dev_tensor(returns, t.float32)
+        if (sc is not None and tuple(sc.shape) != (C,)) or (rt is not None and tuple(rt.shape) != (C, N)):
+            raise ValueError(f"scores must be [{C}] and returns [{C}, {N}]")
+        M = int(elites) if elites is not None else max(1, K // 4)
+        dev = a.device
+        o = {"new_mean": t.empty((T, G, N, 2), dtype=t.float32, device=dev),
+             "new_sigma": t.empty((T, G, N, 2), dtype=t.float32, device=dev),
+             "best": t.empty((G,), dtype=t.int32, device=dev), "best_score": t.empty((G,), dtype=t.float32, device=dev)}
+        if mode == "elites":
+            o["order"] = t.empty((G, M), dtype=t.int32, device=dev)
+        else:
+            o["weights"] = t.empty((C,), dtype=t.float32, device=dev)
+        self._h.update_plans(a, K, sc, rt, mode, M, temperature, sigma_min, out=o, device=True, groups=G, length=T)
+        return o
+
     def _eval_out(self, T, C, leaf=False):
         """The output buffers of evaluate_plans, kept per (T, C); leaf: with the leaf_obs buffer of
         that shape (made at the first call that asks for it; the default call's dict never has it)."""
