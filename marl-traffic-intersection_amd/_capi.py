@@ -637,6 +637,67 @@ class Handle:
         _check(self._lib.mev_step_sequence(self._h, ctypes.byref(a)))
         return out
 
+    def _plan_args(self, a, need, lead, roots, rl, per, count, length, dt, gamma, spawn_route, out, device, flags,
+                   leaf_obs, extra=()):
+        """The part every plan call shares, filled into `a` (a MevEvaluateArgs; `actions` is the
+        caller's): roots [R] with R = `count` or roots.shape[0] (`rl`: R's letter in the messages), C =
+        R * per candidates, T = `length` or lead.shape[0] (`lead`: the caller's actions or mean; `need`:
+        the message when device mode cannot tell T or R), spawn_route [T][C], dt and the outputs --
+        _EVAL_OUTS, `extra` in the same form, leaf_obs if asked for; host mode creates what an empty
+        `out` lacks and checks shapes and dtypes.  Returns T, C, R, out and the arrays `a` points into,
+        which the caller holds until the C call has returned."""
+        N = self.N
+        if device:
+            if length is None:
+                length = getattr(lead, "shape", (None,))[0]
+            if count is None:
+                count = getattr(roots, "shape", (None,))[0]
+            if length is None or count is None:
+                raise ValueError(need)
+            T, R = int(length), int(count)
+            C = R * per
+            out = out if out is not None else {}
+        else:
+            roots = np.ascontiguousarray(roots, np.int32)
+            if roots.ndim != 1:
+                raise ValueError(f"roots must be [{rl}], got {roots.shape}")
+            R = int(roots.shape[0]) if count is None else int(count)
+            T = (int(lead.shape[0]) if lead.ndim else 0) if length is None else int(length)
+            C = R * per
+            if roots.shape != (R,):
+                raise ValueError(f"roots must be [{R}], got {roots.shape}")
+            if spawn_route is not None:
+                spawn_route = np.ascontiguousarray(np.asarray(spawn_route, np.int32))
+                if spawn_route.shape != (T, C):
+                    raise ValueError(f"spawn_route must be [{T}][{C}], got {spawn_route.shape}")
+            out = out if out is not None else {}
+            outs = _EVAL_OUTS + tuple(extra)
+            if not out:
+                for k, dtype, shape in outs:
+                    out[k] = np.zeros(shape(T, C, N), dtype)
+            if leaf_obs:
+                if out.get("leaf_obs") is None:
+                    out["leaf_obs"] = np.zeros((C, N, self.D), np.float32)
+                outs += (("leaf_obs", np.float32, lambda T, C, N: (C, N, self.D)),)
+            for k, dtype, shape in outs:
+                if out.get(k) is not None and (out[k].shape != shape(T, C, N) or out[k].dtype != dtype):
+                    raise ValueError(f"{k} must be {np.dtype(dtype).name} {list(shape(T, C, N))}, got {out[k].shape}")
+        a.roots, a.spawn_route = _ptr(roots), _ptr(spawn_route)
+        a.candidates, a.length, a.gamma = C, T, float(gamma)
+        dts = None
+        if np.ndim(dt) == 0:
+            a.dt = float(dt)
+        else:
+            dts = np.ascontiguousarray(dt, np.float32).reshape(-1)
+            if dts.size != T:
+                raise ValueError(f"dt must be a float or {T} floats, got {dts.size}")
+            a.dt = float(dts[0]) if T else 0.0
+            a.dt_seq = dts.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
+        for k, _, _ in _EVAL_OUTS:
+            setattr(a, k, _ptr(out.get(k)))
+        a.flags = (MEV_DEVICE_PTRS if device else 0) | int(flags)
+        return T, C, R, out, (roots, spawn_route, dts)
+
     def evaluate_plans(self, actions, roots, dt=1.0 / 60.0, gamma: float = 1.0, spawn_route=None,
                        out: Optional[dict] = None, device: bool = False, candidates: Optional[int] = None,
                        length: Optional[int] = None, flags: int = 0, leaf_obs: bool = False, _expand=None):
@@ -651,59 +712,16 @@ class Handle:
         leaf_obs=True (mev_evaluate_leaves): the result gains `leaf_obs` [C][N][obs_dim], the
         observation of the state each candidate stopped at (head and LiDAR block; every float
         written).  In device mode out["leaf_obs"] must be there; the other outputs are optional."""
-        N = self.N
-        if device:
-            if length is None:
-                length = getattr(actions, "shape", (None,))[0]
-            if candidates is None:
-                candidates = getattr(roots, "shape", (None,))[0]
-            if length is None or candidates is None:
-                raise ValueError("evaluate_plans needs actions [T][C][N][2] and roots [C] (or length=T, candidates=C)")
-            T, C = int(length), int(candidates)
-            out = out if out is not None else {}
-        else:
+        if not device:
             actions = np.ascontiguousarray(actions, np.float32)
-            roots = np.ascontiguousarray(roots, np.int32)
-            if roots.ndim != 1:
-                raise ValueError(f"roots must be [C], got {roots.shape}")
-            C = int(roots.shape[0]) if candidates is None else int(candidates)
-            T = (int(actions.shape[0]) if actions.ndim else 0) if length is None else int(length)
-            if roots.shape != (C,):
-                raise ValueError(f"roots must be [{C}], got {roots.shape}")
-            if actions.shape != (T, C, N, 2):
-                raise ValueError(f"actions must be [{T}][{C}][{N}][2], got {actions.shape}")
-            if spawn_route is not None:
-                spawn_route = np.ascontiguousarray(np.asarray(spawn_route, np.int32))
-                if spawn_route.shape != (T, C):
-                    raise ValueError(f"spawn_route must be [{T}][{C}], got {spawn_route.shape}")
-            out = out if out is not None else {}
-            if not out:
-                for k, dtype, shape in _EVAL_OUTS:
-                    out[k] = np.zeros(shape(T, C, N), dtype)
-            for k, dtype, shape in _EVAL_OUTS:
-                if out.get(k) is not None and (out[k].shape != shape(T, C, N) or out[k].dtype != dtype):
-                    raise ValueError(f"{k} must be {np.dtype(dtype).name} {list(shape(T, C, N))}, got {out[k].shape}")
-            if leaf_obs:
-                if out.get("leaf_obs") is None:
-                    out["leaf_obs"] = np.zeros((C, N, self.D), np.float32)
-                if out["leaf_obs"].shape != (C, N, self.D) or out["leaf_obs"].dtype != np.float32:
-                    raise ValueError(f"leaf_obs must be float32 {[C, N, self.D]}, got {out['leaf_obs'].shape}")
         la = MevLeafArgs()
         a = la.eval
-        a.actions, a.roots, a.spawn_route = _ptr(actions), _ptr(roots), _ptr(spawn_route)
-        a.candidates, a.length, a.gamma = C, T, float(gamma)
-        dts = None
-        if np.ndim(dt) == 0:
-            a.dt = float(dt)
-        else:
-            dts = np.ascontiguousarray(dt, np.float32).reshape(-1)
-            if dts.size != T:
-                raise ValueError(f"dt must be a float or {T} floats, got {dts.size}")
-            a.dt = float(dts[0]) if T else 0.0
-            a.dt_seq = dts.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
-        for k, _, _ in _EVAL_OUTS:
-            setattr(a, k, _ptr(out.get(k)))
-        a.flags = (MEV_DEVICE_PTRS if device else 0) | int(flags)
+        T, C, _, out, _keep = self._plan_args(
+            a, "evaluate_plans needs actions [T][C][N][2] and roots [C] (or length=T, candidates=C)", actions, roots,
+            "C", 1, candidates, length, dt, gamma, spawn_route, out, device, flags, leaf_obs)
+        if not device and actions.shape != (T, C, self.N, 2):
+            raise ValueError(f"actions must be [{T}][{C}][{self.N}][2], got {actions.shape}")
+        a.actions = _ptr(actions)
         if _expand is not None:
             xa = MevExpandArgs()
             xa.eval = a
@@ -755,62 +773,16 @@ class Handle:
         array is a device tensor/pointer and only the outputs present in `out` are written; T and G
         are mean.shape[0] and roots.shape[0] (or `length` / `groups` for raw pointers)."""
         N, K = self.N, int(samples)
-        if device:
-            if length is None:
-                length = getattr(mean, "shape", (None,))[0]
-            if groups is None:
-                groups = getattr(roots, "shape", (None,))[0]
-            if length is None or groups is None:
-                raise ValueError("sample_plans needs mean [T][G][N][2] and roots [G] (or length=T, groups=G)")
-            T, G = int(length), int(groups)
-            C = G * K
-            out = out if out is not None else {}
-        else:
+        if not device:
             mean = np.ascontiguousarray(mean, np.float32)
             sigma = np.ascontiguousarray(sigma, np.float32)
-            roots = np.ascontiguousarray(roots, np.int32)
-            if roots.ndim != 1:
-                raise ValueError(f"roots must be [G], got {roots.shape}")
-            G = int(roots.shape[0]) if groups is None else int(groups)
-            T = (int(mean.shape[0]) if mean.ndim else 0) if length is None else int(length)
-            C = G * K
-            if roots.shape != (G,):
-                raise ValueError(f"roots must be [{G}], got {roots.shape}")
-            if mean.shape != (T, G, N, 2) or sigma.shape != mean.shape:
-                raise ValueError(f"mean and sigma must be [{T}][{G}][{N}][2], got {mean.shape} and {sigma.shape}")
-            if spawn_route is not None:
-                spawn_route = np.ascontiguousarray(np.asarray(spawn_route, np.int32))
-                if spawn_route.shape != (T, C):
-                    raise ValueError(f"spawn_route must be [{T}][{C}], got {spawn_route.shape}")
-            out = out if out is not None else {}
-            if not out:
-                for k, dtype, shape in _EVAL_OUTS:
-                    out[k] = np.zeros(shape(T, C, N), dtype)
-                out["actions_out"] = np.zeros((T, C, N, 2), np.float32)
-            checks = list(_EVAL_OUTS) + [("actions_out", np.float32, lambda T, C, N: (T, C, N, 2))]
-            if leaf_obs:
-                if out.get("leaf_obs") is None:
-                    out["leaf_obs"] = np.zeros((C, N, self.D), np.float32)
-                checks.append(("leaf_obs", np.float32, lambda T, C, N: (C, N, self.D)))
-            for k, dtype, shape in checks:
-                if out.get(k) is not None and (out[k].shape != shape(T, C, N) or out[k].dtype != dtype):
-                    raise ValueError(f"{k} must be {np.dtype(dtype).name} {list(shape(T, C, N))}, got {out[k].shape}")
         sa = MevSampleArgs()
-        a = sa.eval
-        a.roots, a.spawn_route = _ptr(roots), _ptr(spawn_route)
-        a.candidates, a.length, a.gamma = C, T, float(gamma)
-        dts = None
-        if np.ndim(dt) == 0:
-            a.dt = float(dt)
-        else:
-            dts = np.ascontiguousarray(dt, np.float32).reshape(-1)
-            if dts.size != T:
-                raise ValueError(f"dt must be a float or {T} floats, got {dts.size}")
-            a.dt = float(dts[0]) if T else 0.0
-            a.dt_seq = dts.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
-        for k, _, _ in _EVAL_OUTS:
-            setattr(a, k, _ptr(out.get(k)))
-        a.flags = (MEV_DEVICE_PTRS if device else 0) | int(flags)
+        T, C, G, out, _keep = self._plan_args(
+            sa.eval, "sample_plans needs mean [T][G][N][2] and roots [G] (or length=T, groups=G)", mean, roots, "G", K,
+            groups, length, dt, gamma, spawn_route, out, device, flags, leaf_obs,
+            extra=(("actions_out", np.float32, lambda T, C, N: (T, C, N, 2)),))
+        if not device and (mean.shape != (T, G, N, 2) or sigma.shape != mean.shape):
+            raise ValueError(f"mean and sigma must be [{T}][{G}][{N}][2], got {mean.shape} and {sigma.shape}")
         sa.leaf_obs = _ptr(out.get("leaf_obs")) if leaf_obs else None
         sa.mean, sa.sigma, sa.actions_out = _ptr(mean), _ptr(sigma), _ptr(out.get("actions_out"))
         sa.lo = (ctypes.c_float * 2)(*[float(v) for v in lo])

@@ -1615,12 +1615,25 @@ int mev_step_sequence(mev_handle* h, const mev_sequence_args* sa) {
 // LiDAR hand-off lives in a per-handle scratch that only grows, to kLeafHandCap at the most: a call
 // with more candidates than the cap holds (or than MEV_LEAF_CHUNK) goes through in chunks.
 constexpr size_t kLeafHandCap = size_t(64) << 20;
+// a device block of the handle that only grows (the staging block, the leaf scratch): at least `need` bytes
+static int grow_block(mev_handle* h, uint8_t** block, size_t* cap, size_t need) {
+    if (need <= *cap) return MEV_OK;
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (*block) (void)hipFree(*block);
+    *block = nullptr;
+    *cap = 0;
+    const hipError_t err = hipMalloc(reinterpret_cast<void**>(block), need);
+    if (err != hipSuccess) return fail(MEV_E_NOMEM, std::string("device allocation failed: ") + hipGetErrorString(err));
+    *cap = need;
+    return MEV_OK;
+}
 // xp: mev_expand_plans' additions (null: the two evaluation calls) -- the candidates' roots are slots
 // of xp->src when that is set, and their stop states go to slots xp->dst_slots of xp->dst.
 // sm: mev_sample_plans' additions (null: the other calls) -- no actions array: the candidates draw
 // their rows from sm->mean / sm->sigma, roots is [groups], and the rows go to sm->actions_out.
-static int evaluate(mev_handle* h, const mev_evaluate_args* ea, float* leaf_obs, bool leaves,
-                    const mev_expand_args* xp = nullptr, const mev_sample_args* sm = nullptr) {
+static int evaluate(mev_handle* h, const mev_evaluate_args* ea, float* leaf_obs, const mev_expand_args* xp = nullptr,
+                    const mev_sample_args* sm = nullptr) {
+    const bool leaves = leaf_obs != nullptr;
     const char* fn = sm ? "mev_sample_plans" : xp ? "mev_expand_plans" : leaves ? "mev_evaluate_leaves" : "mev_evaluate_plans";
     if (xp) {
         if (!xp->dst || !xp->dst_slots) return fail(MEV_E_INVALID, "dst and dst_slots required");
@@ -1708,16 +1721,7 @@ static int evaluate(mev_handle* h, const mev_evaluate_args* ea, float* leaf_obs,
         if (fit < 1) fit = 1;
         chunk = int(h->leaf_chunk ? size_t(h->leaf_chunk) : fit);
         if (size_t(chunk) > C) chunk = int(C);
-        const size_t need = mev::leaf_hand_bytes(h->sp, chunk);
-        if (need > h->leaf_cap) {
-            HIP_TRY(hipStreamSynchronize(h->stream));
-            if (h->d_leaf) (void)hipFree(h->d_leaf);
-            h->d_leaf = nullptr;
-            h->leaf_cap = 0;
-            const hipError_t err = hipMalloc(reinterpret_cast<void**>(&h->d_leaf), need);
-            if (err != hipSuccess) return fail(MEV_E_NOMEM, std::string("device allocation failed: ") + hipGetErrorString(err));
-            h->leaf_cap = need;
-        }
+        if (int r = grow_block(h, &h->d_leaf, &h->leaf_cap, mev::leaf_hand_bytes(h->sp, chunk))) return r;
     }
     mev::SampleIn si{};  // (sm) the device view of the sampling arguments
     if (sm)
@@ -1750,15 +1754,7 @@ static int evaluate(mev_handle* h, const mev_evaluate_args* ea, float* leaf_obs,
         const size_t o_term = take(ea->terminated != nullptr, C), o_trunc = take(ea->truncated != nullptr, C);
         const size_t o_obs = take(leaves, obs_bytes);
         const size_t o_dst = take(xp != nullptr, C * sizeof(int32_t));
-        if (off > h->eval_cap) {
-            HIP_TRY(hipStreamSynchronize(h->stream));
-            if (h->d_eval) (void)hipFree(h->d_eval);
-            h->d_eval = nullptr;
-            h->eval_cap = 0;
-            const hipError_t err = hipMalloc(reinterpret_cast<void**>(&h->d_eval), off);
-            if (err != hipSuccess) return fail(MEV_E_NOMEM, std::string("device allocation failed: ") + hipGetErrorString(err));
-            h->eval_cap = off;
-        }
+        if (int r = grow_block(h, &h->d_eval, &h->eval_cap, off)) return r;
         uint8_t* b = h->d_eval;
         if (sm) {
             HIP_TRY(hipMemcpyAsync(b + o_mean, sm->mean, ms_bytes, hipMemcpyHostToDevice, h->stream));
@@ -1789,17 +1785,10 @@ static int evaluate(mev_handle* h, const mev_evaluate_args* ea, float* leaf_obs,
             d_dst = reinterpret_cast<const int32_t*>(b + o_dst);
         }
     }
-    if (sm)
-        HIP_TRY(mev::launch_sample(h->sp, in, d_roots, rows, int(T), eo, si, leaves ? d_leaf_obs : nullptr, h->d_leaf, chunk,
-                                   h->stream));
-    else if (xp)
-        HIP_TRY(mev::launch_expand(h->sp, in, int(C), d_roots, rows, int(T), eo, xp->src ? &xp->src->st : nullptr,
-                                   xp->dst->st, d_dst, leaves ? d_leaf_obs : nullptr, h->d_leaf, chunk, h->stream));
-    else if (leaves)
-        HIP_TRY(mev::launch_evaluate_leaves(h->sp, in, int(C), d_roots, rows, int(T), eo, d_leaf_obs, h->d_leaf, chunk,
-                                            h->stream));
-    else
-        HIP_TRY(mev::launch_evaluate(h->sp, in, int(C), d_roots, rows, int(T), eo, h->stream));
+    const mev::PlanCall call{int(C), int(T), d_roots, &rows, eo, d_leaf_obs, h->d_leaf, chunk,
+                             xp && xp->src ? &xp->src->st : nullptr, xp ? &xp->dst->st : nullptr, d_dst,
+                             sm ? &si : nullptr};
+    HIP_TRY(mev::launch_plans(h->sp, in, call, h->stream));
     if (!dev) {
         auto back = [h](void* dst, const void* src, size_t bytes) {
             return dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream) : hipSuccess;
@@ -1820,7 +1809,7 @@ static int evaluate(mev_handle* h, const mev_evaluate_args* ea, float* leaf_obs,
 
 int mev_evaluate_plans(mev_handle* h, const mev_evaluate_args* ea) {
     if (!h || !ea) return fail(MEV_E_INVALID, "null argument");
-    return evaluate(h, ea, nullptr, false);
+    return evaluate(h, ea, nullptr);
 }
 
 // mev_evaluate_leaves (include/marlenv.h): mev_evaluate_plans, and the observation of the state every
@@ -1828,7 +1817,7 @@ int mev_evaluate_plans(mev_handle* h, const mev_evaluate_args* ea) {
 int mev_evaluate_leaves(mev_handle* h, const mev_leaf_args* la) {
     if (!h || !la) return fail(MEV_E_INVALID, "null argument");
     if (!la->leaf_obs) return fail(MEV_E_INVALID, "leaf_obs required");
-    return evaluate(h, &la->eval, la->leaf_obs, true);
+    return evaluate(h, &la->eval, la->leaf_obs);
 }
 
 // ---- state pools (include/marlenv.h): env states outside the live batch, in the handle's own SoA
@@ -1914,15 +1903,7 @@ int mev_pool_slots(const mev_pool* pool, int32_t* slots) {
 static int pool_stage(mev_handle* h, const int32_t* a, const int32_t* b, size_t count, const int32_t** da,
                       const int32_t** db) {
     const size_t each = (count * sizeof(int32_t) + 255) & ~size_t(255), need = 2 * each;
-    if (need > h->eval_cap) {
-        HIP_TRY(hipStreamSynchronize(h->stream));
-        if (h->d_eval) (void)hipFree(h->d_eval);
-        h->d_eval = nullptr;
-        h->eval_cap = 0;
-        const hipError_t err = hipMalloc(reinterpret_cast<void**>(&h->d_eval), need);
-        if (err != hipSuccess) return fail(MEV_E_NOMEM, std::string("device allocation failed: ") + hipGetErrorString(err));
-        h->eval_cap = need;
-    }
+    if (int r = grow_block(h, &h->d_eval, &h->eval_cap, need)) return r;
     HIP_TRY(hipMemcpyAsync(h->d_eval, a, count * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
     *da = reinterpret_cast<const int32_t*>(h->d_eval);
     if (b) {
@@ -2009,14 +1990,14 @@ int mev_pool_get_state(mev_pool* pool, const int32_t* slots, int32_t count, cons
 
 int mev_expand_plans(mev_handle* h, const mev_expand_args* xa) {
     if (!h || !xa) return fail(MEV_E_INVALID, "null argument");
-    return evaluate(h, &xa->eval, xa->leaf_obs, xa->leaf_obs != nullptr, xa);
+    return evaluate(h, &xa->eval, xa->leaf_obs, xa);
 }
 
 // mev_sample_plans (include/marlenv.h): the evaluation calls with the actions drawn by the
 // candidates' own waves (the car kernel's SAMPLE mode).
 int mev_sample_plans(mev_handle* h, const mev_sample_args* sa) {
     if (!h || !sa) return fail(MEV_E_INVALID, "null argument");
-    return evaluate(h, &sa->eval, sa->leaf_obs, sa->leaf_obs != nullptr, nullptr, sa);
+    return evaluate(h, &sa->eval, sa->leaf_obs, nullptr, sa);
 }
 
 // mev_update_plans (include/marlenv.h): the reduction over each group's candidates, k_update_plans.

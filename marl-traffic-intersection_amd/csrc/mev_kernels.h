@@ -232,8 +232,11 @@ struct SeqRows {
 };
 hipError_t launch_step_window(const SimParams& p, const StepInputs& in, const Outputs& out, int n,
                               const SeqRows* rows, int32_t* substeps, hipStream_t s);
-// Plan evaluation (mev_evaluate_plans): C candidates, candidate c rolled through a plan of n
-// sub-steps from a private copy of the live env roots[c] (k_cars_repeat<TRAFFIC, true, EVAL =
+// The four plan evaluations (mev_evaluate_plans, mev_evaluate_leaves, mev_expand_plans,
+// mev_sample_plans) are one call, launch_plans, described by a PlanCall below: the paragraphs up to
+// it say what each part of the descriptor adds.
+// Plan evaluation (mev_evaluate_plans; leaf_obs, dst and sample null): C candidates, candidate c
+// rolled through a plan of n sub-steps from a private copy of the live env roots[c] (k_cars_repeat<TRAFFIC, true, EVAL =
 // true>), and nothing of p's state, outputs or diagnostics written: one launch of C single-wave
 // workgroups, no k_lidar.  in.actions is [n][C][N][2], in.spawn_route, if given, [n][C]; the
 // Philox spawner is keyed by c with in.rng_counter + s; in.auto_reset is not read (never a
@@ -246,9 +249,7 @@ struct EvalOutputs {
     uint8_t* terminated;  // [C] flags of the sub-step the candidate stopped at
     uint8_t* truncated;   // [C]
 };
-hipError_t launch_evaluate(const SimParams& p, const StepInputs& in, int C, const int32_t* roots, const SeqRows& rows,
-                           int n, const EvalOutputs& outs, hipStream_t s);
-// Plan evaluation with leaf observations (mev_evaluate_leaves): launch_evaluate's rollout, and
+// Plan evaluation with leaf observations (mev_evaluate_leaves; leaf_obs set): the same rollout, and
 // leaf_obs [C][N][p.D] = the observation of the state each candidate stopped at
 // (k_cars_repeat<TRAFFIC, true, true, LEAF = true>, then k_lidar).  The sub-step a candidate stops
 // at writes its observation head into leaf_obs row c and publishes a LiDAR hand-off indexed by
@@ -267,9 +268,6 @@ struct LeafHand {
     int32_t c0;                   // the chunk's first candidate
 };
 size_t leaf_hand_bytes(const SimParams& p, int chunk);
-hipError_t launch_evaluate_leaves(const SimParams& p, const StepInputs& in, int C, const int32_t* roots,
-                                  const SeqRows& rows, int n, const EvalOutputs& outs, float* leaf_obs, uint8_t* hand,
-                                  int chunk, hipStream_t s);
 // A state pool (mev_pool_create): `slots` complete env states outside the live batch, structure of
 // arrays over slots in the handle's own field layout -- slot d's agent i at d * N + i, its NPC
 // slot k at d * K + k -- so a SimParams copy whose state block points here (pool_view) lets every
@@ -300,18 +298,16 @@ SimParams pool_view(const SimParams& p, const PoolState& pool);
 // either index out of range is skipped: nothing is accessed outside the blocks.
 hipError_t launch_pool_copy(const SimParams& p, const PoolState& src, const PoolState& dst, const int32_t* from,
                             const int32_t* to, int count, hipStream_t s);
-// Plan expansion (mev_expand_plans): launch_evaluate (leaf_obs null) or launch_evaluate_leaves,
+// Plan expansion (mev_expand_plans; dst set): the plan evaluation, without or with leaf observations,
 // bit for bit, with two additions (k_cars_repeat<..., KEEP = true>).  src (nullable): candidate c
 // starts from slot roots[c] of that pool instead of live env roots[c]; a root out of range or a
 // slot whose valid byte is 0 is a candidate without a root.  dst: the sub-step a candidate that
 // ran stops at stores its whole post-step state -- what the plan rollout would write back to an
 // env -- into slot dst_slots[c] of dst and sets the slot's valid byte; an index outside [0,
 // dst.slots) stores nothing.  src and dst may be one pool when no dst slot of the call is a root.
-hipError_t launch_expand(const SimParams& p, const StepInputs& in, int C, const int32_t* roots, const SeqRows& rows,
-                         int n, const EvalOutputs& outs, const PoolState* src, const PoolState& dst,
-                         const int32_t* dst_slots, float* leaf_obs, uint8_t* hand, int chunk, hipStream_t s);
-// Sampled plan evaluation (mev_sample_plans): launch_evaluate (leaf_obs null) or
-// launch_evaluate_leaves, bit for bit, whose candidates draw their own actions
+// Not together with sample.
+// Sampled plan evaluation (mev_sample_plans; sample set): the plan evaluation, without or with leaf
+// observations, bit for bit, whose candidates draw their own actions
 // (k_cars_repeat<..., SAMPLE = true>).  in.actions is not read; candidate c = g * samples + j
 // starts from live env roots[g] (roots is [groups], C = groups * samples) and takes, per sub-step
 // row s, agent i, component k, clamp(mean[s][g][i][k] + sigma[s][g][i][k] * eps[k], lo[k], hi[k])
@@ -327,9 +323,20 @@ struct SampleIn {
     uint32_t seed_lo, seed_hi, ctr_lo, ctr_hi;  // the noise stream: Philox key and counter words 0, 1
     uint32_t mean_first;                        // candidate j == 0 of every group takes eps = 0
 };
-hipError_t launch_sample(const SimParams& p, const StepInputs& in, const int32_t* roots, const SeqRows& rows, int n,
-                         const EvalOutputs& outs, const SampleIn& sm, float* leaf_obs, uint8_t* hand, int chunk,
-                         hipStream_t s);
+struct PlanCall {
+    int C, n;                  // candidates (with sample: groups * samples), sub-steps (1..kMaxSeq)
+    const int32_t* roots;      // [C], or [groups] with sample
+    const SeqRows* rows;       // the [n][C][N] arrays, dt and spawn probability per sub-step
+    EvalOutputs outs;
+    float* leaf_obs;           // [C][N][p.D] (null: no leaf observations, no k_lidar)
+    uint8_t* hand;             // with leaf_obs: the hand-off scratch, leaf_hand_bytes(p, chunk)
+    int chunk;                 // with leaf_obs: candidates per car-kernel launch and cast (>= 1)
+    const PoolState* src;      // with dst: the pool the roots are slots of (null: live envs)
+    const PoolState* dst;      // the pool that receives the stop states (null: none kept)
+    const int32_t* dst_slots;  // with dst: [C]
+    const SampleIn* sample;    // null: the actions are in.actions
+};
+hipError_t launch_plans(const SimParams& p, const StepInputs& in, const PlanCall& c, hipStream_t s);
 // Refit over candidates (mev_update_plans, k_update_plans): one workgroup per group ranks its
 // `samples` candidates by score (scores[c], or the in-order f32 sum of returns[c][0..N); a
 // non-finite score counts as -FLT_MAX; equal scores: the lower j first) and reduces the action rows

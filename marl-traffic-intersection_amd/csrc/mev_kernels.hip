@@ -2668,13 +2668,12 @@ struct RepeatArgs {
 // A later sub-step loads its own action at the top of cars_pre (an experiment build issues it
 // here, ahead of the row stores: measured slower, see kSeqEarlyLoad).  The wave
 // zeroes the rows after the sub-step it stopped at itself (no memset before the launch: one
-// launch, and device-mode callers' arrays need no preparation).  The argument struct begins
-// with RepeatArgs, so the loop reads the shared part the same way.
-struct SeqArgs {
-    RepeatArgs r;
+// launch, and device-mode callers' arrays need no preparation).  Every mode's argument struct
+// derives from the struct of the mode it adds to, so the loop reads the shared parts by name
+// (PlanArgs below chooses the type; the layout asserts after it hold the bytes in place).
+struct SeqArgs : RepeatArgs {
     SeqRows rows;
 };
-static_assert(sizeof(SeqArgs) <= 4096, "the kernel argument segment");
 // EVAL (mev_evaluate_plans, a planner's scoring pass): workgroup = candidate c, not env.  The
 // first sub-step loads the state of the live env roots[c] (cars_pre's src_e; candidates of one
 // root read the same lines: L2), the plan rollout's loop runs on that private copy, and nothing
@@ -2694,11 +2693,9 @@ struct EvalOuts {
     uint8_t* term;         // [C]
     uint8_t* trunc;        // [C]
 };
-struct EvalArgs {
-    SeqArgs s;
+struct EvalArgs : SeqArgs {
     EvalOuts ev;
 };
-static_assert(sizeof(EvalArgs) <= 4096, "the kernel argument segment");
 // LEAF (mev_evaluate_leaves): EVAL over the candidates [e_begin, e_begin + grid) of the call's C --
 // one chunk -- with the observation of the state each candidate stopped at.  Workgroup = candidate
 // c = e_begin + block; roots, actions, rows and outputs are indexed by c as before.  Every
@@ -2707,12 +2704,10 @@ static_assert(sizeof(EvalArgs) <= 4096, "the kernel argument segment");
 // out.obs_ld floats per row) and its LiDAR hand-off into slot c - e_begin of the scratch lf
 // (cars_post with LEAF), from which k_lidar casts the chunk afterwards.  A candidate without a root
 // publishes its agents as dead and zeroes its rows' head and padding columns: k_lidar zeroes a dead
-// agent's LiDAR block.  The argument struct begins with EvalArgs.
-struct LeafArgs {
-    EvalArgs e;
+// agent's LiDAR block.
+struct LeafArgs : EvalArgs {
     LeafHand lf;
 };
-static_assert(sizeof(LeafArgs) <= 4096, "the kernel argument segment");
 // KEEP (mev_expand_plans): EVAL or LEAF whose candidates may start from a slot of a state pool and
 // whose stop state is kept in one.  The SimParams of the arguments is the source's view (pool_view:
 // its state block, E = its slots), so the first sub-step's loads need nothing new; src_valid
@@ -2721,36 +2716,64 @@ static_assert(sizeof(LeafArgs) <= 4096, "the kernel argument segment");
 // candidate's rows and outputs, the state the plan rollout would write back to an env -- every ego
 // field, alive and the sizes from the car LDS (lane = agent), the NPC survivors with their sizes
 // from the NPC LDS (lane = slot, npc_writeback's order), the count, the step counter, and last the
-// valid byte -- into slot dst_slots[c] of dst; an index outside [0, dst.slots) stores nothing.  The
-// argument struct begins with EvalArgs (KeepArgs) or LeafArgs (KeepLeafArgs).
+// valid byte -- into slot dst_slots[c] of dst; an index outside [0, dst.slots) stores nothing.
+// KeepArgs adds to EvalArgs, KeepLeafArgs to LeafArgs.
 struct KeepOuts {
     PoolState dst;
     const int32_t* dst_slots;  // [C]
     const uint8_t* src_valid;  // [p.E] (nullable)
 };
-struct KeepArgs {
-    EvalArgs e;
+struct KeepArgs : EvalArgs {
     KeepOuts k;
 };
-struct KeepLeafArgs {
-    LeafArgs l;
+struct KeepLeafArgs : LeafArgs {
     KeepOuts k;
 };
-static_assert(sizeof(KeepLeafArgs) <= 4096 && sizeof(KeepArgs) <= 4096, "the kernel argument segment");
 // SAMPLE (mev_sample_plans): EVAL or LEAF whose candidate c = g * samples + j starts from live env
 // roots[g] (ev.roots is [groups]) and draws its own actions (sample_action; in.actions is null).
 // The wave fills the rows of actions_out after the sub-step it stopped at -- every row of a
 // candidate without a root -- in the epilogue that zeroes the *_seq rows: still the formula's
-// values.  The argument struct begins with EvalArgs (SampleArgs) or LeafArgs (SampleLeafArgs).
-struct SampleArgs {
-    EvalArgs e;
+// values.  SampleArgs adds to EvalArgs, SampleLeafArgs to LeafArgs.
+struct SampleArgs : EvalArgs {
     SampleIn m;
 };
-struct SampleLeafArgs {
-    LeafArgs l;
+struct SampleLeafArgs : LeafArgs {
     SampleIn m;
 };
-static_assert(sizeof(SampleLeafArgs) <= 4096 && sizeof(SampleArgs) <= 4096, "the kernel argument segment");
+// k_cars_repeat's argument type for a set of modes: the most derived struct of the chain
+//   RepeatArgs <- SeqArgs <- EvalArgs <- LeafArgs, and KEEP or SAMPLE on top of the last two.
+// (The kernel's mangled name spells this expression out, struct names and nesting: changing either
+// renames all sixteen instantiations in profiles and in comparisons of the code object.)
+template <bool SEQ, bool EVAL, bool LEAF, bool KEEP, bool SAMPLE>
+using PlanArgs = typename std::conditional<
+    SAMPLE, typename std::conditional<LEAF, SampleLeafArgs, SampleArgs>::type,
+    typename std::conditional<
+        KEEP, typename std::conditional<LEAF, KeepLeafArgs, KeepArgs>::type,
+        typename std::conditional<
+            LEAF, LeafArgs,
+            typename std::conditional<EVAL, EvalArgs,
+                                      typename std::conditional<SEQ, SeqArgs, RepeatArgs>::type>::type>::type>::
+        type>::type;
+// The layout the launchers fill and the kernel reads, held at every build: each struct is its base
+// followed by its own member, at the offsets the code object's kernarg sizes were taken from.
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Winvalid-offsetof"  // (derived, hence not standard-layout: clang defines it)
+#define MEV_ARGS_LAYOUT(T, BASE, M, SIZE)                                                   \
+    static_assert(std::is_base_of<BASE, T>::value && std::is_trivially_copyable<T>::value && \
+                      __builtin_offsetof(T, M) == sizeof(BASE) && sizeof(T) == (SIZE),      \
+                  #T ": " #BASE ", then " #M)
+static_assert(sizeof(SimParams) == 568 && sizeof(RepeatArgs) == 728 && __builtin_offsetof(RepeatArgs, p) == 0,
+              "RepeatArgs: SimParams first");
+MEV_ARGS_LAYOUT(SeqArgs, RepeatArgs, rows, 1264);
+MEV_ARGS_LAYOUT(EvalArgs, SeqArgs, ev, 1312);
+MEV_ARGS_LAYOUT(LeafArgs, EvalArgs, lf, 1360);
+MEV_ARGS_LAYOUT(KeepArgs, EvalArgs, k, 1424);
+MEV_ARGS_LAYOUT(KeepLeafArgs, LeafArgs, k, 1472);
+MEV_ARGS_LAYOUT(SampleArgs, EvalArgs, m, 1384);
+MEV_ARGS_LAYOUT(SampleLeafArgs, LeafArgs, m, 1432);
+#undef MEV_ARGS_LAYOUT
+#pragma clang diagnostic pop
+static_assert(sizeof(KeepLeafArgs) <= 4096, "the kernel argument segment (the largest of the chain)");
 // KEEP: candidate c's stop state into slot dst_slots[c] of k.dst, by every lane of the wave (c, the
 // slot and the root src are wave-uniform).  The values are taken where the next sub-step would read
 // them: cars_pre's respawns were the last writes of the car LDS' state fields (cars_post only reads
@@ -2808,85 +2831,63 @@ __device__ __forceinline__ void keep_state(const KeepOuts& k, const SimParams& p
 // (four waves per SIMD, as k_step: 4096 envs are one round of single-wave workgroups on 256 CUs;
 // with the NPC phase 128 VGPRs would spill to scratch: two)
 template <bool TRAFFIC, bool SEQ = false, bool EVAL = false, bool LEAF = false, bool KEEP = false, bool SAMPLE = false>
-__global__ __launch_bounds__(WAVE, TRAFFIC ? 2 : 4) void k_cars_repeat(
-    typename std::conditional<
-        SAMPLE, typename std::conditional<LEAF, SampleLeafArgs, SampleArgs>::type,
-        typename std::conditional<
-            KEEP, typename std::conditional<LEAF, KeepLeafArgs, KeepArgs>::type,
-            typename std::conditional<
-                LEAF, LeafArgs,
-                typename std::conditional<EVAL, EvalArgs,
-                                          typename std::conditional<SEQ, SeqArgs, RepeatArgs>::type>::type>::type>::
-            type>::type args) {
+__global__ __launch_bounds__(WAVE, TRAFFIC ? 2 : 4) void k_cars_repeat(PlanArgs<SEQ, EVAL, LEAF, KEEP, SAMPLE> args) {
     static_assert(!EVAL || SEQ, "plan evaluation: the plan rollout's loop");
     static_assert(!LEAF || EVAL, "leaf observations: a plan evaluation");
     static_assert(!KEEP || EVAL, "kept stop states: a plan evaluation");
     static_assert(!SAMPLE || (EVAL && !KEEP), "sampled actions: a plan evaluation from the live batch");
-    using SampleA = typename std::conditional<LEAF, SampleLeafArgs, SampleArgs>::type;
+    using Args = PlanArgs<SEQ, EVAL, LEAF, KEEP, SAMPLE>;
     extern __shared__ __align__(16) unsigned char cars_lds[];
     __shared__ typename std::conditional<TRAFFIC, NpcLDS, char>::type nl_storage;
     NpcLDS* nl = nullptr;
     if constexpr (TRAFFIC) nl = &nl_storage;
-    int repeat;
-    if constexpr (KEEP || SAMPLE) repeat = reinterpret_cast<const RepeatArgs*>(&args)->repeat;
-    else if constexpr (LEAF) repeat = args.e.s.r.repeat;
-    else if constexpr (EVAL) repeat = args.s.r.repeat;
-    else if constexpr (SEQ) repeat = args.r.repeat;
-    else repeat = args.repeat;
+    const int repeat = args.repeat;
     RepCarry rc{0, repeat, 0, 0, false, 0.0f, 0, 0, nullptr, 1.0f, 0.0f, 1.0f};
     int src = 0;       // EVAL: the candidate's root (wave-uniform)
     bool bad = false;  // EVAL: a root outside [0, E): no sub-step runs
     SampleCtx sc{};    // SAMPLE: the candidate's group (wave-uniform), and whether it runs the group's mean
-    if constexpr (SAMPLE) {
-        const EvalArgs& ea = *reinterpret_cast<const EvalArgs*>(&args);
-        const int c = ea.s.r.e_begin + xcd_env((int)blockIdx.x, (int)gridDim.x);  // (without LEAF: e_begin = 0)
-        const unsigned per = (unsigned)args.m.samples;
-        sc.grp = (int)((unsigned)c / per);
-        sc.zero = args.m.mean_first != 0 && (unsigned)c == (unsigned)sc.grp * per;
-        src = __builtin_amdgcn_readfirstlane(ea.ev.roots[sc.grp]);
-        bad = (unsigned)src >= (unsigned)ea.s.r.p.E;
-    } else if constexpr (KEEP) {
-        const EvalArgs& ea = *reinterpret_cast<const EvalArgs*>(&args);
-        const int c = ea.s.r.e_begin + xcd_env((int)blockIdx.x, (int)gridDim.x);  // (without LEAF: e_begin = 0)
-        src = __builtin_amdgcn_readfirstlane(ea.ev.roots[c]);
-        bad = (unsigned)src >= (unsigned)ea.s.r.p.E;
+    if constexpr (EVAL) {
+        // which candidate, its root, and whether it has one
+        int c = xcd_env((int)blockIdx.x, (int)gridDim.x);
+        if constexpr (LEAF || KEEP || SAMPLE) c = args.e_begin + c;  // (a chunk's; plain EVAL is one launch and reads no 0)
+        int r = c;  // the entry of roots
+        if constexpr (SAMPLE) {
+            const unsigned per = (unsigned)args.m.samples;
+            sc.grp = (int)((unsigned)c / per);
+            sc.zero = args.m.mean_first != 0 && (unsigned)c == (unsigned)sc.grp * per;
+            r = sc.grp;
+        }
+        src = __builtin_amdgcn_readfirstlane(args.ev.roots[r]);
+        bad = (unsigned)src >= (unsigned)args.p.E;
         // (KEEP: or a source slot nothing was stored in)
-        if (!bad && args.k.src_valid) bad = __builtin_amdgcn_readfirstlane((int)args.k.src_valid[src]) == 0;
-    } else if constexpr (LEAF) {
-        const int c = args.e.s.r.e_begin + xcd_env((int)blockIdx.x, (int)gridDim.x);
-        src = __builtin_amdgcn_readfirstlane(args.e.ev.roots[c]);
-        bad = (unsigned)src >= (unsigned)args.e.s.r.p.E;
-    } else if constexpr (EVAL) {
-        const int c = xcd_env((int)blockIdx.x, (int)gridDim.x);
-        src = __builtin_amdgcn_readfirstlane(args.ev.roots[c]);
-        bad = (unsigned)src >= (unsigned)args.s.r.p.E;
+        if constexpr (KEEP)
+            if (!bad && args.k.src_valid) bad = __builtin_amdgcn_readfirstlane((int)args.k.src_valid[src]) == 0;
     }
     for (int s = 0; s < (bad ? 0 : repeat); ++s) {
-        typedef const __attribute__((address_space(4))) RepeatArgs CArgs;
+        typedef const __attribute__((address_space(4))) Args CArgs;
         CArgs* ka = (CArgs*)__builtin_amdgcn_kernarg_segment_ptr();  // (args: the first and only argument)
         asm volatile("" : "+s"(ka));
-        const RepeatArgs& a = *(const RepeatArgs*)ka;
+        const Args& a = *(const Args*)ka;
         const SimParams& p = a.p;
         const int e = a.e_begin + xcd_env((int)blockIdx.x, (int)gridDim.x);  // (EVAL: the candidate, e_begin = 0)
         const CarsLDS el = carve_cars_lds(cars_lds, p.N, cars_k(p), true);
         StepInputs in = a.in;
         int rowE = p.E;  // envs (EVAL: candidates) per row of the per-step arrays
         if constexpr (EVAL) {
-            const EvalOuts& ev = reinterpret_cast<const EvalArgs*>(&a)->ev;
-            rowE = ev.C;
-            rc.gamma = ev.gamma;
+            rowE = a.ev.C;
+            rc.gamma = a.ev.gamma;
         }
         if (in.spawn_route) in.spawn_route += (size_t)s * rowE;
         in.rng_counter += (uint64_t)s;
         rc.s = s;
         rc.substeps = a.substeps;
         if constexpr (SEQ) {
-            const SeqRows& q = reinterpret_cast<const SeqArgs*>(&a)->rows;
+            const SeqRows& q = a.rows;
             if constexpr (!SAMPLE) in.actions += 2 * (size_t)s * ((size_t)rowE * p.N);
             in.dt = q.dt[s];
             in.spawn_prob = q.spawn_prob[s];
         }
-        if constexpr (SAMPLE) sc.in = &reinterpret_cast<const SampleA*>(&a)->m;
+        if constexpr (SAMPLE) sc.in = &a.m;
         CarsCtx cx =
             cars_pre<TRAFFIC, false, NpcLDS, 1, false, false, true, false, 0, true, false, SEQ, EVAL, LEAF, SAMPLE>(
                 p, in, a.out, e, el, nl, kDealClasses - 1, &rc, src, sc);
@@ -2894,14 +2895,14 @@ __global__ __launch_bounds__(WAVE, TRAFFIC ? 2 : 4) void k_cars_repeat(
         if (s == 0) rc.first_reset = cx.do_reset;
         if constexpr (LEAF)
             cars_post<TRAFFIC, false, NpcLDS, 1, true, 0, true, 0, SEQ, EVAL, LEAF>(
-                p, a.out, e, el, nl, cx, &rc, &reinterpret_cast<const LeafArgs*>(&a)->lf);
+                p, a.out, e, el, nl, cx, &rc, &a.lf);
         else
             cars_post<TRAFFIC, false, NpcLDS, 1, true, 0, true, 0, SEQ, EVAL>(p, a.out, e, el, nl, cx, &rc);
         if constexpr (SEQ) {
             // row s of the per-step arrays from the car LDS (cars_post left the final reward in
             // el.rew; a lane reads back what it wrote).  (Experiment build: in a sub-step that goes
             // on cars_post has stored nothing, so the next action's load is issued first.)
-            const SeqRows& q = reinterpret_cast<const SeqArgs*>(&a)->rows;
+            const SeqRows& q = a.rows;
             const int tid = threadIdx.x & (WAVE - 1);
             const bool lane_on = tid < p.N;
             const int il = lane_on ? tid : 0;
@@ -2932,17 +2933,14 @@ __global__ __launch_bounds__(WAVE, TRAFFIC ? 2 : 4) void k_cars_repeat(
             if constexpr (EVAL) {
                 // the sub-step the candidate stops at: its return (lane = agent), count and flags
                 if (cx.ended || s + 1 == repeat) {
-                    const EvalOuts& ev = reinterpret_cast<const EvalArgs*>(&a)->ev;
+                    const EvalOuts& ev = a.ev;
                     if (lane_on && ev.returns) gmem(ev.returns)[g] = rc.ret;
                     if (tid == 0) {
                         if (ev.substeps) gmem(ev.substeps)[e] = s + 1;
                         if (ev.term) gmem(ev.term)[e] = cx.term;
                         if (ev.trunc) gmem(ev.trunc)[e] = cx.trunc;
                     }
-                    if constexpr (KEEP) {
-                        using KA = typename std::conditional<LEAF, KeepLeafArgs, KeepArgs>::type;
-                        keep_state<TRAFFIC>(reinterpret_cast<const KA*>(&a)->k, p, e, src, el, nl, cx, tid);
-                    }
+                    if constexpr (KEEP) keep_state<TRAFFIC>(a.k, p, e, src, el, nl, cx, tid);
                 }
             }
         }
@@ -2953,15 +2951,15 @@ __global__ __launch_bounds__(WAVE, TRAFFIC ? 2 : 4) void k_cars_repeat(
     }
     if constexpr (SEQ) {
         // the rows after the sub-step the env stopped at (rc.s): zero, lane = agent
-        typedef const __attribute__((address_space(4))) SeqArgs CArgs;
+        typedef const __attribute__((address_space(4))) Args CArgs;
         CArgs* ka = (CArgs*)__builtin_amdgcn_kernarg_segment_ptr();
         asm volatile("" : "+s"(ka));
-        const SeqArgs& a = *(const SeqArgs*)ka;
-        const int N = a.r.p.N, tid = threadIdx.x & (WAVE - 1);
-        const int e = a.r.e_begin + xcd_env((int)blockIdx.x, (int)gridDim.x);
-        size_t en = (size_t)a.r.p.E * N;
-        if constexpr (EVAL) en = (size_t)reinterpret_cast<const EvalArgs*>(&a)->ev.C * N;
-        if constexpr (SAMPLE) sc.in = &reinterpret_cast<const SampleA*>(&a)->m;
+        const Args& a = *(const Args*)ka;
+        const int N = a.p.N, tid = threadIdx.x & (WAVE - 1);
+        const int e = a.e_begin + xcd_env((int)blockIdx.x, (int)gridDim.x);
+        size_t en = (size_t)a.p.E * N;
+        if constexpr (EVAL) en = (size_t)a.ev.C * N;
+        if constexpr (SAMPLE) sc.in = &a.m;
         if (tid < N) {
             for (int z = bad ? 0 : rc.s + 1; z < repeat; ++z) {
                 const size_t g = (size_t)z * en + (size_t)e * N + tid;
@@ -2976,7 +2974,7 @@ __global__ __launch_bounds__(WAVE, TRAFFIC ? 2 : 4) void k_cars_repeat(
         }
         if constexpr (EVAL) {
             if (bad) {  // a candidate without a root: every output defined, all zero
-                const EvalOuts& ev = reinterpret_cast<const EvalArgs*>(&a)->ev;
+                const EvalOuts& ev = a.ev;
                 if (tid < N && ev.returns) gmem(ev.returns)[(size_t)e * N + tid] = 0.0f;
                 if (tid == 0) {
                     if (ev.substeps) gmem(ev.substeps)[e] = 0;
@@ -2986,10 +2984,9 @@ __global__ __launch_bounds__(WAVE, TRAFFIC ? 2 : 4) void k_cars_repeat(
                 if constexpr (LEAF) {
                     // its agents dead in the hand-off (k_lidar zeroes their LiDAR blocks), and the
                     // head and padding columns of its rows zero: every float of the rows defined
-                    const LeafArgs& la = *reinterpret_cast<const LeafArgs*>(&a);
-                    const Outputs& out = a.r.out;
-                    const int ls = a.r.p.lidar_slots;
-                    if (tid < N) gmem(la.lf.alive)[(size_t)(e - la.lf.c0) * N + tid] = 0;
+                    const Outputs& out = a.out;
+                    const int ls = a.p.lidar_slots;
+                    if (tid < N) gmem(a.lf.alive)[(size_t)(e - a.lf.c0) * N + tid] = 0;
                     for (int i = 0; i < N; ++i) {
                         float* row = out.obs + ((size_t)e * N + i) * out.obs_ld;
                         for (int cc = tid; cc < out.obs_ld - ls; cc += WAVE) row[cc < OBS_HEAD ? cc : cc + ls] = 0.0f;
@@ -4366,18 +4363,6 @@ hipError_t launch_step_window(const SimParams& p, const StepInputs& in, const Ou
     return launch_part(p, in, out, 0, p.E, s, nullptr, &w);
 }
 
-hipError_t launch_evaluate(const SimParams& p, const StepInputs& in, int C, const int32_t* roots, const SeqRows& rows,
-                           int n, const EvalOutputs& outs, hipStream_t s) {
-    if (n < 1 || n > kMaxSeq || C < 1 || !roots) return hipErrorInvalidValue;
-    // the window's car kernel over the candidates, and nothing after it: no k_lidar
-    const unsigned cars_lds = (unsigned)cars_lds_bytes(p.N, cars_k(p), true);
-    const EvalArgs ea{SeqArgs{RepeatArgs{p, in, Outputs{}, 0, n, nullptr}, rows},
-                      EvalOuts{roots, C, outs.gamma, outs.returns, outs.substeps, outs.terminated, outs.truncated}};
-    if (p.traffic) hipLaunchKernelGGL((k_cars_repeat<true, true, true>), dim3(C), dim3(WAVE), cars_lds, s, ea);
-    else hipLaunchKernelGGL((k_cars_repeat<false, true, true>), dim3(C), dim3(WAVE), cars_lds, s, ea);
-    return hipGetLastError();
-}
-
 // the hand-off scratch of `chunk` candidates: each array at a 256-byte boundary
 static size_t leaf_al(size_t b) { return (b + 255) & ~size_t(255); }
 static size_t leaf_stride(const SimParams& p, int chunk) { return leaf_al((size_t)chunk * p.N * sizeof(float)) / sizeof(float); }
@@ -4385,51 +4370,6 @@ size_t leaf_hand_bytes(const SimParams& p, int chunk) {
     const size_t cn = (size_t)chunk * p.N;
     return 4 * leaf_stride(p, chunk) * sizeof(float) + leaf_al(cn * 16) + leaf_al((size_t)chunk * p.ob_stride * sizeof(int4)) +
            leaf_al(cn);
-}
-
-hipError_t launch_evaluate_leaves(const SimParams& p, const StepInputs& in, int C, const int32_t* roots,
-                                  const SeqRows& rows, int n, const EvalOutputs& outs, float* leaf_obs, uint8_t* hand,
-                                  int chunk, hipStream_t s) {
-    if (n < 1 || n > kMaxSeq || C < 1 || !roots || !leaf_obs || !hand || chunk < 1) return hipErrorInvalidValue;
-    if (chunk > C) chunk = C;
-    const unsigned cars_lds = (unsigned)cars_lds_bytes(p.N, cars_k(p), true);
-    const size_t cn = (size_t)chunk * p.N, S = leaf_stride(p, chunk);
-    LeafHand lf{};
-    lf.pose = reinterpret_cast<float*>(hand);
-    lf.stride = (int64_t)S;
-    lf.cand = reinterpret_cast<unsigned long long*>(hand + 4 * S * sizeof(float));
-    lf.box = reinterpret_cast<int4*>(reinterpret_cast<uint8_t*>(lf.cand) + leaf_al(cn * 16));
-    lf.alive = reinterpret_cast<uint8_t*>(lf.box) + leaf_al((size_t)chunk * p.ob_stride * sizeof(int4));
-    // what k_lidar casts from: the scratch in the place of the ego block and the hand-off tables
-    // (LidarSrcHbm reads x, y, heading, alive, ob_cand, ob_box and the beam list, nothing else of the state)
-    SimParams lp = p;
-    lp.E = chunk;
-    lp.ego = EgoSoA{};
-    lp.ego.x = lf.pose;
-    lp.ego.alive = lf.alive;
-    lp.ego.stride = lf.stride;
-    lp.ob_box = lf.box;
-    lp.ob_cand = lf.cand;
-    Outputs co{};  // the car kernel's rows: leaf_obs by the global candidate
-    co.obs = leaf_obs;
-    co.obs_ld = p.D;
-    for (int c0 = 0; c0 < C; c0 += chunk) {
-        const int nc = C - c0 < chunk ? C - c0 : chunk;
-        lf.c0 = c0;
-        const LeafArgs la{EvalArgs{SeqArgs{RepeatArgs{p, in, co, c0, n, nullptr}, rows},
-                                   EvalOuts{roots, C, outs.gamma, outs.returns, outs.substeps, outs.terminated,
-                                            outs.truncated}},
-                          lf};
-        if (p.traffic) hipLaunchKernelGGL((k_cars_repeat<true, true, true, true>), dim3(nc), dim3(WAVE), cars_lds, s, la);
-        else hipLaunchKernelGGL((k_cars_repeat<false, true, true, true>), dim3(nc), dim3(WAVE), cars_lds, s, la);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-        Outputs lo = co;  // the cast's rows: the chunk's, by the candidate's slot
-        lo.obs = leaf_obs + (size_t)c0 * p.N * p.D;
-        e = launch_lidar(lp, lo, 0, nc * p.N, s);
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
 }
 
 PoolState pool_of_live(const SimParams& p) {
@@ -4468,107 +4408,91 @@ SimParams pool_view(const SimParams& p, const PoolState& pool) {
     return q;
 }
 
-hipError_t launch_expand(const SimParams& p, const StepInputs& in, int C, const int32_t* roots, const SeqRows& rows,
-                         int n, const EvalOutputs& outs, const PoolState* src, const PoolState& dst,
-                         const int32_t* dst_slots, float* leaf_obs, uint8_t* hand, int chunk, hipStream_t s) {
-    if (n < 1 || n > kMaxSeq || C < 1 || !roots || !dst_slots || dst.slots < 1) return hipErrorInvalidValue;
-    if (leaf_obs && (!hand || chunk < 1)) return hipErrorInvalidValue;
-    const unsigned cars_lds = (unsigned)cars_lds_bytes(p.N, cars_k(p), true);
-    const SimParams sp = src ? pool_view(p, *src) : p;  // what the first sub-step loads from
-    const KeepOuts ko{dst, dst_slots, src ? src->valid : nullptr};
-    const EvalOuts eo{roots, C, outs.gamma, outs.returns, outs.substeps, outs.terminated, outs.truncated};
-    if (!leaf_obs) {
-        const KeepArgs ka{EvalArgs{SeqArgs{RepeatArgs{sp, in, Outputs{}, 0, n, nullptr}, rows}, eo}, ko};
-        if (p.traffic) hipLaunchKernelGGL((k_cars_repeat<true, true, true, false, true>), dim3(C), dim3(WAVE), cars_lds, s, ka);
-        else hipLaunchKernelGGL((k_cars_repeat<false, true, true, false, true>), dim3(C), dim3(WAVE), cars_lds, s, ka);
-        return hipGetLastError();
-    }
-    // with leaf observations: launch_evaluate_leaves' chunks, scratch and cast
-    if (chunk > C) chunk = C;
+// What a plan call with leaf observations needs besides the car kernel's own arguments, from the
+// hand-off scratch of `chunk` candidates.
+struct LeafCast {
+    LeafHand lf;   // the scratch, carved (c0 is the chunk loop's)
+    SimParams lp;  // what k_lidar casts from: the scratch in the place of the ego block and the hand-off tables
+                   // (LidarSrcHbm reads x, y, heading, alive, ob_cand, ob_box and the beam list, nothing else of the state)
+    Outputs co;    // the car kernel's rows: leaf_obs by the global candidate
+};
+static LeafCast leaf_cast(const SimParams& p, uint8_t* hand, int chunk, float* leaf_obs) {
     const size_t cn = (size_t)chunk * p.N, S = leaf_stride(p, chunk);
-    LeafHand lf{};
+    LeafCast k{LeafHand{}, p, Outputs{}};
+    LeafHand& lf = k.lf;
     lf.pose = reinterpret_cast<float*>(hand);
     lf.stride = (int64_t)S;
     lf.cand = reinterpret_cast<unsigned long long*>(hand + 4 * S * sizeof(float));
     lf.box = reinterpret_cast<int4*>(reinterpret_cast<uint8_t*>(lf.cand) + leaf_al(cn * 16));
     lf.alive = reinterpret_cast<uint8_t*>(lf.box) + leaf_al((size_t)chunk * p.ob_stride * sizeof(int4));
-    SimParams lp = p;
-    lp.E = chunk;
-    lp.ego = EgoSoA{};
-    lp.ego.x = lf.pose;
-    lp.ego.alive = lf.alive;
-    lp.ego.stride = lf.stride;
-    lp.ob_box = lf.box;
-    lp.ob_cand = lf.cand;
-    Outputs co{};
-    co.obs = leaf_obs;
-    co.obs_ld = p.D;
-    for (int c0 = 0; c0 < C; c0 += chunk) {
-        const int nc = C - c0 < chunk ? C - c0 : chunk;
-        lf.c0 = c0;
-        const KeepLeafArgs la{LeafArgs{EvalArgs{SeqArgs{RepeatArgs{sp, in, co, c0, n, nullptr}, rows}, eo}, lf}, ko};
-        if (p.traffic) hipLaunchKernelGGL((k_cars_repeat<true, true, true, true, true>), dim3(nc), dim3(WAVE), cars_lds, s, la);
-        else hipLaunchKernelGGL((k_cars_repeat<false, true, true, true, true>), dim3(nc), dim3(WAVE), cars_lds, s, la);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-        Outputs lo = co;
-        lo.obs = leaf_obs + (size_t)c0 * p.N * p.D;
-        e = launch_lidar(lp, lo, 0, nc * p.N, s);
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
+    k.lp.E = chunk;
+    k.lp.ego = EgoSoA{};
+    k.lp.ego.x = lf.pose;
+    k.lp.ego.alive = lf.alive;
+    k.lp.ego.stride = lf.stride;
+    k.lp.ob_box = lf.box;
+    k.lp.ob_cand = lf.cand;
+    k.co.obs = leaf_obs;
+    k.co.obs_ld = p.D;
+    return k;
 }
 
-hipError_t launch_sample(const SimParams& p, const StepInputs& in, const int32_t* roots, const SeqRows& rows, int n,
-                         const EvalOutputs& outs, const SampleIn& sm, float* leaf_obs, uint8_t* hand, int chunk,
-                         hipStream_t s) {
-    if (n < 1 || n > kMaxSeq || sm.groups < 1 || sm.samples < 1 || !roots || !sm.mean || !sm.sigma)
-        return hipErrorInvalidValue;
-    if (leaf_obs && (!hand || chunk < 1)) return hipErrorInvalidValue;
-    const int C = sm.groups * sm.samples;
-    const unsigned cars_lds = (unsigned)cars_lds_bytes(p.N, cars_k(p), true);
-    const EvalOuts eo{roots, C, outs.gamma, outs.returns, outs.substeps, outs.terminated, outs.truncated};
-    if (!leaf_obs) {
-        const SampleArgs sa{EvalArgs{SeqArgs{RepeatArgs{p, in, Outputs{}, 0, n, nullptr}, rows}, eo}, sm};
-        if (p.traffic)
-            hipLaunchKernelGGL((k_cars_repeat<true, true, true, false, false, true>), dim3(C), dim3(WAVE), cars_lds, s, sa);
-        else
-            hipLaunchKernelGGL((k_cars_repeat<false, true, true, false, false, true>), dim3(C), dim3(WAVE), cars_lds, s, sa);
-        return hipGetLastError();
+// The plan call's car kernel for one set of modes, over the candidates [c0, c0 + nc): the argument
+// struct of the modes (PlanArgs) is `ea` plus the modes' own members.  The twelve EVAL
+// instantiations of k_cars_repeat are named here and nowhere else.
+template <bool LEAF, bool KEEP, bool SAMPLE>
+static hipError_t launch_plan_kernel(bool traffic, int nc, unsigned lds, hipStream_t s, const EvalArgs& ea,
+                                     const LeafHand& lf, const KeepOuts& ko, const SampleIn* sm) {
+    using Args = PlanArgs<true, true, LEAF, KEEP, SAMPLE>;
+    const auto base = [&] {
+        if constexpr (LEAF) return LeafArgs{ea, lf};
+        else return ea;
+    }();
+    const Args a = [&] {
+        if constexpr (KEEP) return Args{base, ko};
+        else if constexpr (SAMPLE) return Args{base, *sm};
+        else return base;
+    }();
+    if (traffic) hipLaunchKernelGGL((k_cars_repeat<true, true, true, LEAF, KEEP, SAMPLE>), dim3(nc), dim3(WAVE), lds, s, a);
+    else hipLaunchKernelGGL((k_cars_repeat<false, true, true, LEAF, KEEP, SAMPLE>), dim3(nc), dim3(WAVE), lds, s, a);
+    return hipGetLastError();
+}
+// by LEAF | KEEP << 1 | SAMPLE << 2 (KEEP with SAMPLE: no kernel, launch_plans rejects the call)
+static constexpr decltype(&launch_plan_kernel<false, false, false>) kPlanKernels[] = {
+    launch_plan_kernel<false, false, false>, launch_plan_kernel<true, false, false>,
+    launch_plan_kernel<false, true, false>,  launch_plan_kernel<true, true, false>,
+    launch_plan_kernel<false, false, true>,  launch_plan_kernel<true, false, true>};
+
+hipError_t launch_plans(const SimParams& p, const StepInputs& in, const PlanCall& c, hipStream_t s) {
+    const int C = c.C, n = c.n;
+    if (n < 1 || n > kMaxSeq || C < 1 || !c.roots || !c.rows) return hipErrorInvalidValue;
+    if (c.leaf_obs && (!c.hand || c.chunk < 1)) return hipErrorInvalidValue;
+    if (c.dst && (c.sample || !c.dst_slots || c.dst->slots < 1)) return hipErrorInvalidValue;
+    if (!c.dst && c.src) return hipErrorInvalidValue;
+    if (c.sample) {
+        const SampleIn& sm = *c.sample;
+        if (sm.groups < 1 || sm.samples < 1 || (int64_t)sm.groups * sm.samples != C || !sm.mean || !sm.sigma)
+            return hipErrorInvalidValue;
     }
-    // with leaf observations: launch_evaluate_leaves' chunks, scratch and cast
-    if (chunk > C) chunk = C;
-    const size_t cn = (size_t)chunk * p.N, S = leaf_stride(p, chunk);
-    LeafHand lf{};
-    lf.pose = reinterpret_cast<float*>(hand);
-    lf.stride = (int64_t)S;
-    lf.cand = reinterpret_cast<unsigned long long*>(hand + 4 * S * sizeof(float));
-    lf.box = reinterpret_cast<int4*>(reinterpret_cast<uint8_t*>(lf.cand) + leaf_al(cn * 16));
-    lf.alive = reinterpret_cast<uint8_t*>(lf.box) + leaf_al((size_t)chunk * p.ob_stride * sizeof(int4));
-    SimParams lp = p;
-    lp.E = chunk;
-    lp.ego = EgoSoA{};
-    lp.ego.x = lf.pose;
-    lp.ego.alive = lf.alive;
-    lp.ego.stride = lf.stride;
-    lp.ob_box = lf.box;
-    lp.ob_cand = lf.cand;
-    Outputs co{};
-    co.obs = leaf_obs;
-    co.obs_ld = p.D;
+    const unsigned cars_lds = (unsigned)cars_lds_bytes(p.N, cars_k(p), true);
+    const SimParams sp = c.src ? pool_view(p, *c.src) : p;  // what the first sub-step loads from
+    const KeepOuts ko = c.dst ? KeepOuts{*c.dst, c.dst_slots, c.src ? c.src->valid : nullptr} : KeepOuts{};
+    const EvalOuts eo{c.roots, C, c.outs.gamma, c.outs.returns, c.outs.substeps, c.outs.terminated, c.outs.truncated};
+    // without leaf observations: the window's car kernel over the candidates, and nothing after it
+    // (no k_lidar); with them: per chunk the car kernel, then the cast of the chunk's hand-off
+    const auto launch = kPlanKernels[(c.leaf_obs ? 1 : 0) | (c.dst ? 2 : 0) | (c.sample ? 4 : 0)];
+    const int chunk = !c.leaf_obs ? C : c.chunk > C ? C : c.chunk;
+    LeafCast lc{};
+    if (c.leaf_obs) lc = leaf_cast(p, c.hand, chunk, c.leaf_obs);
     for (int c0 = 0; c0 < C; c0 += chunk) {
         const int nc = C - c0 < chunk ? C - c0 : chunk;
-        lf.c0 = c0;
-        const SampleLeafArgs la{LeafArgs{EvalArgs{SeqArgs{RepeatArgs{p, in, co, c0, n, nullptr}, rows}, eo}, lf}, sm};
-        if (p.traffic)
-            hipLaunchKernelGGL((k_cars_repeat<true, true, true, true, false, true>), dim3(nc), dim3(WAVE), cars_lds, s, la);
-        else
-            hipLaunchKernelGGL((k_cars_repeat<false, true, true, true, false, true>), dim3(nc), dim3(WAVE), cars_lds, s, la);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-        Outputs lo = co;
-        lo.obs = leaf_obs + (size_t)c0 * p.N * p.D;
-        e = launch_lidar(lp, lo, 0, nc * p.N, s);
+        lc.lf.c0 = c0;
+        const EvalArgs ea{SeqArgs{RepeatArgs{sp, in, lc.co, c0, n, nullptr}, *c.rows}, eo};
+        hipError_t e = launch(p.traffic, nc, cars_lds, s, ea, lc.lf, ko, c.sample);
+        if (e != hipSuccess || !c.leaf_obs) return e;
+        Outputs lo = lc.co;  // the cast's rows: the chunk's, by the candidate's slot
+        lo.obs = c.leaf_obs + (size_t)c0 * p.N * p.D;
+        e = launch_lidar(lc.lp, lo, 0, nc * p.N, s);
         if (e != hipSuccess) return e;
     }
     return hipSuccess;

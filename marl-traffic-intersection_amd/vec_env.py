@@ -262,6 +262,15 @@ class VecIntersectionEnv:
                                   "status_seq")}
         return o["obs"], o["reward"], o["terminated"], o["truncated"], info
 
+    def _dev_tensor(self, x, dtype):
+        """x as a contiguous tensor of `dtype` on this env's device (torch backend)."""
+        t = self._torch
+        if isinstance(x, t.Tensor) and x.is_cuda and x.dtype == dtype and x.is_contiguous():
+            if x.device.index != self.device_index:
+                raise ValueError("an argument is on another device")
+            return x
+        return t.as_tensor(x, dtype=dtype, device=self._out["obs"].device).contiguous()
+
     def evaluate_plans(self, actions, roots, dt=1.0 / 60.0, gamma: float = 1.0, spawn_route=None, copy: bool = False,
                        leaf_obs: bool = False, _expand=None):
         """Score C candidate plans from the live batch without touching it (Handle.evaluate_plans):
@@ -277,27 +286,19 @@ class VecIntersectionEnv:
         if self.backend == "torch":
             t = self._torch
             self._bind_stream()
-            dev = self._out["obs"].device
-            a = actions
-            if not (isinstance(a, t.Tensor) and a.is_cuda and a.dtype == t.float32 and a.is_contiguous()):
-                a = t.as_tensor(a, dtype=t.float32, device=dev).contiguous()
-            r = roots
-            if not (isinstance(r, t.Tensor) and r.is_cuda and r.dtype == t.int32 and r.is_contiguous()):
-                r = t.as_tensor(r, dtype=t.int32, device=dev).contiguous()
+            a, r = self._dev_tensor(actions, t.float32), self._dev_tensor(roots, t.int32)
             if r.dim() != 1 or a.dim() != 4 or tuple(a.shape[1:]) != (r.shape[0], self.num_agents, 2):
                 raise ValueError(f"actions must be [T, C, {self.num_agents}, 2] and roots [C], got {tuple(a.shape)} "
                                  f"and {tuple(r.shape)}")
-            if a.device.index != self.device_index or r.device.index != self.device_index:
-                raise ValueError("actions or roots are on another device")
             T, C = int(a.shape[0]), int(r.shape[0])
             o = self._eval_out(T, C, leaf_obs)
             sp = None
             if spawn_route is not None:
-                sp = t.as_tensor(spawn_route, dtype=t.int32, device=dev).contiguous()
+                sp = self._dev_tensor(spawn_route, t.int32)
                 if tuple(sp.shape) != (T, C):
                     raise ValueError(f"spawn_route must be [{T}][{C}], got {tuple(sp.shape)}")
             if _expand is not None:
-                d = t.as_tensor(_expand["dst_slots"], dtype=t.int32, device=dev).contiguous()
+                d = self._dev_tensor(_expand["dst_slots"], t.int32)
                 if tuple(d.shape) != (C,):
                     raise ValueError(f"dst_slots must be [{C}], got {tuple(d.shape)}")
                 self._h.expand_plans(a, r, _expand["dst"], d, _expand["src"], _expand["counter_offset"], leaf_obs, dt,
@@ -330,15 +331,6 @@ class VecIntersectionEnv:
         state, last outputs and random stream stay as they are."""
         return self.evaluate_plans(actions, roots, dt, gamma, spawn_route, copy, leaf_obs,
                                    _expand=dict(dst=dst, dst_slots=dst_slots, src=src, counter_offset=counter_offset))
-
-    def _dev_tensor(self, x, dtype):
-        """x as a contiguous tensor of `dtype` on this env's device (torch backend)."""
-        t = self._torch
-        if isinstance(x, t.Tensor) and x.is_cuda and x.dtype == dtype and x.is_contiguous():
-            if x.device.index != self.device_index:
-                raise ValueError("an argument is on another device")
-            return x
-        return t.as_tensor(x, dtype=dtype, device=self._out["obs"].device).contiguous()
 
     def sample_plans(self, mean, sigma, roots, samples: int, dt=1.0 / 60.0, gamma: float = 1.0, lo=(-1.0, -1.0),
                      hi=(1.0, 1.0), seed: int = 0, counter: int = 0, mean_first: bool = False, leaf_obs: bool = False,

@@ -149,6 +149,24 @@ def test_traffic(mev, max_npcs):
     h.close()
 
 
+def test_traffic_without_leaf_obs(mev):
+    """The smallest scene with the NPC phase and no leaf_obs (the one mode test_traffic leaves out): 2
+    envs of 2 agents, 8 rays, 4 NPC slots, one group of K = 5 candidates over 3 rows, Philox spawner."""
+    En, N, Tn = 2, 2, 3
+    h, _ = EP._handle(mev, En, N, 8, max_npcs=4, traffic=True, density=20.0, max_steps=2000)
+    EP._device_history_traffic(h, EP.TRAFFIC["seed"])
+    before = EP._snap_all(h)
+    assert before["state"]["npc_count"].max() >= 1
+    roots = np.array([1], np.int32)
+    mean, sigma = draw_dist(N, seed=53, groups=1, t=Tn)
+    out = sample(h, mean, sigma, roots=roots, dt=DTS[:Tn], leaf=False)
+    assert "leaf_obs" not in out
+    assert G.bits_equal(out["actions_out"], PN.sampled_actions(mean, sigma, K, LO, HI, SEED, COUNTER))
+    assert_equals_evaluate("traffic, no leaf_obs", h, out, roots, dts=DTS[:Tn], leaf=False)
+    EP._assert_same("traffic, no leaf_obs", before, EP._snap_all(h))
+    h.close()
+
+
 def test_chunks_cut_through_groups(mev, scene, monkeypatch):
     """MEV_LEAF_CHUNK=3 at creation, K = 5: 20 candidates in chunks of 3, every output the same."""
     S = scene
