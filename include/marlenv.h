@@ -283,8 +283,9 @@ int mev_step_repeat(mev_handle* h, const mev_repeat_args* args);
  * 1..MEV_MAX_REPEAT or null actions: MEV_E_INVALID, the handle untouched).  Launch path as
  * mev_step_repeat: a resident step server is stopped first, the runtime-layout kernels run
  * (any N <= 64, <= 64 NPC slots, per-car sizes, any beam list), not counted by
- * mev_kernel_timing.  Host mode stages actions, spawn_route and the *_seq arrays in per-handle
- * device buffers made at the first call (sized for MEV_MAX_REPEAT rows) and is synchronous.
+ * mev_kernel_timing.  Host mode stages actions, spawn_route, substeps and the *_seq arrays in the
+ * handle's staging block, which every host-mode call shares and which grows to the largest call
+ * seen (no more than the call's own rows), and is synchronous.
  * Measured (python tools/bench_sequence.py -> profiles/sequence_sweep.json): at 4096 envs x
  * 8 agents x 64 beams one call with all three *_seq arrays takes 73.9 us at T = 4 against 102.1 us for four
  * mev_step calls with the same actions (1.38x), 109.7 against 205.5 us at T = 8 (1.87x), 180.9 against 412.9 us

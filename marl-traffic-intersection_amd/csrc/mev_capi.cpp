@@ -106,16 +106,8 @@ struct mev_handle {
     mev::Outputs last{};  // where the most recent outputs were written
     float* d_actions = nullptr;
     int32_t* d_spawn = nullptr;
-    int32_t* d_spawn_rep = nullptr;  // [MEV_MAX_REPEAT][E] spawn routes of a host-mode mev_step_repeat (made at the first)
-    int32_t* d_substeps = nullptr;   // [E] its sub-step counts
-    // host-mode mev_step_sequence (each made at the first call that needs it, sized for MEV_MAX_REPEAT rows)
-    float* d_act_seq = nullptr;      // [MEV_MAX_REPEAT][E][N][2] action rows
-    float* d_rew_seq = nullptr;      // [MEV_MAX_REPEAT][E][N] per-step rewards
-    uint8_t* d_done_seq = nullptr;   // [MEV_MAX_REPEAT][E][N]
-    uint8_t* d_status_seq = nullptr; // [MEV_MAX_REPEAT][E][N]
-    int32_t* d_env_map = nullptr;    // [E] env map of a host-mode mev_restore_map
-    uint8_t* d_eval = nullptr;       // every array of a host-mode mev_evaluate_plans, grown to the largest call seen
-    size_t eval_cap = 0;
+    uint8_t* d_stage = nullptr;  // the staging block of host-mode calls (Stage, below), grown to the largest call seen
+    size_t stage_cap = 0;
     // mev_evaluate_leaves: the candidates' LiDAR hand-off (mev::LeafHand), grow-only up to kLeafHandCap
     uint8_t* d_leaf = nullptr;
     size_t leaf_cap = 0;
@@ -129,8 +121,6 @@ struct mev_handle {
     float* d_rel = nullptr;
     int32_t* d_traffic = nullptr;
     int32_t* d_reset_routes = nullptr;  // [nroutes]: pool for per-reset route draws
-    uint8_t* d_snap_stage = nullptr;    // device copy of a host snapshot (masked restore)
-    size_t snap_stage_bytes = 0;
     uint64_t rng_counter = 0;
     // per-kernel timing (mev_kernel_timing): 3 events per step, folded into sums when the ring fills
     std::vector<hipEvent_t> tev;
@@ -265,8 +255,7 @@ struct mev_handle {
         if (serve_ev) (void)hipEventDestroy(serve_ev);
         if (serve_stream) (void)hipStreamDestroy(serve_stream);
         if (gs_pin) (void)hipHostFree(gs_pin);
-        if (d_snap_stage) (void)hipFree(d_snap_stage);
-        if (d_eval) (void)hipFree(d_eval);
+        if (d_stage) (void)hipFree(d_stage);
         if (d_leaf) (void)hipFree(d_leaf);
         for (mev_pool* q : pools) {
             if (q->block) (void)hipFree(q->block);
@@ -277,14 +266,84 @@ struct mev_handle {
     }
 };
 
-// a scratch buffer of host-mode calls, made (zeroed, freed with the handle) at the first call that wants it
-template <class T>
-static int scratch(mev_handle* h, bool wanted, T** p, size_t n) {
-    if (!wanted || *p) return MEV_OK;
-    const hipError_t err = h->alloc(p, n);
-    if (err == hipSuccess) return MEV_OK;
-    return fail(MEV_E_NOMEM, std::string("device allocation failed: ") + hipGetErrorString(err));
+// a device block of the handle that only grows (the staging block, the leaf scratch): at least `need` bytes
+static int grow_block(mev_handle* h, uint8_t** block, size_t* cap, size_t need) {
+    if (need <= *cap) return MEV_OK;
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (*block) (void)hipFree(*block);
+    *block = nullptr;
+    *cap = 0;
+    const hipError_t err = hipMalloc(reinterpret_cast<void**>(block), need);
+    if (err != hipSuccess) return fail(MEV_E_NOMEM, std::string("device allocation failed: ") + hipGetErrorString(err));
+    *cap = need;
+    return MEV_OK;
 }
+
+// Stage: the caller's arrays of one call on the device.  The call names each array once, with the
+// slot its kernel arguments read the device address from: in() what the device reads, out() what it
+// writes; a null array makes its slot null.  upload(), after the arguments have been checked, lays
+// the named arrays out in the handle's staging block (d_stage), each at a 256-byte boundary, grows
+// the block to hold them, points the slots into it and enqueues the inputs' copies; download()
+// enqueues the outputs' copies back and synchronises the stream.  fetch() adds an output that
+// another device array holds.  With `dev` (MEV_DEVICE_PTRS) the slots receive the caller's own
+// pointers, nothing is copied and download() does not synchronise: a call has no host / device
+// branch of its own for its arrays.
+// One block serves every call: a host-mode call that stages ends in download()'s synchronise, so
+// the block is idle when the next one starts; device-mode calls never touch it; and a call's
+// inputs and outputs lie side by side in one layout.
+// Not staged: mev_step and mev_reset (the per-step path: d_actions, d_spawn, d_mask and the pinned
+// zero-copy block, sized at mev_create), the unmasked mev_restore and mev_set_state (copies straight
+// into the state arrays), mev_get_state (its pinned read-back) and the configuration calls.
+struct Stage {
+    Stage(mev_handle* h, bool dev) : h(h), dev(dev) {}
+    template <class T>
+    void in(const T** slot, const T* host, size_t n) { add(slot, host, n * sizeof(T), false); }
+    template <class T>
+    void out(T** slot, T* host, size_t n) { add(slot, host, n * sizeof(T), true); }
+    void fetch(void* host, const void* d, size_t bytes) {
+        if (!dev && host && bytes) items.push_back({nullptr, host, const_cast<void*>(d), 0, bytes, true});
+    }
+    int upload() {
+        if (dev) return MEV_OK;
+        if (int r = grow_block(h, &h->d_stage, &h->stage_cap, need)) return r;
+        for (Item& it : items) {
+            if (!it.slot) continue;
+            it.d = h->d_stage + it.off;
+            memcpy(it.slot, &it.d, sizeof(void*));
+            if (!it.out) HIP_TRY(hipMemcpyAsync(it.d, it.host, it.bytes, hipMemcpyHostToDevice, h->stream));
+        }
+        return MEV_OK;
+    }
+    int download() {
+        if (dev) return MEV_OK;
+        for (const Item& it : items)
+            if (it.out) HIP_TRY(hipMemcpyAsync(it.host, it.d, it.bytes, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        return MEV_OK;
+    }
+
+private:
+    struct Item {
+        void* slot;  // the address of the caller's pointer variable (null: fetch)
+        void* host;
+        void* d;
+        size_t off, bytes;
+        bool out;
+    };
+    // (the slot is written as bytes: it is a pointer variable of the array's own type)
+    void add(void* slot, const void* host, size_t bytes, bool out) {
+        if (dev || !host) {
+            memcpy(slot, &host, sizeof(void*));
+            return;
+        }
+        items.push_back({slot, const_cast<void*>(host), nullptr, need, bytes, out});
+        need += (bytes + 255) & ~size_t(255);
+    }
+    mev_handle* h;
+    bool dev;
+    size_t need = 0;
+    std::vector<Item> items;
+};
 
 extern "C" {
 
@@ -1516,25 +1575,10 @@ static int step_window(mev_handle* h, const mev_step_args* a, const WindowArgs& 
     const bool dev = (a->flags & MEV_DEVICE_PTRS) != 0;
     const int n = w.n;
     const size_t E = size_t(h->cfg.num_envs), EN = E * size_t(h->cfg.num_agents);
-    // host mode stages its arrays in per-handle buffers sized for MEV_MAX_REPEAT rows
-    const size_t cap = size_t(MEV_MAX_REPEAT);
-    if (!dev && (scratch(h, w.plan, &h->d_act_seq, cap * EN * 2) ||
-                 scratch(h, a->spawn_route != nullptr, &h->d_spawn_rep, cap * E) ||
-                 scratch(h, w.substeps != nullptr, &h->d_substeps, E) ||
-                 scratch(h, w.reward_seq != nullptr, &h->d_rew_seq, cap * EN) ||
-                 scratch(h, w.done_seq != nullptr, &h->d_done_seq, cap * EN) ||
-                 scratch(h, w.status_seq != nullptr, &h->d_status_seq, cap * EN)))
-        return MEV_E_NOMEM;
-    // a held action: one row, staged where mev_step stages it, and no rows for the kernel
+    // a held action: one row, and no rows for the kernel
     mev::SeqRows rows{};
-    size_t act_rows = 1;
-    float* d_act = h->d_actions;
-    const mev::SeqRows* krows = nullptr;
-    if (w.plan) {
-        act_rows = size_t(n);
-        d_act = h->d_act_seq;
-        krows = &rows;
-    }
+    const size_t act_rows = w.plan ? size_t(n) : 1;
+    const mev::SeqRows* krows = w.plan ? &rows : nullptr;
     // each row's dt and spawn probability (as mev_step), read from the caller's memory now; a
     // plan's travel by value with the kernel's arguments
     for (size_t s = 0; s < act_rows; ++s) {
@@ -1546,45 +1590,23 @@ static int step_window(mev_handle* h, const mev_step_args* a, const WindowArgs& 
     in.spawn_prob = rows.spawn_prob[0];
     in.auto_reset = (a->flags & MEV_AUTO_RESET) ? 1 : 0;
     in.rng_counter = h->rng_counter;  // sub-step s: + s (k_cars_repeat)
-    h->rng_counter += uint64_t(n);
     int32_t* d_sub = nullptr;
-    if (dev) {
-        in.actions = a->actions;
-        in.spawn_route = a->spawn_route;
-        d_sub = w.substeps;
-        rows.reward = w.reward_seq;
-        rows.done = w.done_seq;
-        rows.status = w.status_seq;
-    } else {
-        HIP_TRY(hipMemcpyAsync(d_act, a->actions, act_rows * EN * 2 * sizeof(float), hipMemcpyHostToDevice, h->stream));
-        in.actions = d_act;
-        if (a->spawn_route) {
-            HIP_TRY(hipMemcpyAsync(h->d_spawn_rep, a->spawn_route, size_t(n) * E * sizeof(int32_t), hipMemcpyHostToDevice,
-                                   h->stream));
-            in.spawn_route = h->d_spawn_rep;
-        }
-        if (w.substeps) d_sub = h->d_substeps;
-        if (w.reward_seq) rows.reward = h->d_rew_seq;
-        if (w.done_seq) rows.done = h->d_done_seq;
-        if (w.status_seq) rows.status = h->d_status_seq;
-    }
+    Stage st(h, dev);
+    st.in(&in.actions, a->actions, act_rows * EN * 2);
+    st.in(&in.spawn_route, a->spawn_route, size_t(n) * E);
+    st.out(&d_sub, w.substeps, E);
+    st.out(&rows.reward, w.reward_seq, size_t(n) * EN);
+    st.out(&rows.done, w.done_seq, size_t(n) * EN);
+    st.out(&rows.status, w.status_seq, size_t(n) * EN);
+    if (int r = st.upload()) return r;
+    h->rng_counter += uint64_t(n);
     const mev::Outputs o = resolve_outputs(h, *a, dev);
     h->deal_valid = false;  // NPC counts change outside the fused step: the deal restarts
     HIP_TRY(mev::launch_step_window(h->sp, in, o, n, krows, d_sub, h->stream));
     h->last = o;
-    if (!dev) {
+    if (!dev)  // (the step's own outputs: from the handle's buffers, as mev_step)
         if (int r = copy_out(h, o, *a, hipMemcpyDeviceToHost)) return r;
-        if (w.substeps)
-            HIP_TRY(hipMemcpyAsync(w.substeps, d_sub, E * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-        if (w.reward_seq)
-            HIP_TRY(hipMemcpyAsync(w.reward_seq, rows.reward, size_t(n) * EN * sizeof(float), hipMemcpyDeviceToHost,
-                                   h->stream));
-        if (w.done_seq) HIP_TRY(hipMemcpyAsync(w.done_seq, rows.done, size_t(n) * EN, hipMemcpyDeviceToHost, h->stream));
-        if (w.status_seq)
-            HIP_TRY(hipMemcpyAsync(w.status_seq, rows.status, size_t(n) * EN, hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(hipStreamSynchronize(h->stream));
-    }
-    return MEV_OK;
+    return st.download();
 }
 
 int mev_step_repeat(mev_handle* h, const mev_repeat_args* ra) {
@@ -1609,24 +1631,11 @@ int mev_step_sequence(mev_handle* h, const mev_sequence_args* sa) {
 }
 
 // mev_evaluate_plans (include/marlenv.h): the plan rollout's loop over C candidates that start from
-// copies of live envs, nothing of the handle written.  Host mode stages every array in one device
-// block of the handle that grows to the largest call seen.
+// copies of live envs, nothing of the handle written.
 // leaf_obs: mev_evaluate_leaves' [C][N][obs_dim] rows (null: mev_evaluate_plans).  The candidates'
 // LiDAR hand-off lives in a per-handle scratch that only grows, to kLeafHandCap at the most: a call
 // with more candidates than the cap holds (or than MEV_LEAF_CHUNK) goes through in chunks.
 constexpr size_t kLeafHandCap = size_t(64) << 20;
-// a device block of the handle that only grows (the staging block, the leaf scratch): at least `need` bytes
-static int grow_block(mev_handle* h, uint8_t** block, size_t* cap, size_t need) {
-    if (need <= *cap) return MEV_OK;
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    if (*block) (void)hipFree(*block);
-    *block = nullptr;
-    *cap = 0;
-    const hipError_t err = hipMalloc(reinterpret_cast<void**>(block), need);
-    if (err != hipSuccess) return fail(MEV_E_NOMEM, std::string("device allocation failed: ") + hipGetErrorString(err));
-    *cap = need;
-    return MEV_OK;
-}
 // xp: mev_expand_plans' additions (null: the two evaluation calls) -- the candidates' roots are slots
 // of xp->src when that is set, and their stop states go to slots xp->dst_slots of xp->dst.
 // sm: mev_sample_plans' additions (null: the other calls) -- no actions array: the candidates draw
@@ -1708,11 +1717,10 @@ static int evaluate(mev_handle* h, const mev_evaluate_args* ea, float* leaf_obs,
     in.dt = rows.dt[0];
     in.spawn_prob = rows.spawn_prob[0];
     in.rng_counter = h->rng_counter + (xp ? xp->counter_offset : 0);  // sub-step s: + s; the handle's counter stays
-    mev::EvalOutputs eo{ea->gamma, ea->returns, ea->substeps, ea->terminated, ea->truncated};
-    const int32_t* d_roots = ea->roots;
-    const int32_t* d_dst = xp ? xp->dst_slots : nullptr;
-    const size_t obs_bytes = leaves ? CN * size_t(h->sp.D) * sizeof(float) : 0;
-    float* d_leaf_obs = leaf_obs;
+    mev::EvalOutputs eo{};
+    eo.gamma = ea->gamma;
+    const int32_t *d_roots = nullptr, *d_dst = nullptr;
+    float* d_leaf_obs = nullptr;
     int chunk = 0;
     if (leaves) {
         // candidates per chunk: what the capped scratch holds (at least one), or MEV_LEAF_CHUNK
@@ -1724,87 +1732,35 @@ static int evaluate(mev_handle* h, const mev_evaluate_args* ea, float* leaf_obs,
         if (int r = grow_block(h, &h->d_leaf, &h->leaf_cap, mev::leaf_hand_bytes(h->sp, chunk))) return r;
     }
     mev::SampleIn si{};  // (sm) the device view of the sampling arguments
-    if (sm)
-        si = mev::SampleIn{sm->mean, sm->sigma, sm->actions_out, {sm->lo[0], sm->lo[1]}, {sm->hi[0], sm->hi[1]},
+    Stage st(h, dev);
+    if (sm) {
+        si = mev::SampleIn{nullptr, nullptr, nullptr, {sm->lo[0], sm->lo[1]}, {sm->hi[0], sm->hi[1]},
                            sm->groups, sm->samples, uint32_t(sm->noise_seed), uint32_t(sm->noise_seed >> 32),
                            uint32_t(sm->noise_counter), uint32_t(sm->noise_counter >> 32),
                            (sm->sample_flags & MEV_SAMPLE_MEAN_FIRST) ? 1u : 0u};
-    if (dev) {
-        in.actions = ea->actions;
-        in.spawn_route = ea->spawn_route;
-        rows.reward = ea->reward_seq;
-        rows.done = ea->done_seq;
-        rows.status = ea->status_seq;
+        st.in(&si.mean, sm->mean, T * R * N * 2);
+        st.in(&si.sigma, sm->sigma, T * R * N * 2);
+        st.out(&si.actions_out, sm->actions_out, T * CN * 2);
     } else {
-        // the staging block: every array of this call, each at a 256-byte boundary
-        size_t off = 0;
-        auto take = [&off](bool wanted, size_t bytes) {
-            const size_t at = off;
-            if (wanted) off += (bytes + 255) & ~size_t(255);
-            return at;
-        };
-        const size_t act_bytes = T * CN * 2 * sizeof(float), ms_bytes = T * R * N * 2 * sizeof(float);
-        const size_t o_act = take(!sm || sm->actions_out, act_bytes), o_roots = take(true, R * sizeof(int32_t));
-        const size_t o_mean = take(sm != nullptr, ms_bytes), o_sigma = take(sm != nullptr, ms_bytes);
-        const size_t o_spawn = take(ea->spawn_route != nullptr, T * C * sizeof(int32_t));
-        const size_t o_ret = take(ea->returns != nullptr, CN * sizeof(float));
-        const size_t o_rew = take(ea->reward_seq != nullptr, T * CN * sizeof(float));
-        const size_t o_done = take(ea->done_seq != nullptr, T * CN), o_status = take(ea->status_seq != nullptr, T * CN);
-        const size_t o_sub = take(ea->substeps != nullptr, C * sizeof(int32_t));
-        const size_t o_term = take(ea->terminated != nullptr, C), o_trunc = take(ea->truncated != nullptr, C);
-        const size_t o_obs = take(leaves, obs_bytes);
-        const size_t o_dst = take(xp != nullptr, C * sizeof(int32_t));
-        if (int r = grow_block(h, &h->d_eval, &h->eval_cap, off)) return r;
-        uint8_t* b = h->d_eval;
-        if (sm) {
-            HIP_TRY(hipMemcpyAsync(b + o_mean, sm->mean, ms_bytes, hipMemcpyHostToDevice, h->stream));
-            HIP_TRY(hipMemcpyAsync(b + o_sigma, sm->sigma, ms_bytes, hipMemcpyHostToDevice, h->stream));
-            si.mean = reinterpret_cast<const float*>(b + o_mean);
-            si.sigma = reinterpret_cast<const float*>(b + o_sigma);
-            if (sm->actions_out) si.actions_out = reinterpret_cast<float*>(b + o_act);
-        } else {
-            HIP_TRY(hipMemcpyAsync(b + o_act, ea->actions, act_bytes, hipMemcpyHostToDevice, h->stream));
-            in.actions = reinterpret_cast<const float*>(b + o_act);
-        }
-        HIP_TRY(hipMemcpyAsync(b + o_roots, ea->roots, R * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
-        d_roots = reinterpret_cast<const int32_t*>(b + o_roots);
-        if (ea->spawn_route) {
-            HIP_TRY(hipMemcpyAsync(b + o_spawn, ea->spawn_route, T * C * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
-            in.spawn_route = reinterpret_cast<const int32_t*>(b + o_spawn);
-        }
-        if (ea->returns) eo.returns = reinterpret_cast<float*>(b + o_ret);
-        if (ea->reward_seq) rows.reward = reinterpret_cast<float*>(b + o_rew);
-        if (ea->done_seq) rows.done = b + o_done;
-        if (ea->status_seq) rows.status = b + o_status;
-        if (ea->substeps) eo.substeps = reinterpret_cast<int32_t*>(b + o_sub);
-        if (ea->terminated) eo.terminated = b + o_term;
-        if (ea->truncated) eo.truncated = b + o_trunc;
-        if (leaves) d_leaf_obs = reinterpret_cast<float*>(b + o_obs);
-        if (xp) {
-            HIP_TRY(hipMemcpyAsync(b + o_dst, xp->dst_slots, C * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
-            d_dst = reinterpret_cast<const int32_t*>(b + o_dst);
-        }
+        st.in(&in.actions, ea->actions, T * CN * 2);
     }
+    st.in(&d_roots, ea->roots, R);
+    st.in(&in.spawn_route, ea->spawn_route, T * C);
+    st.out(&eo.returns, ea->returns, CN);
+    st.out(&rows.reward, ea->reward_seq, T * CN);
+    st.out(&rows.done, ea->done_seq, T * CN);
+    st.out(&rows.status, ea->status_seq, T * CN);
+    st.out(&eo.substeps, ea->substeps, C);
+    st.out(&eo.terminated, ea->terminated, C);
+    st.out(&eo.truncated, ea->truncated, C);
+    st.out(&d_leaf_obs, leaf_obs, CN * size_t(h->sp.D));
+    if (xp) st.in(&d_dst, xp->dst_slots, C);
+    if (int r = st.upload()) return r;
     const mev::PlanCall call{int(C), int(T), d_roots, &rows, eo, d_leaf_obs, h->d_leaf, chunk,
                              xp && xp->src ? &xp->src->st : nullptr, xp ? &xp->dst->st : nullptr, d_dst,
                              sm ? &si : nullptr};
     HIP_TRY(mev::launch_plans(h->sp, in, call, h->stream));
-    if (!dev) {
-        auto back = [h](void* dst, const void* src, size_t bytes) {
-            return dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream) : hipSuccess;
-        };
-        HIP_TRY(back(ea->returns, eo.returns, CN * sizeof(float)));
-        HIP_TRY(back(ea->reward_seq, rows.reward, T * CN * sizeof(float)));
-        HIP_TRY(back(ea->done_seq, rows.done, T * CN));
-        HIP_TRY(back(ea->status_seq, rows.status, T * CN));
-        HIP_TRY(back(ea->substeps, eo.substeps, C * sizeof(int32_t)));
-        HIP_TRY(back(ea->terminated, eo.terminated, C));
-        HIP_TRY(back(ea->truncated, eo.truncated, C));
-        HIP_TRY(back(leaf_obs, d_leaf_obs, obs_bytes));
-        if (sm) HIP_TRY(back(sm->actions_out, si.actions_out, T * CN * 2 * sizeof(float)));
-        HIP_TRY(hipStreamSynchronize(h->stream));
-    }
-    return MEV_OK;
+    return st.download();
 }
 
 int mev_evaluate_plans(mev_handle* h, const mev_evaluate_args* ea) {
@@ -1899,20 +1855,6 @@ int mev_pool_slots(const mev_pool* pool, int32_t* slots) {
     return MEV_OK;
 }
 
-// host index arrays of a pool call into the handle's staging block (grown as mev_evaluate_plans grows it)
-static int pool_stage(mev_handle* h, const int32_t* a, const int32_t* b, size_t count, const int32_t** da,
-                      const int32_t** db) {
-    const size_t each = (count * sizeof(int32_t) + 255) & ~size_t(255), need = 2 * each;
-    if (int r = grow_block(h, &h->d_eval, &h->eval_cap, need)) return r;
-    HIP_TRY(hipMemcpyAsync(h->d_eval, a, count * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
-    *da = reinterpret_cast<const int32_t*>(h->d_eval);
-    if (b) {
-        HIP_TRY(hipMemcpyAsync(h->d_eval + each, b, count * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
-        *db = reinterpret_cast<const int32_t*>(h->d_eval + each);
-    }
-    return MEV_OK;
-}
-
 int mev_pool_capture(mev_handle* h, mev_pool* pool, const int32_t* envs, const int32_t* slots, int32_t count,
                      uint32_t flags) {
     if (!h || !pool || !envs || !slots) return fail(MEV_E_INVALID, "null argument");
@@ -1932,12 +1874,13 @@ int mev_pool_capture(mev_handle* h, mev_pool* pool, const int32_t* envs, const i
         }
     HIP_TRY(hipSetDevice(h->cfg.device));
     if (int r = serve_stop(h)) return r;  // (the server holds the stream)
-    const int32_t *d_envs = envs, *d_slots = slots;
-    if (!dev)
-        if (int r = pool_stage(h, envs, slots, size_t(count), &d_envs, &d_slots)) return r;
+    const int32_t *d_envs = nullptr, *d_slots = nullptr;
+    Stage st(h, dev);
+    st.in(&d_envs, envs, size_t(count));
+    st.in(&d_slots, slots, size_t(count));
+    if (int r = st.upload()) return r;
     HIP_TRY(mev::launch_pool_copy(h->sp, mev::pool_of_live(h->sp), pool->st, d_envs, d_slots, count, h->stream));
-    if (!dev) HIP_TRY(hipStreamSynchronize(h->stream));
-    return MEV_OK;
+    return st.download();
 }
 
 int mev_pool_get_state(mev_pool* pool, const int32_t* slots, int32_t count, const mev_state* s, float* ego_dims,
@@ -1953,8 +1896,10 @@ int mev_pool_get_state(mev_pool* pool, const int32_t* slots, int32_t count, cons
     HIP_TRY(hipSetDevice(h->cfg.device));
     if (int r = serve_stop(h)) return r;  // (the server holds the stream)
     // the asked slots gathered into a pool of `count` slots, row i = slot slots[i], then read field by field
-    const int32_t *d_slots = nullptr, *unused = nullptr;
-    if (int r = pool_stage(h, slots, nullptr, size_t(count), &d_slots, &unused)) return r;
+    const int32_t* d_slots = nullptr;
+    Stage st(h, false);
+    st.in(&d_slots, slots, size_t(count));
+    if (int r = st.upload()) return r;
     uint8_t* block = nullptr;
     mev::PoolState g{};
     const hipError_t err = pool_alloc(h, count, &block, &g);
@@ -1963,29 +1908,25 @@ int mev_pool_get_state(mev_pool* pool, const int32_t* slots, int32_t count, cons
         return fail(MEV_E_NOMEM, std::string("device allocation failed: ") + hipGetErrorString(err));
     }
     const size_t S = size_t(count), SN = S * size_t(h->cfg.num_agents), SK = S * size_t(h->cfg.max_npcs);
-    hipError_t e = mev::launch_pool_copy(h->sp, pool->st, g, d_slots, nullptr, count, h->stream);
-    auto back = [&](void* dst, const void* src, size_t bytes) {
-        if (e == hipSuccess && dst && bytes) e = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream);
-    };
+    const hipError_t e = mev::launch_pool_copy(h->sp, pool->st, g, d_slots, nullptr, count, h->stream);
     void* const ego4[mev::EF_COUNT] = {s->x, s->y, s->v, s->heading, s->acc, s->steering, s->prev_dist,
                                       s->prev_a0, s->prev_a1, s->spawn_x, s->spawn_y, s->spawn_v,
                                       s->spawn_heading, s->path_index, s->route, s->intention};
     void* const npc4[mev::NF_COUNT] = {s->npc_x, s->npc_y, s->npc_v, s->npc_heading, s->npc_acc,
                                       s->npc_steering, s->npc_path_index, s->npc_route, s->npc_intention};
-    for (int k = 0; k < mev::EF_COUNT; ++k) back(ego4[k], g.ego + g.ego_stride * k, SN * 4);
-    for (int k = 0; k < mev::NF_COUNT; ++k) back(npc4[k], g.npc + g.npc_stride * k, SK * 4);
-    back(s->alive, g.ego_alive, SN);
-    back(s->npc_alive, g.npc_alive, SK);
-    back(s->npc_count, g.npc_count, S * 4);
-    back(s->step_count, g.step_count, S * 4);
-    back(ego_dims, g.ego_dim, SN * 8);
-    back(npc_dims, g.npc_dim, SK * 8);
-    back(valid, g.valid, S);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    else (void)hipStreamSynchronize(h->stream);
+    for (int k = 0; k < mev::EF_COUNT; ++k) st.fetch(ego4[k], g.ego + g.ego_stride * k, SN * 4);
+    for (int k = 0; k < mev::NF_COUNT; ++k) st.fetch(npc4[k], g.npc + g.npc_stride * k, SK * 4);
+    st.fetch(s->alive, g.ego_alive, SN);
+    st.fetch(s->npc_alive, g.npc_alive, SK);
+    st.fetch(s->npc_count, g.npc_count, S * 4);
+    st.fetch(s->step_count, g.step_count, S * 4);
+    st.fetch(ego_dims, g.ego_dim, SN * 8);
+    st.fetch(npc_dims, g.npc_dim, SK * 8);
+    st.fetch(valid, g.valid, S);
+    const int r = e == hipSuccess ? st.download() : fail(MEV_E_HIP, std::string("mev_pool_get_state: ") + hipGetErrorString(e));
+    if (r) (void)hipStreamSynchronize(h->stream);  // (the gather may still be writing the block)
     (void)hipFree(block);
-    if (e != hipSuccess) return fail(MEV_E_HIP, std::string("mev_pool_get_state: ") + hipGetErrorString(e));
-    return MEV_OK;
+    return r;
 }
 
 int mev_expand_plans(mev_handle* h, const mev_expand_args* xa) {
@@ -2033,63 +1974,22 @@ int mev_update_plans(mev_handle* h, const mev_update_args* ua) {
         }
     HIP_TRY(hipSetDevice(h->cfg.device));
     if (int r = serve_stop(h)) return r;  // (the server holds the stream)
-    mev::UpdateArgs u{ua->actions, ua->scores, ua->returns, ua->groups, ua->samples, ua->length, int32_t(N), ua->mode,
-                      ua->elites, ua->inv_temperature, ua->sigma_min, ua->new_mean, ua->new_sigma, ua->best,
-                      ua->best_score, elites ? ua->order : nullptr, elites ? nullptr : ua->weights};
-    if (dev) {
-        HIP_TRY(mev::launch_update_plans(u, h->stream));
-        return MEV_OK;
-    }
-    // the staging block: every array of this call, each at a 256-byte boundary
-    size_t off = 0;
-    auto take = [&off](bool wanted, size_t bytes) {
-        const size_t at = off;
-        if (wanted) off += (bytes + 255) & ~size_t(255);
-        return at;
-    };
-    const size_t act_bytes = T * C * N * 2 * sizeof(float), ms_bytes = T * G * N * 2 * sizeof(float);
-    const size_t o_act = take(true, act_bytes), o_sc = take(u.scores != nullptr, C * sizeof(float));
-    const size_t o_ret = take(!u.scores, C * N * sizeof(float));
-    const size_t o_mean = take(u.new_mean != nullptr, ms_bytes), o_sigma = take(u.new_sigma != nullptr, ms_bytes);
-    const size_t o_best = take(u.best != nullptr, G * sizeof(int32_t)), o_bs = take(u.best_score != nullptr, G * sizeof(float));
-    const size_t o_ord = take(u.order != nullptr, G * M * sizeof(int32_t)), o_w = take(u.weights != nullptr, C * sizeof(float));
-    if (off > h->eval_cap) {
-        HIP_TRY(hipStreamSynchronize(h->stream));
-        if (h->d_eval) (void)hipFree(h->d_eval);
-        h->d_eval = nullptr;
-        h->eval_cap = 0;
-        const hipError_t err = hipMalloc(reinterpret_cast<void**>(&h->d_eval), off);
-        if (err != hipSuccess) return fail(MEV_E_NOMEM, std::string("device allocation failed: ") + hipGetErrorString(err));
-        h->eval_cap = off;
-    }
-    uint8_t* b = h->d_eval;
-    HIP_TRY(hipMemcpyAsync(b + o_act, ua->actions, act_bytes, hipMemcpyHostToDevice, h->stream));
-    u.actions = reinterpret_cast<const float*>(b + o_act);
-    if (u.scores) {
-        HIP_TRY(hipMemcpyAsync(b + o_sc, ua->scores, C * sizeof(float), hipMemcpyHostToDevice, h->stream));
-        u.scores = reinterpret_cast<const float*>(b + o_sc);
-    } else {
-        HIP_TRY(hipMemcpyAsync(b + o_ret, ua->returns, C * N * sizeof(float), hipMemcpyHostToDevice, h->stream));
-        u.returns = reinterpret_cast<const float*>(b + o_ret);
-    }
-    if (u.new_mean) u.new_mean = reinterpret_cast<float*>(b + o_mean);
-    if (u.new_sigma) u.new_sigma = reinterpret_cast<float*>(b + o_sigma);
-    if (u.best) u.best = reinterpret_cast<int32_t*>(b + o_best);
-    if (u.best_score) u.best_score = reinterpret_cast<float*>(b + o_bs);
-    if (u.order) u.order = reinterpret_cast<int32_t*>(b + o_ord);
-    if (u.weights) u.weights = reinterpret_cast<float*>(b + o_w);
+    mev::UpdateArgs u{};
+    u.groups = ua->groups; u.samples = ua->samples; u.n = ua->length; u.N = int32_t(N);
+    u.mode = ua->mode; u.elites = ua->elites; u.inv_temperature = ua->inv_temperature; u.sigma_min = ua->sigma_min;
+    Stage st(h, dev);
+    st.in(&u.actions, ua->actions, T * C * N * 2);
+    st.in(&u.scores, ua->scores, C);
+    st.in(&u.returns, ua->scores ? nullptr : ua->returns, C * N);  // (read when there are no scores)
+    st.out(&u.new_mean, ua->new_mean, T * G * N * 2);
+    st.out(&u.new_sigma, ua->new_sigma, T * G * N * 2);
+    st.out(&u.best, ua->best, G);
+    st.out(&u.best_score, ua->best_score, G);
+    st.out(&u.order, elites ? ua->order : nullptr, G * M);
+    st.out(&u.weights, elites ? nullptr : ua->weights, C);
+    if (int r = st.upload()) return r;
     HIP_TRY(mev::launch_update_plans(u, h->stream));
-    auto back = [h](void* dst, const void* src, size_t bytes) {
-        return dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream) : hipSuccess;
-    };
-    HIP_TRY(back(ua->new_mean, u.new_mean, ms_bytes));
-    HIP_TRY(back(ua->new_sigma, u.new_sigma, ms_bytes));
-    HIP_TRY(back(ua->best, u.best, G * sizeof(int32_t)));
-    HIP_TRY(back(ua->best_score, u.best_score, G * sizeof(float)));
-    if (elites) HIP_TRY(back(ua->order, u.order, G * M * sizeof(int32_t)));
-    else HIP_TRY(back(ua->weights, u.weights, C * sizeof(float)));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return MEV_OK;
+    return st.download();
 }
 
 static int sync_internal(mev_handle* h);  // below, with mev_device_outputs
@@ -2486,26 +2386,6 @@ static int snap_read_header(mev_handle* h, const void* src, bool dev, bool per_e
     return MEV_OK;
 }
 
-// The snapshot on the device for the per-env copy kernels: a host snapshot is staged in the
-// handle's staging buffer (grown on demand) on the handle's stream.
-static int snap_stage(mev_handle* h, const uint8_t* s, size_t total, bool dev, const uint8_t** dsrc) {
-    *dsrc = s;
-    if (dev) return MEV_OK;
-    if (h->snap_stage_bytes < total) {
-        if (h->d_snap_stage) {
-            HIP_TRY(hipStreamSynchronize(h->stream));
-            HIP_TRY(hipFree(h->d_snap_stage));
-            h->d_snap_stage = nullptr;
-            h->snap_stage_bytes = 0;
-        }
-        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&h->d_snap_stage), total));
-        h->snap_stage_bytes = total;
-    }
-    HIP_TRY(hipMemcpyAsync(h->d_snap_stage, s, total, hipMemcpyHostToDevice, h->stream));
-    *dsrc = h->d_snap_stage;
-    return MEV_OK;
-}
-
 static mev::RestoreTab restore_tab(const std::vector<SnapField>& f, const std::vector<size_t>& off) {
     mev::RestoreTab tab{};
     tab.n = int32_t(f.size());
@@ -2536,24 +2416,21 @@ int mev_restore(mev_handle* h, const void* src, const uint8_t* env_mask, uint32_
     std::vector<size_t> off;
     const size_t total = snap_offsets(f, E, &off);
     const uint8_t* s = static_cast<const uint8_t*>(src);
+    Stage st(h, dev);  // (unmasked: nothing staged, the copies go straight into the state arrays)
     if (!env_mask) {
         const hipMemcpyKind kind = dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
         for (size_t i = 0; i < f.size(); ++i) HIP_TRY(hipMemcpyAsync(f[i].restore, s + off[i], f[i].bpe * E, kind, h->stream));
         h->rng_counter = hd.rng_counter;
         h->sp.dims = hd.dims;
     } else {
-        const uint8_t* dsrc = s;
-        const uint8_t* dmask = env_mask;
-        if (int r = snap_stage(h, s, total, dev, &dsrc)) return r;  // stage the snapshot and the mask on the device
-        if (!dev) {
-            HIP_TRY(hipMemcpyAsync(h->d_mask, env_mask, E, hipMemcpyHostToDevice, h->stream));
-            dmask = h->d_mask;
-        }
+        const uint8_t *dsrc = nullptr, *dmask = nullptr;
+        st.in(&dsrc, s, total);  // the per-env copy kernel reads the snapshot and the mask on the device
+        st.in(&dmask, env_mask, E);
+        if (int r = st.upload()) return r;
         HIP_TRY(mev::launch_restore(restore_tab(f, off), dsrc, dmask, h->cfg.num_envs, h->stream));
         h->sp.dims = h->sp.dims || hd.dims;  // (the sizes arrays hold valid entries either way)
     }
-    if (!dev) HIP_TRY(hipStreamSynchronize(h->stream));
-    return MEV_OK;
+    return st.download();
 }
 
 int mev_restore_map(mev_handle* h, const void* src, const int32_t* env_map, uint32_t flags) {
@@ -2569,7 +2446,6 @@ int mev_restore_map(mev_handle* h, const void* src, const int32_t* env_map, uint
             if (env_map[e] < -1 || env_map[e] >= int32_t(E))
                 return fail(MEV_E_RANGE, "env_map[" + std::to_string(e) + "] = " + std::to_string(env_map[e]) +
                                              " is outside [-1, " + std::to_string(E) + ")");
-        if (int r = scratch(h, true, &h->d_env_map, E)) return r;
     }
     // envs the map leaves alone keep their current outputs: bring those into the handle's own
     // buffers, the restore's targets, first (as a masked mev_restore)
@@ -2580,16 +2456,14 @@ int mev_restore_map(mev_handle* h, const void* src, const int32_t* env_map, uint
     std::vector<size_t> off;
     const size_t total = snap_offsets(f, E, &off);
     const uint8_t* dsrc = nullptr;
-    const int32_t* dmap = env_map;
-    if (int r = snap_stage(h, static_cast<const uint8_t*>(src), total, dev, &dsrc)) return r;
-    if (!dev) {
-        HIP_TRY(hipMemcpyAsync(h->d_env_map, env_map, E * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
-        dmap = h->d_env_map;
-    }
+    const int32_t* dmap = nullptr;
+    Stage st(h, dev);
+    st.in(&dsrc, static_cast<const uint8_t*>(src), total);
+    st.in(&dmap, env_map, E);
+    if (int r = st.upload()) return r;
     HIP_TRY(mev::launch_restore_map(restore_tab(f, off), dsrc, dmap, h->cfg.num_envs, h->stream));
     h->sp.dims = h->sp.dims || hd.dims;  // (the sizes arrays hold valid entries either way)
-    if (!dev) HIP_TRY(hipStreamSynchronize(h->stream));
-    return MEV_OK;
+    return st.download();
 }
 
 // ---- multi-GPU gather (include/marlenv.h) ----------------
