@@ -541,7 +541,7 @@ int mev_expand_plans(mev_handle* h, const mev_expand_args* args);
  * outputs.  Host pointers: a root outside [0, E) -> MEV_E_RANGE; mean, sigma and actions_out go through
  * the same staging block, and the call is synchronous.  Device pointers: such a root makes all `samples`
  * candidates of its group the usual all-zero no-ops (their actions_out rows are still the formula's);
- * no synchronisation.  State pools as source or destination are not part of this call.
+ * no synchronisation.  State pools as source or destination: mev_sample_expand_plans below.
  * Measured (python tools/bench_plan_iteration.py -> profiles/plan_iteration_sweep.json; mev_evaluate_plans'
  * method): at 4096 envs x 8 agents x 64 beams, device pointers, 64 groups x 64 candidates, every output, medians of
  * five blocks -- mev_sample_plans + mev_update_plans (softmax) 65.0 us per iteration at T = 4 against 95.1 us for the
@@ -564,6 +564,52 @@ typedef struct {
     uint32_t sample_flags;    /* MEV_SAMPLE_MEAN_FIRST */
 } mev_sample_args;
 int mev_sample_plans(mev_handle* h, const mev_sample_args* args);
+
+/* Sampled plan expansion: mev_sample_plans whose groups may START from a slot of a pool and whose
+ * candidates' STOP STATES are kept in one -- sampled continuations below the root of a tree (beam
+ * search over sampled plans, multi-level MPPI, sampled MuZero-style expansion).  It is the two calls
+ * at once and defines nothing of its own.  With A = actions_out:
+ *   - every output in sample.eval, leaf_obs, and every field of every slot written in dst (the valid
+ *     bytes included) is bit for bit what mev_expand_plans returns and stores for actions = A,
+ *     roots[c] = sample.eval.roots[c / samples] and the same src, dst, dst_slots and counter_offset;
+ *   - A is bit for bit mev_sample_plans' formula, noise at (noise_seed; noise_counter, c * 64 + i, s),
+ *     MEV_SAMPLE_MEAN_FIRST honoured: a function of mean, sigma, lo, hi, groups, samples and the noise
+ *     stream only, not of src, dst or counter_offset.  Every element of A is written, also for
+ *     candidates that stop early or have no root.
+ * The live batch, last outputs, Philox counter, NPC diagnostics and a snapshot's bytes are untouched.
+ * A root without a state -- roots[g] outside the source, or a src slot whose valid byte is 0 -- is
+ * handled per group as mev_sample_plans handles an out-of-range root: MEV_E_RANGE with host pointers,
+ * nothing changed; with device pointers all `samples` candidates of the group are the all-zero no-ops,
+ * their actions_out rows still the formula's, and nothing is stored for them.
+ * Composition: mev_update_plans(MEV_UPDATE_ELITES) writes order[G][M], the elites' candidate indices; with
+ * dst_slots[c] = c these are the slots of the next level's roots, so a beam search over sampled plans
+ * is sample_expand -> update -> sample_expand -> update ... per level with device pointers throughout:
+ * no host round trip and no framework kernel for the noise.  (Raise counter_offset by the sub-steps
+ * already run and change noise_counter per level.)
+ * Errors: everything mev_sample_plans refuses, plus a null dst or dst_slots and a pool of another handle
+ * (MEV_E_INVALID); "no output pointer at all" is not an error, the pool is an output.  Host pointers:
+ * mev_expand_plans' checks over the C dst_slots entries, each before anything is launched -- an entry
+ * outside [-1, slots of dst) -> MEV_E_RANGE; a slot named twice, or with src == dst an entry that is
+ * one of the G roots -> MEV_E_INVALID -- with the handle and the pools unchanged.  Launch path, staging,
+ * synchronisation and, with leaf_obs, scratch and chunks (MEV_LEAF_CHUNK honoured; a chunk may cut
+ * through a group) as the two calls.
+ * Measured (python tools/bench_sample_expand.py -> profiles/sample_expand_sweep.json; mev_evaluate_plans'
+ * method): at 4096 envs x 8 agents x 64 beams, device pointers, 64 groups x 64 candidates, every output, medians of
+ * five blocks -- the second level of a tree from a pool, one slot per candidate, costs 39.0 us at T = 4 against 54.1 us
+ * for the draw in eager torch followed by mev_expand_plans (72.2 against 87.3 us at T = 8; with leaf_obs 79.8 / 119.1
+ * against 93.8 / 131.3 us; 4096 groups x 4: 130.6 against 147.1 and 248.4 against 261.9 us, with leaf_obs 259.7 against
+ * 271.5 us at T = 4; one-ego traffic 88.8 against 99.1 us, with leaf_obs 124.7 against 137.2 us): below it by more than
+ * the blocks' spreads at nine of the ten measured shapes, by 10.3-16.4 us.  At 4096 groups x 4, T = 8 with leaf_obs it
+ * is 403.8 against 406.4 us, 2.6 us inside a block spread of 10.7 us: no gain shown there.  Over mev_sample_plans from the
+ * live batch the call costs 1.1-4.5 us at 4096 candidates and 4.0-14.3 us at 16384. */
+typedef struct {
+    mev_sample_args sample;    /* exactly as mev_sample_plans, except: sample.eval.roots[g] is a slot of src when src != NULL */
+    const mev_pool* src;       /* NULL: the groups' roots are live envs; else slots of src */
+    mev_pool* dst;             /* required */
+    const int32_t* dst_slots;  /* [C], C = groups * samples: slot that receives candidate c's stop state; -1: not stored */
+    uint64_t counter_offset;   /* NPC spawner: sub-step s uses the handle's counter + counter_offset + (s - 1), keyed by c */
+} mev_sample_expand_args;
+int mev_sample_expand_plans(mev_handle* h, const mev_sample_expand_args* args);
 
 /* The reduction over each group's candidates: the refit half of a CEM / MPPI iteration.  Candidates
  * c = g * samples + j; score[c] = scores[c], or with scores NULL the f32 sum of returns[c][i] over

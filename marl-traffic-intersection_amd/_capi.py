@@ -52,6 +52,7 @@ EXPORTED = (
     "mev_set_beam_angles", "mev_get_beam_angles", "mev_decode_errors", "mev_step_sequence", "mev_restore_map",
     "mev_evaluate_plans", "mev_evaluate_leaves", "mev_pool_create", "mev_pool_destroy", "mev_pool_slots",
     "mev_pool_capture", "mev_pool_get_state", "mev_expand_plans", "mev_sample_plans", "mev_update_plans",
+    "mev_sample_expand_plans",
 )
 
 
@@ -124,6 +125,11 @@ class MevSampleArgs(ctypes.Structure):  # mev_sample_args
                 ("lo", ctypes.c_float * 2), ("hi", ctypes.c_float * 2), ("groups", ctypes.c_int32),
                 ("samples", ctypes.c_int32), ("noise_seed", ctypes.c_uint64), ("noise_counter", ctypes.c_uint64),
                 ("actions_out", _vp), ("sample_flags", ctypes.c_uint32)]
+
+
+class MevSampleExpandArgs(ctypes.Structure):  # mev_sample_expand_args
+    _fields_ = [("sample", MevSampleArgs), ("src", _vp), ("dst", _vp), ("dst_slots", _vp),
+                ("counter_offset", ctypes.c_uint64)]
 
 
 class MevUpdateArgs(ctypes.Structure):  # mev_update_args
@@ -213,6 +219,7 @@ def load_library(variant: str = None):
     L.mev_pool_get_state.argtypes = [_vp, _vp, ctypes.c_int32, ctypes.POINTER(MevState), _vp, _vp, _vp]
     L.mev_expand_plans.argtypes = [_vp, ctypes.POINTER(MevExpandArgs)]
     L.mev_sample_plans.argtypes = [_vp, ctypes.POINTER(MevSampleArgs)]
+    L.mev_sample_expand_plans.argtypes = [_vp, ctypes.POINTER(MevSampleExpandArgs)]
     L.mev_update_plans.argtypes = [_vp, ctypes.POINTER(MevUpdateArgs)]
     L.mev_get_outputs.argtypes = [_vp] + [_vp] * 8 + [ctypes.c_uint32]
     L.mev_get_state.argtypes = [_vp, ctypes.POINTER(MevState)]
@@ -762,7 +769,9 @@ class Handle:
     def sample_plans(self, mean, sigma, roots, samples: int, dt=1.0 / 60.0, gamma: float = 1.0, lo=(-1.0, -1.0),
                      hi=(1.0, 1.0), seed: int = 0, counter: int = 0, mean_first: bool = False, leaf_obs: bool = False,
                      spawn_route=None, out: Optional[dict] = None, device: bool = False, groups: Optional[int] = None,
-                     length: Optional[int] = None, flags: int = 0, sample_flags: Optional[int] = None):
+                     length: Optional[int] = None, flags: int = 0, sample_flags: Optional[int] = None,
+                     src: Optional["Pool"] = None, dst: Optional["Pool"] = None, dst_slots=None,
+                     counter_offset: int = 0):
         """evaluate_plans (leaf_obs=True: with the leaf observations) whose candidates draw their own
         actions on the device -- mev_sample_plans.  mean, sigma [T][G][N][2], roots [G] (the live env
         of each group); candidate c = g * samples + j runs clamp(mean + sigma * eps, lo, hi) with eps
@@ -771,12 +780,20 @@ class Handle:
         mean.  Returns evaluate_plans' outputs over C = G * samples candidates plus `actions_out`
         [T][C][N][2], the actions the candidates ran (every element written).  device=True: every
         array is a device tensor/pointer and only the outputs present in `out` are written; T and G
-        are mean.shape[0] and roots.shape[0] (or `length` / `groups` for raw pointers)."""
+        are mean.shape[0] and roots.shape[0] (or `length` / `groups` for raw pointers).
+        dst (mev_sample_expand_plans): the candidates' stop states go to the slots dst_slots[c] ([C];
+        -1: not stored) of pool `dst`, the groups start from the slots roots[g] of pool `src` (None:
+        from live envs), and the Philox spawner of sub-step s uses the handle's counter +
+        counter_offset + (s - 1), all as expand_plans defines them; an empty `out` is allowed in
+        device mode (the pool is an output).  src or dst_slots without dst: ValueError."""
         N, K = self.N, int(samples)
+        if dst is None and (src is not None or dst_slots is not None):
+            raise ValueError("src and dst_slots need dst (the pool that receives the stop states)")
         if not device:
             mean = np.ascontiguousarray(mean, np.float32)
             sigma = np.ascontiguousarray(sigma, np.float32)
-        sa = MevSampleArgs()
+        xa = MevSampleExpandArgs()
+        sa = xa.sample
         T, C, G, out, _keep = self._plan_args(
             sa.eval, "sample_plans needs mean [T][G][N][2] and roots [G] (or length=T, groups=G)", mean, roots, "G", K,
             groups, length, dt, gamma, spawn_route, out, device, flags, leaf_obs,
@@ -790,7 +807,16 @@ class Handle:
         sa.groups, sa.samples = G, K
         sa.noise_seed, sa.noise_counter = int(seed) & (2**64 - 1), int(counter) & (2**64 - 1)
         sa.sample_flags = (MEV_SAMPLE_MEAN_FIRST if mean_first else 0) if sample_flags is None else int(sample_flags)
-        _check(self._lib.mev_sample_plans(self._h, ctypes.byref(sa)))
+        if dst is None:
+            _check(self._lib.mev_sample_plans(self._h, ctypes.byref(sa)))
+            return out
+        if not device and dst_slots is not None:
+            dst_slots = np.ascontiguousarray(dst_slots, np.int32)
+            if dst_slots.shape != (C,):
+                raise ValueError(f"dst_slots must be [{C}], got {dst_slots.shape}")
+        xa.src, xa.dst, xa.dst_slots = src._p if src is not None else None, dst._p, _ptr(dst_slots)
+        xa.counter_offset = int(counter_offset)
+        _check(self._lib.mev_sample_expand_plans(self._h, ctypes.byref(xa)))
         return out
 
     def update_plans(self, actions, samples: int, scores=None, returns=None, mode: str = "elites",

@@ -1640,16 +1640,18 @@ constexpr size_t kLeafHandCap = size_t(64) << 20;
 // of xp->src when that is set, and their stop states go to slots xp->dst_slots of xp->dst.
 // sm: mev_sample_plans' additions (null: the other calls) -- no actions array: the candidates draw
 // their rows from sm->mean / sm->sigma, roots is [groups], and the rows go to sm->actions_out.
+// Both (mev_sample_expand_plans): the [groups] roots are slots of xp->src when that is set.
 static int evaluate(mev_handle* h, const mev_evaluate_args* ea, float* leaf_obs, const mev_expand_args* xp = nullptr,
                     const mev_sample_args* sm = nullptr) {
     const bool leaves = leaf_obs != nullptr;
-    const char* fn = sm ? "mev_sample_plans" : xp ? "mev_expand_plans" : leaves ? "mev_evaluate_leaves" : "mev_evaluate_plans";
+    const char* fn = sm && xp ? "mev_sample_expand_plans" : sm ? "mev_sample_plans" : xp ? "mev_expand_plans"
+                     : leaves ? "mev_evaluate_leaves" : "mev_evaluate_plans";
     if (xp) {
         if (!xp->dst || !xp->dst_slots) return fail(MEV_E_INVALID, "dst and dst_slots required");
         if (xp->dst->h != h || (xp->src && xp->src->h != h)) return fail(MEV_E_INVALID, "the pool belongs to another handle");
     }
     if (sm) {
-        if (ea->actions) return fail(MEV_E_INVALID, "mev_sample_plans draws the actions: eval.actions must be NULL");
+        if (ea->actions) return fail(MEV_E_INVALID, std::string(fn) + " draws the actions: eval.actions must be NULL");
         if (!ea->roots || !sm->mean || !sm->sigma) return fail(MEV_E_INVALID, "roots, mean and sigma required");
         if (sm->groups < 1 || sm->samples < 1 || int64_t(sm->groups) * sm->samples != int64_t(ea->candidates))
             return fail(MEV_E_INVALID, "candidates must equal groups * samples (each at least 1)");
@@ -1693,7 +1695,7 @@ static int evaluate(mev_handle* h, const mev_evaluate_args* ea, float* leaf_obs,
             taken[size_t(d)] = true;
         }
         if (xp->src == xp->dst)
-            for (size_t c = 0; c < C; ++c)
+            for (size_t c = 0; c < R; ++c)
                 if (taken[size_t(ea->roots[c])])
                     return fail(MEV_E_INVALID, "slot " + std::to_string(ea->roots[c]) + " is a root and in dst_slots");
     }
@@ -1703,7 +1705,7 @@ static int evaluate(mev_handle* h, const mev_evaluate_args* ea, float* leaf_obs,
         std::vector<uint8_t> valid(size_t(xp->src->slots));
         HIP_TRY(hipMemcpyAsync(valid.data(), xp->src->st.valid, valid.size(), hipMemcpyDeviceToHost, h->stream));
         HIP_TRY(hipStreamSynchronize(h->stream));
-        for (size_t c = 0; c < C; ++c)
+        for (size_t c = 0; c < R; ++c)
             if (!valid[size_t(ea->roots[c])])
                 return fail(MEV_E_RANGE, "roots[" + std::to_string(c) + "] = " + std::to_string(ea->roots[c]) +
                                              ": nothing valid is stored in that slot");
@@ -1939,6 +1941,15 @@ int mev_expand_plans(mev_handle* h, const mev_expand_args* xa) {
 int mev_sample_plans(mev_handle* h, const mev_sample_args* sa) {
     if (!h || !sa) return fail(MEV_E_INVALID, "null argument");
     return evaluate(h, &sa->eval, sa->leaf_obs, nullptr, sa);
+}
+
+// mev_sample_expand_plans (include/marlenv.h): mev_sample_plans whose groups may start from slots of a
+// pool and whose candidates' stop states are kept in one (the car kernel's KEEP and SAMPLE modes at
+// once): the sampled call's arguments, and the expansion's over them.
+int mev_sample_expand_plans(mev_handle* h, const mev_sample_expand_args* xa) {
+    if (!h || !xa) return fail(MEV_E_INVALID, "null argument");
+    const mev_expand_args xp{xa->sample.eval, xa->sample.leaf_obs, xa->src, xa->dst, xa->dst_slots, xa->counter_offset};
+    return evaluate(h, &xa->sample.eval, xa->sample.leaf_obs, &xp, &xa->sample);
 }
 
 // mev_update_plans (include/marlenv.h): the reduction over each group's candidates, k_update_plans.

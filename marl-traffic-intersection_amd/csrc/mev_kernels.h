@@ -232,9 +232,9 @@ struct SeqRows {
 };
 hipError_t launch_step_window(const SimParams& p, const StepInputs& in, const Outputs& out, int n,
                               const SeqRows* rows, int32_t* substeps, hipStream_t s);
-// The four plan evaluations (mev_evaluate_plans, mev_evaluate_leaves, mev_expand_plans,
-// mev_sample_plans) are one call, launch_plans, described by a PlanCall below: the paragraphs up to
-// it say what each part of the descriptor adds.
+// The five plan evaluations (mev_evaluate_plans, mev_evaluate_leaves, mev_expand_plans,
+// mev_sample_plans, mev_sample_expand_plans) are one call, launch_plans, described by a PlanCall
+// below: the paragraphs up to it say what each part of the descriptor adds.
 // Plan evaluation (mev_evaluate_plans; leaf_obs, dst and sample null): C candidates, candidate c
 // rolled through a plan of n sub-steps from a private copy of the live env roots[c] (k_cars_repeat<TRAFFIC, true, EVAL =
 // true>), and nothing of p's state, outputs or diagnostics written: one launch of C single-wave
@@ -305,11 +305,12 @@ hipError_t launch_pool_copy(const SimParams& p, const PoolState& src, const Pool
 // ran stops at stores its whole post-step state -- what the plan rollout would write back to an
 // env -- into slot dst_slots[c] of dst and sets the slot's valid byte; an index outside [0,
 // dst.slots) stores nothing.  src and dst may be one pool when no dst slot of the call is a root.
-// Not together with sample.
+// Together with sample (mev_sample_expand_plans): roots is [groups] and names slots of src.
 // Sampled plan evaluation (mev_sample_plans; sample set): the plan evaluation, without or with leaf
 // observations, bit for bit, whose candidates draw their own actions
 // (k_cars_repeat<..., SAMPLE = true>).  in.actions is not read; candidate c = g * samples + j
-// starts from live env roots[g] (roots is [groups], C = groups * samples) and takes, per sub-step
+// starts from live env roots[g] (roots is [groups], C = groups * samples; with dst: from slot
+// roots[g] of src when that is set, and its stop state is kept as above) and takes, per sub-step
 // row s, agent i, component k, clamp(mean[s][g][i][k] + sigma[s][g][i][k] * eps[k], lo[k], hi[k])
 // with eps from Philox4x32-10 keyed by the noise seed at counter (noise counter, c * 64 + i, s).
 // Every element of actions_out (nullable) is written, for candidates that stop early or have no

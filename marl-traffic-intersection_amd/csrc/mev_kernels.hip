@@ -2740,12 +2740,27 @@ struct SampleArgs : EvalArgs {
 struct SampleLeafArgs : LeafArgs {
     SampleIn m;
 };
+// KEEP with SAMPLE (mev_sample_expand_plans): both at once -- ev.roots is [groups] and names slots of
+// the source's view, the candidates draw their actions and their stop states are kept.  The two
+// modes' members under the names the loop reads them by, SampleIn first.
+struct SampleKeepArgs : EvalArgs {
+    SampleIn m;
+    KeepOuts k;
+};
+struct SampleKeepLeafArgs : LeafArgs {
+    SampleIn m;
+    KeepOuts k;
+};
 // k_cars_repeat's argument type for a set of modes: the most derived struct of the chain
-//   RepeatArgs <- SeqArgs <- EvalArgs <- LeafArgs, and KEEP or SAMPLE on top of the last two.
+//   RepeatArgs <- SeqArgs <- EvalArgs <- LeafArgs, and KEEP, SAMPLE or both on top of the last two.
 // (The kernel's mangled name spells this expression out, struct names and nesting: changing either
-// renames all sixteen instantiations in profiles and in comparisons of the code object.)
+// renames all twenty instantiations in profiles and in comparisons of the code object.  KEEP with
+// SAMPLE is the outermost choice: the branches below it are the expression the sixteen kernels
+// before it were named by, and a comparison with a build before it matches by template arguments.)
 template <bool SEQ, bool EVAL, bool LEAF, bool KEEP, bool SAMPLE>
 using PlanArgs = typename std::conditional<
+    KEEP && SAMPLE, typename std::conditional<LEAF, SampleKeepLeafArgs, SampleKeepArgs>::type,
+    typename std::conditional<
     SAMPLE, typename std::conditional<LEAF, SampleLeafArgs, SampleArgs>::type,
     typename std::conditional<
         KEEP, typename std::conditional<LEAF, KeepLeafArgs, KeepArgs>::type,
@@ -2753,7 +2768,7 @@ using PlanArgs = typename std::conditional<
             LEAF, LeafArgs,
             typename std::conditional<EVAL, EvalArgs,
                                       typename std::conditional<SEQ, SeqArgs, RepeatArgs>::type>::type>::type>::
-        type>::type;
+        type>::type>::type;
 // The layout the launchers fill and the kernel reads, held at every build: each struct is its base
 // followed by its own member, at the offsets the code object's kernarg sizes were taken from.
 #pragma clang diagnostic push
@@ -2771,9 +2786,14 @@ MEV_ARGS_LAYOUT(KeepArgs, EvalArgs, k, 1424);
 MEV_ARGS_LAYOUT(KeepLeafArgs, LeafArgs, k, 1472);
 MEV_ARGS_LAYOUT(SampleArgs, EvalArgs, m, 1384);
 MEV_ARGS_LAYOUT(SampleLeafArgs, LeafArgs, m, 1432);
+MEV_ARGS_LAYOUT(SampleKeepArgs, EvalArgs, m, 1496);
+MEV_ARGS_LAYOUT(SampleKeepLeafArgs, LeafArgs, m, 1544);
+static_assert(__builtin_offsetof(SampleKeepArgs, k) == sizeof(SampleArgs) &&
+                  __builtin_offsetof(SampleKeepLeafArgs, k) == sizeof(SampleLeafArgs),
+              "KEEP with SAMPLE: KeepOuts after SampleIn");
 #undef MEV_ARGS_LAYOUT
 #pragma clang diagnostic pop
-static_assert(sizeof(KeepLeafArgs) <= 4096, "the kernel argument segment (the largest of the chain)");
+static_assert(sizeof(SampleKeepLeafArgs) <= 4096, "the kernel argument segment (the largest of the chain)");
 // KEEP: candidate c's stop state into slot dst_slots[c] of k.dst, by every lane of the wave (c, the
 // slot and the root src are wave-uniform).  The values are taken where the next sub-step would read
 // them: cars_pre's respawns were the last writes of the car LDS' state fields (cars_post only reads
@@ -2835,7 +2855,7 @@ __global__ __launch_bounds__(WAVE, TRAFFIC ? 2 : 4) void k_cars_repeat(PlanArgs<
     static_assert(!EVAL || SEQ, "plan evaluation: the plan rollout's loop");
     static_assert(!LEAF || EVAL, "leaf observations: a plan evaluation");
     static_assert(!KEEP || EVAL, "kept stop states: a plan evaluation");
-    static_assert(!SAMPLE || (EVAL && !KEEP), "sampled actions: a plan evaluation from the live batch");
+    static_assert(!SAMPLE || EVAL, "sampled actions: a plan evaluation");
     using Args = PlanArgs<SEQ, EVAL, LEAF, KEEP, SAMPLE>;
     extern __shared__ __align__(16) unsigned char cars_lds[];
     __shared__ typename std::conditional<TRAFFIC, NpcLDS, char>::type nl_storage;
@@ -4438,7 +4458,7 @@ static LeafCast leaf_cast(const SimParams& p, uint8_t* hand, int chunk, float* l
 }
 
 // The plan call's car kernel for one set of modes, over the candidates [c0, c0 + nc): the argument
-// struct of the modes (PlanArgs) is `ea` plus the modes' own members.  The twelve EVAL
+// struct of the modes (PlanArgs) is `ea` plus the modes' own members.  The sixteen EVAL
 // instantiations of k_cars_repeat are named here and nowhere else.
 template <bool LEAF, bool KEEP, bool SAMPLE>
 static hipError_t launch_plan_kernel(bool traffic, int nc, unsigned lds, hipStream_t s, const EvalArgs& ea,
@@ -4449,7 +4469,8 @@ static hipError_t launch_plan_kernel(bool traffic, int nc, unsigned lds, hipStre
         else return ea;
     }();
     const Args a = [&] {
-        if constexpr (KEEP) return Args{base, ko};
+        if constexpr (KEEP && SAMPLE) return Args{base, *sm, ko};
+        else if constexpr (KEEP) return Args{base, ko};
         else if constexpr (SAMPLE) return Args{base, *sm};
         else return base;
     }();
@@ -4457,17 +4478,18 @@ static hipError_t launch_plan_kernel(bool traffic, int nc, unsigned lds, hipStre
     else hipLaunchKernelGGL((k_cars_repeat<false, true, true, LEAF, KEEP, SAMPLE>), dim3(nc), dim3(WAVE), lds, s, a);
     return hipGetLastError();
 }
-// by LEAF | KEEP << 1 | SAMPLE << 2 (KEEP with SAMPLE: no kernel, launch_plans rejects the call)
+// by LEAF | KEEP << 1 | SAMPLE << 2
 static constexpr decltype(&launch_plan_kernel<false, false, false>) kPlanKernels[] = {
     launch_plan_kernel<false, false, false>, launch_plan_kernel<true, false, false>,
     launch_plan_kernel<false, true, false>,  launch_plan_kernel<true, true, false>,
-    launch_plan_kernel<false, false, true>,  launch_plan_kernel<true, false, true>};
+    launch_plan_kernel<false, false, true>,  launch_plan_kernel<true, false, true>,
+    launch_plan_kernel<false, true, true>,   launch_plan_kernel<true, true, true>};
 
 hipError_t launch_plans(const SimParams& p, const StepInputs& in, const PlanCall& c, hipStream_t s) {
     const int C = c.C, n = c.n;
     if (n < 1 || n > kMaxSeq || C < 1 || !c.roots || !c.rows) return hipErrorInvalidValue;
     if (c.leaf_obs && (!c.hand || c.chunk < 1)) return hipErrorInvalidValue;
-    if (c.dst && (c.sample || !c.dst_slots || c.dst->slots < 1)) return hipErrorInvalidValue;
+    if (c.dst && (!c.dst_slots || c.dst->slots < 1)) return hipErrorInvalidValue;
     if (!c.dst && c.src) return hipErrorInvalidValue;
     if (c.sample) {
         const SampleIn& sm = *c.sample;

@@ -334,14 +334,21 @@ class VecIntersectionEnv:
 
     def sample_plans(self, mean, sigma, roots, samples: int, dt=1.0 / 60.0, gamma: float = 1.0, lo=(-1.0, -1.0),
                      hi=(1.0, 1.0), seed: int = 0, counter: int = 0, mean_first: bool = False, leaf_obs: bool = False,
-                     spawn_route=None, copy: bool = False):
+                     spawn_route=None, copy: bool = False, src=None, dst=None, dst_slots=None, counter_offset: int = 0):
         """evaluate_plans whose C = G * samples candidates draw their own actions on the device
         (Handle.sample_plans): mean, sigma [T, G, N, 2], roots [G] -> evaluate_plans' dict plus
         actions_out [T, C, N, 2], the clamped actions the candidates ran.  The noise is the stated
         Irwin-Hall approximation of a unit Gaussian from the Philox stream (seed, counter): pass a
         new counter per iteration.  The same buffers (kept per (T, C)) and stream rules as
-        evaluate_plans; the env's state, last outputs and random stream stay as they are."""
+        evaluate_plans; the env's state, last outputs and random stream stay as they are.
+        dst (mev_sample_expand_plans): the stop states go to slots dst_slots[c] ([C]; -1: not stored)
+        of pool `dst` and the groups start from slots roots[g] of pool `src` (None: from live envs),
+        as in expand_plans -- with dst_slots[c] = c, update_plans' `order` names the next level's
+        roots.  src or dst_slots without dst: ValueError."""
         K, N = int(samples), self.num_agents
+        if dst is None and (src is not None or dst_slots is not None):
+            raise ValueError("src and dst_slots need dst (the pool that receives the stop states)")
+        pool = dict(src=src, dst=dst, dst_slots=dst_slots, counter_offset=counter_offset)
         if self.backend == "torch":
             t = self._torch
             self._bind_stream()
@@ -356,15 +363,19 @@ class VecIntersectionEnv:
                 sp = self._dev_tensor(spawn_route, t.int32)
                 if tuple(sp.shape) != (T, G * K):
                     raise ValueError(f"spawn_route must be [{T}][{G * K}], got {tuple(sp.shape)}")
+            if dst_slots is not None:
+                pool["dst_slots"] = self._dev_tensor(dst_slots, t.int32)
+                if tuple(pool["dst_slots"].shape) != (G * K,):
+                    raise ValueError(f"dst_slots must be [{G * K}], got {tuple(pool['dst_slots'].shape)}")
             self._h.sample_plans(m, s, r, K, dt, gamma, lo, hi, seed, counter, mean_first, leaf_obs, sp, out=o,
-                                 device=True, groups=G, length=T)
+                                 device=True, groups=G, length=T, **pool)
             return {k: v.clone() for k, v in o.items()} if copy else o
         shape = np.shape(mean)
         if len(shape) != 4:
             raise ValueError(f"mean must be [T, G, {N}, 2], got {shape}")
         o = self._sample_out(int(shape[0]), int(shape[1]) * K, leaf_obs)
         self._h.sample_plans(mean, sigma, roots, K, dt, gamma, lo, hi, seed, counter, mean_first, leaf_obs, spawn_route,
-                             out=o)
+                             out=o, **pool)
         return {k: v.copy() for k, v in o.items()} if copy else o
 
     def _sample_out(self, T, C, leaf):
