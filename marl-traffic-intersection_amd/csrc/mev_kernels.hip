@@ -19,6 +19,7 @@
 #include "mev_kernels.h"
 #include "mev_world.h"
 #include "mev_nsort.h"
+#include "mev_roadbound.h"
 
 namespace mev {
 
@@ -3039,86 +3040,13 @@ __global__ __launch_bounds__(WAVE, TRAFFIC ? 2 : 4) void k_cars_repeat(PlanArgs<
 // accumulated distances is absorbed by the slab margins and by one extra probe
 // index at each end of the range, so a real hit is never dropped.
 
-// Straight-line LiDAR arithmetic: the value is computed on every lane (an empty
-// volatile asm statement the compiler cannot sink into a branch), so a select
-// replaces the divergent branch -- exec-mask bookkeeping and a pipeline break --
-// the compiler would otherwise wrap around a short computation.  No instruction
-// is emitted for it.
-template <class T>
-__device__ __forceinline__ T lidar_keep(T v) {
-    asm volatile("" : "+v"(v));
-    return v;
-}
 // beam steps over a provably safe stretch (0 when it is shorter than one step)
 __device__ __forceinline__ int safe_steps(float safe, float stp, float inv_stp) {
     const int j = lidar_keep((int)(safe * inv_stp));
     return (safe >= stp) ? j : 0;
 }
 
-// Distance along a beam from its real point (fx, fy) over which every probe is
-// provably on screen and on the road (the truncated pixel is within 1 px per
-// axis, < 1.42 px, of the real point).  Each bound below alone guarantees its
-// stretch, so the road bound is their maximum; all are directional:
-//  - strips: distance to the strip edge (|x - 375| = rw - 1.5) the ray heads for;
-//  - centre square: inside the square shrunk by 1.55 px, within the current
-//    quadrant (only its own grass disc can be met there), outside that disc
-//    grown by 2 px (extra margin for the tangent-case rounding of the root):
-//    distance to the first of the grown disc, the shrunk square's edge and the
-//    quadrant's edge;
-//  - screen: distance to the half-pixel-inset screen edge.
-__device__ inline float road_safe(float fx, float fy, float dx, float dy, float idx, float idy, float iadx,
-                                  float iady, float rwm, float ccen, float crf) {
-    const float big = 1.0e6f;
-    const float rx = fx - 375.0f, ry = fy - 375.0f;
-    const float ax = fabs_f(rx), ay = fabs_f(ry);
-    const float sx = ax < rwm ? rwm * iadx - rx * idx : 0.0f;
-    const float sy = ay < rwm ? rwm * iady - ry * idy : 0.0f;
-    const float sqm = ccen - 1.55f, rg = crf + 2.0f;
-    // the quadrant the ray is in, or heads into from an axis (rx == 0: the sign of dx)
-    const float qx = rx != 0.0f ? rx : dx, qy = ry != 0.0f ? ry : dy;
-    const float ocx = rx - (qx >= 0.0f ? ccen : -ccen), ocy = ry - (qy >= 0.0f ? ccen : -ccen);
-    const float bq = ocx * dx + ocy * dy;
-    const float cq = ocx * ocx + ocy * ocy - rg * rg;
-    const float disc = bq * bq - cq;
-    const float troot = lidar_keep(-bq - __builtin_amdgcn_sqrtf(disc));
-    const float tdisc = cq <= 0.0f ? 0.0f : ((disc < 0.0f || bq >= 0.0f) ? big : troot);
-    const float tsq = fminf(sqm * iadx - rx * idx, sqm * iady - ry * idy);
-    const float tq = fminf(rx * dx < 0.0f ? -rx * idx : big, ry * dy < 0.0f ? -ry * idy : big);
-    const float sc = fmaxf(ax, ay) < sqm ? fminf(tdisc, fminf(tsq, tq)) : 0.0f;
-    const float road = fmaxf(fmaxf(sx, sy), sc);
-    const float tx = (dx > 0.0f ? 748.5f - fx : fx - 0.5f) * iadx;
-    const float ty = (dy > 0.0f ? 748.5f - fy : fy - 0.5f) * iady;
-    return fminf(road, fminf(tx, ty));
-}
-
-// road_safe from a point every lane of the wave shares (phase 1: the car centre
-// of the pass's agent): the strip and centre-square terms are wave-uniform
-// branches, so a car outside the centre square does not evaluate the disc root.
-__device__ inline float road_safe_uniform(float fx, float fy, float dx, float dy, float idx, float idy, float iadx,
-                                          float iady, float rwm, float ccen, float crf) {
-    const float big = 1.0e6f;
-    const float rx = fx - 375.0f, ry = fy - 375.0f;
-    const float ax = fabs_f(rx), ay = fabs_f(ry);
-    const float sqm = ccen - 1.55f, rg = crf + 2.0f;
-    float road = 0.0f;
-    if (__builtin_amdgcn_readfirstlane((int)(ax < rwm))) road = fmaxf(road, rwm * iadx - rx * idx);
-    if (__builtin_amdgcn_readfirstlane((int)(ay < rwm))) road = fmaxf(road, rwm * iady - ry * idy);
-    if (__builtin_amdgcn_readfirstlane((int)(fmaxf(ax, ay) < sqm))) {
-        const float qx = rx != 0.0f ? rx : dx, qy = ry != 0.0f ? ry : dy;
-        const float ocx = rx - (qx >= 0.0f ? ccen : -ccen), ocy = ry - (qy >= 0.0f ? ccen : -ccen);
-        const float bq = ocx * dx + ocy * dy;
-        const float cq = ocx * ocx + ocy * ocy - rg * rg;
-        const float disc = bq * bq - cq;
-        const float troot = lidar_keep(-bq - __builtin_amdgcn_sqrtf(disc));
-        const float tdisc = cq <= 0.0f ? 0.0f : ((disc < 0.0f || bq >= 0.0f) ? big : troot);
-        const float tsq = fminf(sqm * iadx - rx * idx, sqm * iady - ry * idy);
-        const float tq = fminf(rx * dx < 0.0f ? -rx * idx : big, ry * dy < 0.0f ? -ry * idy : big);
-        road = fmaxf(road, fminf(tdisc, fminf(tsq, tq)));
-    }
-    const float tx = (dx > 0.0f ? 748.5f - fx : fx - 0.5f) * iadx;
-    const float ty = (dy > 0.0f ? 748.5f - fy : fy - 0.5f) * iady;
-    return fminf(road, fminf(tx, ty));
-}
+// (the safe-distance bounds themselves: mev_roadbound.h)
 
 // atan2 to ~1e-5 rad and wrap to [-pi, pi]: culling only (beam ranges carry one
 // beam of margin); every hit is still decided by exact probes.
@@ -3171,6 +3099,16 @@ __device__ inline void slab_clip(float c0, float dc, float idc, float a, float b
 #define MEV_LIDAR_NPR 2
 #endif
 constexpr int LIDAR_NPR = MEV_LIDAR_NPR;
+// The road march's bound (mev_roadbound.h), lidar_body's RB: 0 = road_safe / road_safe_uniform; 1 =
+// road_entry_safe, in phase 1's jump from the car centre and after each phase-2 iteration's probes.
+// 1 in the fused kernels without traffic (config 3 26.03 -> 25.80 us, config 2 10.15 -> 9.76, 96 beams
+// 41.2 -> 39.9, config 5's share 42.98 -> 42.52: profiles/ab_road_entry_bench.txt); the traffic
+// kernels and k_lidar measured the same with either and keep 0.  (MEV_ROAD_BOUND: one value for all.)
+#if defined(MEV_ROAD_BOUND)
+constexpr int kRoadBoundStep = MEV_ROAD_BOUND, kRoadBoundTraffic = MEV_ROAD_BOUND, kRoadBoundLidar = MEV_ROAD_BOUND;
+#else
+constexpr int kRoadBoundStep = 1, kRoadBoundTraffic = 0, kRoadBoundLidar = 0;
+#endif
 // The march's tail (the queue empty, the few longest beams still running, lanes
 // mostly idle): once at most kMarchHelp beams run, each gets a group of 2-8 lanes
 // that test kNptHelp consecutive probes each per step (config 3 39.4 -> 35.6 us,
@@ -3276,7 +3214,7 @@ struct LidarSrcLdsEnvs {
 // SEGL: the car phase's segments by lane (phase 3 below): the fused kernels of the 8-slot layout without
 // traffic, whose pools have at most 8 agents and whose waves at most 8 boxes.
 template <bool TAB, int ILP, class Src, int NPT = LIDAR_NPR, bool HELP = false, int PART = 0, int P1 = 0,
-          bool WC = false, bool SEGL = false>
+          bool WC = false, bool SEGL = false, int RB = 0>
 __device__ __forceinline__ void lidar_body(const SimParams& p, const Outputs& out, const Src& src, const int G,
                                            const int a0, const int na, const int lane, unsigned char* base,
                                            const LidarLayout& lay, const unsigned long long redo = 0ull,
@@ -3396,7 +3334,9 @@ __device__ __forceinline__ void lidar_body(const SimParams& p, const Outputs& ou
         const unsigned pmax = (unsigned)px > (unsigned)py ? (unsigned)px : (unsigned)py;
         const float idx = __builtin_amdgcn_rcpf(dx), idy = __builtin_amdgcn_rcpf(dy);
         float safe;
-        if (uni)
+        if constexpr (RB == 1)
+            safe = road_entry_safe(a.x, a.y, dx, dy, idx, idy, fabs_f(idx), fabs_f(idy), rwm, ccen, crf);
+        else if (uni)
             safe = road_safe_uniform(a.x, a.y, dx, dy, idx, idy, fabs_f(idx), fabs_f(idy), rwm, ccen, crf);
         else
             safe = road_safe(a.x, a.y, dx, dy, idx, idy, fabs_f(idx), fabs_f(idy), rwm, ccen, crf);
@@ -3528,6 +3468,11 @@ __device__ __forceinline__ void lidar_body(const SimParams& p, const Outputs& ou
     int slot = lane < qn ? (int)queue[lane] : -1;
     float cx = 0.0f, cy = 0.0f, dx = 0.0f, dy = 0.0f, idx = 0.0f, idy = 0.0f, iadx = 0.0f, iady = 0.0f;
     int k = 0;
+    // the bound after an iteration's probes
+    auto bound2 = [&](float fx, float fy) -> float {
+        if constexpr (RB == 1) return road_entry_safe(fx, fy, dx, dy, idx, idy, iadx, iady, rwm, ccen, crf);
+        else return road_safe(fx, fy, dx, dy, idx, idy, iadx, iady, rwm, ccen, crf);
+    };
     auto load_beam = [&](int qq) {
         // agent of beam slot qq = j*R + b: exact float quotient (qq < 2^20, R <= 1024)
         const int j = (int)(((float)qq + 0.5f) * invR);
@@ -3543,6 +3488,9 @@ __device__ __forceinline__ void lidar_body(const SimParams& p, const Outputs& ou
     if (slot >= 0) load_beam(slot);
     int* hscr = reinterpret_cast<int*>(base + lay.scr);  // phase 3's scratch, free until then
     bool help = false;
+#if defined(MEV_ITER_COUNTS)  // diagnostic (tools/iter_hist.py): the pool's march iterations and busy lanes
+    int ic_pool = 0, ic_grp = 0, ic_busy = 0, ic_nb = 0;
+#endif
     while (ballot(slot >= 0) != 0ull) {
         // the tail down to <= 16 beams: continue with 4 lanes per beam (below)
         if (HELP && next >= qn && __popcll(ballot(slot >= 0)) <= kMarchHelp) {
@@ -3551,6 +3499,10 @@ __device__ __forceinline__ void lidar_body(const SimParams& p, const Outputs& ou
         }
         // branch-free body: every lane evaluates its probes; idle lanes only skip the store
         const bool act = slot >= 0;
+#if defined(MEV_ITER_COUNTS)
+        ++ic_pool;
+        ic_busy += __popcll(ballot(act));
+#endif
         float fx, fy;
         int r, npr = LIDAR_NPR;
         if (NPT != LIDAR_NPR && next >= qn) {  // wave-uniform: the queue is empty
@@ -3559,9 +3511,8 @@ __device__ __forceinline__ void lidar_body(const SimParams& p, const Outputs& ou
         } else {
             r = probes(cx, cy, dx, dy, k, fx, fy);
         }
-        const float safe = road_safe(fx, fy, dx, dy, idx, idy, iadx, iady, rwm, ccen, crf);
         // probes kl+1 .. kl+j lie within j*step <= safe of the last probe kl = k + npr - 1
-        const int kn = k + npr + safe_steps(safe, stp, inv_stp);
+        const int kn = k + npr + safe_steps(bound2(fx, fy), stp, inv_stp);
         const bool fin = act & ((r >= 0) | (kn >= S));
         if (fin) res[slot] = r >= 0 ? r : (S << 1);
         k = kn;
@@ -3584,6 +3535,9 @@ __device__ __forceinline__ void lidar_body(const SimParams& p, const Outputs& ou
         constexpr int NPH = kNptHelp;
         const unsigned long long am = ballot(slot >= 0);
         const int nb = __popcll(am);
+#if defined(MEV_ITER_COUNTS)
+        ic_nb = nb;
+#endif
         if (slot >= 0) {
             const int rk = lane_rank(am);
             hscr[2 * rk] = slot;
@@ -3598,21 +3552,34 @@ __device__ __forceinline__ void lidar_body(const SimParams& p, const Outputs& ou
             if (slot >= 0) load_beam(slot);
             k = k_h;
             while (ballot(slot >= 0) != 0ull) {
+#if defined(MEV_ITER_COUNTS)
+                ++ic_grp;
+                ic_busy += __popcll(ballot(slot >= 0));
+#endif
                 float fx, fy;
                 const int k0 = k + j * NPH;
                 int r = probes_n(std::integral_constant<int, NPH>{}, cx, cy, dx, dy, k0, fx, fy);
                 r = r >= 0 ? r : 0x7fffffff;
-                const float safe = road_safe(fx, fy, dx, dy, idx, idy, iadx, iady, rwm, ccen, crf);
-                int kn = k0 + NPH + safe_steps(safe, stp, inv_stp);
                 r = min(r, __builtin_amdgcn_mov_dpp(r, 0xB1, 0xf, 0xf, false));  // quad_perm [1,0,3,2]
+                if constexpr (GS != 2) {
+                    r = min(r, __builtin_amdgcn_mov_dpp(r, 0x4E, 0xf, 0xf, false));  // quad_perm [2,3,0,1]
+                    // the other quad's minimum by the half-row mirror
+                    if constexpr (GS == 8) r = min(r, __builtin_amdgcn_mov_dpp(r, 0x141, 0xf, 0xf, false));
+                }
+                // RB == 1 (the entry bound: one pass nearly always): every running group stopped among
+                // these probes -- no jump to compute (wave-uniform)
+                if constexpr (RB == 1) {
+                    if (ballot(slot >= 0 && r == 0x7fffffff) == 0ull) {
+                        if (slot >= 0 && j == 0) res[slot] = r;
+                        break;
+                    }
+                }
+                int kn = k0 + NPH + safe_steps(bound2(fx, fy), stp, inv_stp);
                 if constexpr (GS == 2) {
                     kn = __builtin_amdgcn_mov_dpp(kn, 0xF5, 0xf, 0xf, false);  // quad_perm [1,1,3,3]
                 } else {
-                    r = min(r, __builtin_amdgcn_mov_dpp(r, 0x4E, 0xf, 0xf, false));  // quad_perm [2,3,0,1]
-                    kn = __builtin_amdgcn_mov_dpp(kn, 0xFF, 0xf, 0xf, false);        // quad_perm [3,3,3,3]
-                    if constexpr (GS == 8) {
-                        // the other quad's minimum and lane 7's jump by the half-row mirror
-                        r = min(r, __builtin_amdgcn_mov_dpp(r, 0x141, 0xf, 0xf, false));
+                    kn = __builtin_amdgcn_mov_dpp(kn, 0xFF, 0xf, 0xf, false);  // quad_perm [3,3,3,3]
+                    if constexpr (GS == 8) {  // lane 7's jump by the half-row mirror
                         const int km = __builtin_amdgcn_mov_dpp(kn, 0x141, 0xf, 0xf, false);
                         kn = j < 4 ? km : kn;
                     }
@@ -3627,6 +3594,16 @@ __device__ __forceinline__ void lidar_body(const SimParams& p, const Outputs& ou
         else if (nb <= 16) group_march(std::integral_constant<int, 4>{});
         else group_march(std::integral_constant<int, 2>{});
     }
+#if defined(MEV_ITER_COUNTS)  // slots 0-3: iterations, queued beams, pooled iterations, busy lane-iterations; 4: beams regrouped
+    if (lane == 0 && na == p.N) {
+        unsigned long long* dbg = p.debug + (size_t)(a0 / p.N) * 8;
+        dbg[0] = (unsigned long long)(ic_pool + ic_grp);
+        dbg[1] = (unsigned long long)qn;
+        dbg[2] = (unsigned long long)ic_pool;
+        dbg[3] = (unsigned long long)ic_busy;
+        dbg[4] = (unsigned long long)ic_nb;
+    }
+#endif
     wave_lds_sync();
     if constexpr (PART == 1) return;  // the early split's road march: phase 3 after the car part
 #if defined(MEV_EXP_STOP) && MEV_EXP_STOP == 3  // timing-only: stop after phase 2
@@ -4028,7 +4005,7 @@ __global__ __launch_bounds__(256, 8) void k_lidar(SimParams p, Outputs out, int 
     const int na = a_end - a0 < G ? a_end - a0 : G;
     __builtin_amdgcn_s_setprio(kPrioLidar);
     const LidarLayout lay = lidar_layout(G, p.R, lidar_cand_max(p));
-    lidar_body<TAB, 1>(p, out, LidarSrcHbm{p}, G, a0, na, lane, lds_raw + (size_t)wv * (size_t)lay.bytes, lay);
+    lidar_body<TAB, 1, LidarSrcHbm, LIDAR_NPR, false, 0, 0, false, false, kRoadBoundLidar>(p, out, LidarSrcHbm{p}, G, a0, na, lane, lds_raw + (size_t)wv * (size_t)lay.bytes, lay);
 }
 
 

@@ -116,8 +116,8 @@
 #pragma unroll
         for (int j = 0; j < PK; ++j) src.env[j] = es[j];
         const int nal = __popcll(am);
-        lidar_body<TAB, kEsplitIlp, LidarSrcLdsEnvs<PK>, LIDAR_NPR, true, 1, P1>(p, out, src, PK, 0, nal, lane, lbase,
-                                                                             lay, 0ull, am);
+        lidar_body<TAB, kEsplitIlp, LidarSrcLdsEnvs<PK>, LIDAR_NPR, true, 1, P1, false, false, kRoadBoundTraffic>(
+            p, out, src, PK, 0, nal, lane, lbase, lay, 0ull, am);
         __syncthreads();  // barrier H: the car waves take their egos from here (after their NPC phase)
         __syncthreads();  // barrier B: the car waves' obstacle tables, candidate masks and respawns
         // respawned egos: their spawn poses into ag[] and their beams marched again
@@ -137,8 +137,8 @@
             wave_lds_sync();
         }
         __builtin_amdgcn_s_setprio(kPrioEsplitCarPhase);
-        lidar_body<TAB, kEsplitIlp, LidarSrcLdsEnvs<PK>, LIDAR_NPR, true, 2, P1>(p, out, src, PK, 0, nal, lane, lbase,
-                                                                             lay, redo, am);
+        lidar_body<TAB, kEsplitIlp, LidarSrcLdsEnvs<PK>, LIDAR_NPR, true, 2, P1, false, false, kRoadBoundTraffic>(
+            p, out, src, PK, 0, nal, lane, lbase, lay, redo, am);
         return;
     } else if constexpr (ESPLIT) {
         static_assert(SPLIT && !TRAFFIC && NM > 0, "early split without traffic: two waves");
@@ -191,7 +191,7 @@
             float4* ag = reinterpret_cast<float4*>(lbase + lay.ag);
             if (alive) ag[lane_rank(am)] = make_float4(k.x, k.y, k.h, __int_as_float(g0 + il));
             wave_lds_sync();
-            lidar_body<TAB, kEsplitIlp, LidarSrcLds, LIDAR_NPR, true, 1, P1, false, SEGL>(
+            lidar_body<TAB, kEsplitIlp, LidarSrcLds, LIDAR_NPR, true, 1, P1, false, SEGL, kRoadBoundStep>(
                 p, out, LidarSrcLds{el, g0}, NS, g0, NS, lane, lbase, lay, 0ull, am);
             __syncthreads();  // barrier B: the car part's obstacle table, candidate masks and respawns
             // respawned egos: their spawn poses into ag[] and their beams marched again
@@ -208,7 +208,7 @@
                 wave_lds_sync();
             }
             __builtin_amdgcn_s_setprio(kPrioEsplitCarPhase);
-            lidar_body<TAB, kEsplitIlp, LidarSrcLds, LIDAR_NPR, true, 2, P1, false, SEGL>(
+            lidar_body<TAB, kEsplitIlp, LidarSrcLds, LIDAR_NPR, true, 2, P1, false, SEGL, kRoadBoundStep>(
                 p, out, LidarSrcLds{el, g0}, NS, g0, NS, lane, lbase, lay, redo, am);
         }
         return;
@@ -246,7 +246,8 @@
         if (j0 > 0) wave_lds_sync();
         if (j0 > 0) __builtin_amdgcn_s_setprio(kPrioLidar);  // each further pool (cars and LiDAR start at one level)
         const int na = NS - j0 < G ? NS - j0 : G;
-        lidar_body<TAB, kPhase1Ilp, LidarSrcLds, LIDAR_NPR, true, 0, P1, WC, SEGL>(
+        lidar_body<TAB, kPhase1Ilp, LidarSrcLds, LIDAR_NPR, true, 0, P1, WC, SEGL,
+                   (TRAFFIC ? kRoadBoundTraffic : kRoadBoundStep)>(
             p, out, LidarSrcLds{el, g0}, G, g0 + j0, na, lane, lbase, lay);
     }
 #if defined(MEV_STAMPS_Q)

@@ -1,8 +1,8 @@
 """Diagnostic: road-march (LiDAR phase 2) statistics per beam pool, exp_iters build.
     python tools/iter_hist.py [--step-kernel 2]
 Per pool (k_step: one per env): wave iterations, queued beams after phase 1, the
-iteration at which the queue ran dry (after it only the tail of running beams
-remains) and the lane utilisation (busy lane-iterations / 64 x iterations)."""
+pooled and the helper-group iterations, the beams the helper groups took over and
+the lane utilisation (busy lane-iterations / 64 x iterations)."""
 import argparse
 import os
 import sys
@@ -20,9 +20,10 @@ def main():
     ap.add_argument("--agents", type=int, default=8)
     ap.add_argument("--rays", type=int, default=64)
     ap.add_argument("--pack", type=int, default=0)
+    ap.add_argument("--variant", default="exp_iters", help="the counting build (tools/variants.py)")
     a = ap.parse_args()
     mev = pkgload.load()
-    mev._capi.VARIANT = "exp_iters"
+    mev._capi.VARIANT = a.variant
     h = mev.Handle(num_envs=a.envs, num_agents=a.agents, lidar_rays=a.rays, use_team_reward=1)
     h.set_step_kernel(a.step_kernel)
     h.set_step_pack(a.pack)
@@ -40,14 +41,10 @@ def main():
     print(f"pools: {ok.sum()} of {a.envs}")
     stat("iterations", it[ok])
     stat("queued beams", qn[ok])
-    stat("iteration queue ran dry", dry[ok])
-    stat("tail iterations", (it - dry)[ok])
+    stat("pooled iterations", dry[ok])
+    stat("helper-group iterations", (it - dry)[ok])
+    stat("beams regrouped", d[ok, 4])
     stat("lane utilisation %", 100.0 * busy[ok] / (64.0 * it[ok]))
-    print("phase 3 (car pairs):")
-    stat("segments (agent, box)", d[ok, 4])
-    stat("pairs (beam, box)", d[ok, 5])
-    stat("64-pair chunks", d[ok, 6])
-    stat("probe-loop trips", d[ok, 7])
 
 
 if __name__ == "__main__":

@@ -1,7 +1,9 @@
-"""CPU model of k_lidar's road march (statistics only, not a parity tool):
-iterations per beam for variants of the road/screen safe-distance bound, on
-poses from the C oracle stepping uniform random actions with auto-reset (the
-bench workload).  Each iteration = one exact probe + one bound evaluation.
+"""CPU model of lidar_body's road march (statistics only, not a parity tool; the
+shipped bounds are checked by tests/native/roadbound_check.cpp): queued beams and
+phase-2 iterations for variants of the road/screen safe-distance bound, on poses
+from the C oracle stepping uniform random actions with auto-reset (the bench
+workload).  The march is the kernel's: a jump of 1 + safe_steps from the car
+centre, LIDAR_NPR probes (phase 1), then iterations of 2 probes and a jump.
     python tools/road_bound_model.py [--envs 64] [--steps 200]"""
 from __future__ import annotations
 
@@ -40,7 +42,7 @@ def poses(envs, steps, n=8, rays=64, seed=0):
 
 
 def safe_v0(fx, fy, dx, dy, rw):
-    """The current device bound (road_safe in mev_kernels.hip)."""
+    """The current device bound (road_safe in mev_roadbound.h)."""
     ccen, crf = f32(rw + 84), f32(84)
     rwm = f32(rw - 1.5)
     idx, idy = f32(1) / dx, f32(1) / dy
@@ -92,6 +94,42 @@ def _rest(fx, fy, dx, dy, idx, idy, iadx, iady, rx, ry, ax, ay, sx, sy, sqm, rg,
     return np.minimum(road, np.minimum(tx, ty))
 
 
+def safe_entry(fx, fy, dx, dy, rw):
+    """road_entry_safe (mev_roadbound.h): the ray's first entry into the four grown grass quadrants."""
+    never = f32(1e6)
+    ccen, crf = f32(rw + 84), f32(84)
+    rwm, sqm, rg = f32(rw - 1.5), ccen - f32(1.55), crf + f32(2)
+    with np.errstate(all="ignore"):
+        iadx, iady = np.abs(f32(1) / dx), np.abs(f32(1) / dy)
+        rx, ry = fx - f32(375), fy - f32(375)
+        x, y = np.where(dx < 0, -rx, rx), np.where(dy < 0, -ry, ry)
+        a, b = np.abs(dx), np.abs(dy)
+        txp, txm, txs = (rwm - x) * iadx, (-rwm - x) * iadx, (sqm - x) * iadx
+        typ, tym, tys = (rwm - y) * iady, (-rwm - y) * iady, (sqm - y) * iady
+        inx, iny = np.fmax(txp, 0), np.fmax(typ, 0)
+        t1 = np.fmax(inx, iny)
+        xn, yn = x < -rwm, y < -rwm
+        v4, v2, v3 = xn & yn, xn & (iny < txm), yn & (inx < tym)
+        mA = np.where(v2, iny, np.where(v3, inx, t1))
+        oA = np.where(v2, txm, np.where(v3, tym, never))
+        mB = np.where(v2 | v3, t1, never)
+        m1, o1, m2 = np.where(v4, 0, mA), np.where(v4, np.fmin(txm, tym), oA), np.where(v4, mA, mB)
+        xg, yg = ~(v4 | v2), ~(v4 | v3)
+        ue, ve = np.abs(x + a * m1), np.abs(y + b * m1)
+        ocx, ocy = ue - ccen, ve - ccen
+        bq = ocx * np.where(xg, a, -a) + ocy * np.where(yg, b, -b)
+        cq = ocx * ocx + ocy * ocy - rg * rg
+        disc = bq * bq - cq
+        root = -bq - np.sqrt(np.maximum(disc, 0))
+        tdisc = np.where(cq <= 0, 0, np.where((disc < 0) | (bq >= 0), never, root))
+        tcorner = np.fmin(m1 + tdisc, np.fmin(np.where(xg, txs, never), np.where(yg, tys, never)))
+        tq = np.where(np.maximum(ue, ve) >= sqm, m1, np.where(tcorner < o1, tcorner, never))
+        road = np.fmin(tq, m2)
+        tx = (np.where(dx > 0, f32(373.5), f32(374.5)) - x) * iadx
+        ty = (np.where(dy > 0, f32(373.5), f32(374.5)) - y) * iady
+        return np.fmin(road, np.fmin(tx, ty)).astype(f32)
+
+
 def on_road_px(px, py, rw):
     ccen, cr = rw + 84, 84
     iax, iay = np.abs(px - 375), np.abs(py - 375)
@@ -100,37 +138,58 @@ def on_road_px(px, py, rw):
     return onv <= 0
 
 
-def march(P, rel, safe_fn, rw=126, stp=4.0, S=63):
-    """Returns (iterations per beam, stop index per beam) with the exact probe rule."""
+NPR = 2  # LIDAR_NPR
+
+
+def march(P, rel, safe1, safe2, pre=False, rw=126, stp=4.0, S=63):
+    """lidar_body's march with phase 1's bound safe1 and phase 2's safe2 (pre: phase 2 jumps from the
+    beam's last tested probe before its probes, else after them).  Returns (phase-2 iterations per
+    beam, stop index per beam); a beam with 0 iterations finished in phase 1."""
     A, R = len(P), len(rel)
     cx = np.repeat(P[:, 0], R); cy = np.repeat(P[:, 1], R)
     ang = (np.repeat(P[:, 2], R) + np.tile(rel, A)).astype(f32)
     dx, dy = np.cos(ang).astype(f32), (-np.sin(ang)).astype(f32)
     stp = f32(stp)
-    # phase 1: first probe from the centre
+    n = len(cx)
+
+    def steps(s):
+        with np.errstate(invalid="ignore"):
+            return np.where(s >= stp, np.nan_to_num(s / stp, nan=0.0, posinf=1e6, neginf=0).astype(np.int64), 0)
+
+    def probes(i, k, cnt):
+        """Probes k .. k + cnt - 1 of beams i: (stop index or -1, point of the last probe)."""
+        stop = np.full(len(i), -1, np.int64)
+        for t in range(cnt):
+            kk = k + t
+            d = np.minimum(kk, S - 1).astype(f32) * stp
+            fx, fy = cx[i] + dx[i] * d, cy[i] + dy[i] * d
+            qx, qy = np.trunc(fx).astype(np.int64), np.trunc(fy).astype(np.int64)
+            off = (qx < 0) | (qx >= W) | (qy < 0) | (qy >= W)
+            hit = np.where(kk >= S, True, off | ((kk > 0) & ~on_road_px(qx, qy, rw)))
+            stop = np.where((stop < 0) & hit, np.minimum(kk, S), stop)
+        return stop, fx, fy
+
     px, py = cx.astype(np.int32), cy.astype(np.int32)
     onscr = (px >= 0) & (px < W) & (py >= 0) & (py < W)
-    s0 = safe_fn(cx, cy, dx, dy, rw)
-    k = np.where(onscr, np.where(s0 >= 2 * stp, (s0 / stp).astype(np.int32), 1), 0)
-    it = np.zeros(len(cx), np.int32)
-    stop = np.full(len(cx), -1, np.int32)
-    act = np.ones(len(cx), bool)
+    allb = np.arange(n)
+    k = np.where(onscr, 1 + steps(safe1(cx, cy, dx, dy, rw)), 0)
+    stop, lfx, lfy = probes(allb, k, NPR)
+    k = k + NPR
+    it = np.zeros(n, np.int32)
+    act = stop < 0
     while act.any():
         i = np.nonzero(act)[0]
-        kk = k[i]
-        past = kk >= S
-        d = np.minimum(kk, S - 1).astype(f32) * stp
-        fx, fy = cx[i] + dx[i] * d, cy[i] + dy[i] * d
-        qx, qy = np.trunc(fx).astype(np.int64), np.trunc(fy).astype(np.int64)
-        off = (qx < 0) | (qx >= W) | (qy < 0) | (qy >= W)
-        stp_ = ~past & (off | ((kk > 0) & ~on_road_px(qx, qy, rw)))
-        s = safe_fn(fx, fy, dx[i], dy[i], rw)
-        kn = kk + np.where(s >= 2 * stp, (s / stp).astype(np.int32), 1)
-        fin = past | stp_ | (kn >= S)
         it[i] += 1
-        stop[i[fin]] = np.where(stp_[fin], kk[fin], S)
+        if pre:
+            k[i] += steps(safe2(lfx[i], lfy[i], dx[i], dy[i], rw))
+        st, fx, fy = probes(i, k[i], 2)
+        k[i] += 2
+        if not pre:
+            k[i] += steps(safe2(fx, fy, dx[i], dy[i], rw))
+        lfx[i], lfy[i] = fx, fy
+        fin = (st >= 0) | (k[i] >= S)
+        stop[i[fin]] = np.where(st[fin] >= 0, st[fin], S)
         act[i[fin]] = False
-        k[i] = kn
     return it, stop
 
 
@@ -139,16 +198,23 @@ def main():
     ap.add_argument("--envs", type=int, default=32)
     ap.add_argument("--steps", type=int, default=300)
     a = ap.parse_args()
-    P = poses(a.envs, a.steps)
-    R = 64
+    N, R = 8, 64
+    P = poses(a.envs, a.steps, n=N, rays=R)
     rel = np.array([np.float32(np.float32(-180.0) + np.float32(i) * np.float32(360.0 / (R - 1))) for i in range(R)],
                    np.float32) * np.float32(np.pi / 180.0)
-    base_it, base_stop = march(P, rel, safe_v0)
-    print(f"{len(P)} agent poses x {R} beams")
-    for name, fn in [("v0 (current)", safe_v0), ("v1 exact axes", safe_v1)]:
-        it, stop = march(P, rel, fn)
+    _, base_stop = march(P, rel, safe_v0, safe_v0)
+    print(f"{len(P)} agent poses x {R} beams; an 'env' below = {N} consecutive poses")
+    for name, s1, s2, pre in [("road_safe (current)", safe_v0, safe_v0, False),
+                              ("exact-axes margins", safe_v1, safe_v1, False),
+                              ("entry bound, placement (a)", safe_entry, safe_entry, False),
+                              ("entry bound, placement (b)", safe_v0, safe_entry, True)]:
+        it, stop = march(P, rel, s1, s2, pre)
         assert (stop == base_stop).all(), f"{name}: stop index differs from the current bound"
-        print(f"{name:16s} mean iterations/beam {it.mean():.3f}  hist {np.bincount(it, minlength=8)[:10]}")
+        ne = len(P) // N
+        q = (it > 0)[:ne * N * R].reshape(ne, N * R).sum(1)
+        itb = it[:ne * N * R].reshape(ne, N * R)
+        print(f"{name:28s} queued beams per env mean {q.mean():.1f} p90 {np.percentile(q, 90):.0f} max {q.max()}; "
+              f"beam-iterations per env {itb.sum(1).mean():.1f}; longest beam's iterations per env {itb.max(1).mean():.2f}")
 
 
 if __name__ == "__main__":

@@ -68,7 +68,13 @@ EXPERIMENTS = {"stampsr": ["-DMEV_STAMPS", "-DMEV_STAMPS_R"],
                # the plan rollout (k_cars_repeat<.., SEQ>) issuing a sub-step's action load ahead of the
                # previous sub-step's row stores instead of in its own cars_pre (exact; measured slower:
                # tools/bench_sequence.py)
-               "seqearly": ["-DMEV_SEQ_EARLY_LOAD"]}
+               "seqearly": ["-DMEV_SEQ_EARLY_LOAD"],
+               # the road march's bound in every lidar_body (mev_roadbound.h; exact): road_safe, the entry bound
+               "rb0": ["-DMEV_ROAD_BOUND=0"], "rb1": ["-DMEV_ROAD_BOUND=1"],
+               # diagnostic: the road march's iterations per pool (tools/iter_hist.py --variant), as built / per bound
+               "exp_iters": ["-DMEV_ITER_COUNTS"],
+               "exp_iters_rb0": ["-DMEV_ITER_COUNTS", "-DMEV_ROAD_BOUND=0"],
+               "exp_iters_rb1": ["-DMEV_ITER_COUNTS", "-DMEV_ROAD_BOUND=1"]}
 
 
 def build(name: str, force: bool = False) -> str:
