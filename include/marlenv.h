@@ -778,6 +778,16 @@ int mev_get_step_pack(const mev_handle* h, int32_t* envs_per_wave);
  * nothing in the reference. */
 int mev_set_step_split(mev_handle* h, int32_t mode);
 int mev_get_step_split(const mev_handle* h, int32_t* split);
+/* Which compiled kernel the handle runs (for tests; each pointer may be NULL).
+ * step_row: the row of the k_step instantiation table (kStepKeys, csrc/mev_plan.h)
+ * that the next launched mev_step into the handle's own output buffers runs, -1
+ * on the two-kernel path.  serve_row: the row of k_serve's table (kServeKeys)
+ * that the persistent step server runs for this handle, -1 where it does not
+ * apply.  tab: 1 when the kernels read the LiDAR's probe distances from a table
+ * (lidar_step values whose multiples are not exact), else 0.  A step into a
+ * caller's device rows of the same width runs the same row.  Replaces nothing in
+ * the reference. */
+int mev_get_step_row(const mev_handle* h, int32_t* step_row, int32_t* serve_row, int32_t* tab);
 /* Scheduling (results are identical either way): the NPC-aware env deal of the
  * fused traffic k_step -- workgroups take envs heaviest NPC count first, from
  * orders the previous step built.  on: 1 (default; MEV_NO_DEAL=1 in the

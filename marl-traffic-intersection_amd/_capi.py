@@ -52,7 +52,7 @@ EXPORTED = (
     "mev_set_beam_angles", "mev_get_beam_angles", "mev_decode_errors", "mev_step_sequence", "mev_restore_map",
     "mev_evaluate_plans", "mev_evaluate_leaves", "mev_pool_create", "mev_pool_destroy", "mev_pool_slots",
     "mev_pool_capture", "mev_pool_get_state", "mev_expand_plans", "mev_sample_plans", "mev_update_plans",
-    "mev_sample_expand_plans",
+    "mev_sample_expand_plans", "mev_get_step_row",
 )
 
 
@@ -244,6 +244,7 @@ def load_library(variant: str = None):
     L.mev_set_step_split.argtypes = [_vp, ctypes.c_int32]
     L.mev_set_env_deal.argtypes = [_vp, ctypes.c_int32]
     L.mev_get_step_split.argtypes = [_vp, i32p]
+    L.mev_get_step_row.argtypes = [_vp, i32p, i32p, i32p]
     L.mev_set_serve.argtypes = [_vp, ctypes.c_int32]
     L.mev_serve_stats.argtypes = [_vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64), i32p]
     L.mev_configure.argtypes = [_vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]
@@ -1041,6 +1042,15 @@ class Handle:
         v = ctypes.c_int32()
         _check(self._lib.mev_get_step_split(self._h, ctypes.byref(v)))
         return int(v.value)
+
+    def step_row(self) -> dict:
+        """The compiled kernels this handle runs (mev_get_step_row): `step`, the k_step row (kStepKeys,
+        csrc/mev_plan.h) of the next launched step into the handle's own buffers, -1 on the two-kernel
+        path; `serve`, the k_serve row (kServeKeys) of the persistent step server, -1 where it does
+        not apply; `tab`, 1 when the kernels read the probe distances from a table."""
+        a, b, c = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
+        _check(self._lib.mev_get_step_row(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)))
+        return {"step": int(a.value), "serve": int(b.value), "tab": int(c.value)}
 
     def set_serve(self, mode: int = 1):
         """Host-mode steps through the persistent step server: 0 off, 1 automatic (results identical)."""

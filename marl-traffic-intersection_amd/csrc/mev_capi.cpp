@@ -2259,6 +2259,16 @@ int mev_get_step_split(const mev_handle* h, int32_t* split) {
     return MEV_OK;
 }
 
+int mev_get_step_row(const mev_handle* h, int32_t* step_row, int32_t* serve_row, int32_t* tab) {
+    if (!h) return fail(MEV_E_INVALID, "null handle");
+    const mev::StepPlan pl = mev::plan_step(h->sp);
+    // (the pinned block of a small handle holds rows of the same width as the internal buffers)
+    if (step_row) *step_row = mev::step_row(pl, mev::plain_rows(h->sp, h->internal));
+    if (serve_row) *serve_row = mev::serve_row(pl);
+    if (tab) *tab = h->sp.dist_tab ? 1 : 0;
+    return MEV_OK;
+}
+
 int mev_set_reset_routes(mev_handle* h, const int32_t* routes, int32_t count) {
     if (!h) return fail(MEV_E_INVALID, "null handle");
     if (count < 0 || count > h->P * h->P)

@@ -205,6 +205,12 @@ inline StepShape step_shape(const SimParams& p) {
             !p.no_world_const && !p.dims && reference_world(p)};
 }
 inline StepPlan plan_step(const SimParams& p) { return plan_step(step_shape(p)); }
+// whether a step of p into out writes plain rows: 31 + R floats, every column written by the
+// step, neither compact gather format (what a kernel with the rows at compile time, StepKey::wc,
+// assumes; step_row in mev_plan.h)
+inline bool plain_rows(const SimParams& p, const Outputs& out) {
+    return out.obs_ld == OBS_HEAD + p.R && p.D == out.obs_ld && !out.lidar_u8 && !out.state;
+}
 // ev (nullable): three events recorded before k_cars, between k_cars and k_lidar, after k_lidar
 // (with k_step: before it, and twice after it)
 // dp: a device copy of p (k_step reads its parameters through it)

@@ -4337,13 +4337,11 @@ static const ServeFn kServeFns[][2] = {MEV_SERVE_KERNELS(MEV_SERVE_FNS)};
 
 hipError_t launch_step(const SimParams& p, const SimParams* dp, const StepInputs& in, const Outputs& out,
                        hipStream_t s, const hipEvent_t* ev) {
-    StepPlan pl = plan_step(p);
+    const StepPlan pl = plan_step(p);
     if (pl.path == 0) return hipErrorInvalidValue;
     if (pl.path == 1) return launch_part(p, in, out, 0, p.E, s, ev);
-    // the rows at compile time (StepKey::wc) only for this call's plain rows: 31 + R floats, every
-    // column written by the step, neither compact gather format
-    if (!(out.obs_ld == OBS_HEAD + p.R && p.D == out.obs_ld && !out.lidar_u8 && !out.state)) pl.step.key.wc = 0;
-    const int row = key_row(kStepKeys, pl.step.key);
+    // (the rows at compile time, StepKey::wc, only for this call's plain rows)
+    const int row = step_row(pl, plain_rows(p, out));
     if (row < 0) return hipErrorInvalidValue;  // (a plan without a kernel: a bug, never another kernel)
     if (ev) (void)hipEventRecord(ev[0], s);
     hipLaunchKernelGGL(kStepFns[!p.dist_tab][row], dim3(pl.step.grid), dim3(pl.step.block), pl.step.lds, s,
@@ -4648,7 +4646,7 @@ hipError_t launch_pool_copy(const SimParams& p, const PoolState& src, const Pool
 hipError_t launch_serve(const SimParams& p, const SimParams* dp, const ServeArgs& sa, const Outputs& out,
                         hipStream_t s) {
     const StepPlan pl = plan_step(p);
-    const int row = pl.serve_fits ? serve_row(pl.serve.key) : -1;
+    const int row = serve_row(pl);
     if (row < 0) return hipErrorInvalidValue;
     hipLaunchKernelGGL(kServeFns[row][!p.dist_tab], dim3(pl.serve.grid), dim3(pl.serve.block),
                        pl.serve.lds, s, dp, sa, out);

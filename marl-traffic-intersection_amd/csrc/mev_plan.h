@@ -259,4 +259,18 @@ inline StepPlan plan_step(const StepShape& p) {
     return pl;
 }
 
+// The rows the launchers run for plan pl, and the getter reports (mev_get_step_row): k_step's
+// row in kStepKeys, -1 unless path 2 -- plain_rows: the call's observation rows are 31 + R
+// floats, every column written by the step, neither compact gather format (plain_rows() in
+// mev_kernels.h); only then does the key keep its wc -- and k_serve's row in kServeKeys, -1
+// where the server does not apply.  (-1 on path 2 / with serve_fits: a plan without a kernel,
+// a bug.)
+inline int step_row(const StepPlan& pl, bool plain_rows) {
+    if (pl.path != 2) return -1;
+    StepKey k = pl.step.key;
+    if (!plain_rows) k.wc = 0;
+    return key_row(kStepKeys, k);
+}
+inline int serve_row(const StepPlan& pl) { return pl.serve_fits ? serve_row(pl.serve.key) : -1; }
+
 }  // namespace mev

@@ -33,6 +33,8 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
 import refharness as R  # noqa: E402
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import edge_poses as EP  # noqa: E402  (the edge-pose generator and the `edge` group's configurations)
 
 OUT = os.path.dirname(os.path.abspath(__file__))
 HERE = OUT
@@ -557,6 +559,92 @@ def gen_ties():
         inject=inject_npc_ring(48, spread=340))
 
 
+def run_edge(name: str):
+    """tests/golden/edge_<name>.npz: P pose sets of configuration EP.FIXTURES[name] at the edge poses
+    of tests/edge_poses.py (every kind, interleaved by pose set).  Each pose set is written into a
+    fresh env (rh_set_car, rh_add_npc; respawn off, no spawns) and stepped twice: step 1 with zero
+    actions, step 2 with seeded random ones; even pose sets stand still (v = 0), odd ones have
+    v in [0, 8].  Recorded per pose set: the injected state and everything rh_step and rh_get_cars
+    return for both steps (arrays [P][2]...).  Not a trajectory: golden_replay.scenario_names skips it."""
+    c = EP.FIXTURES[name]
+    lanes, n, K, P, rays = c["lanes"], c["n"], c["npcs"], c["P"], c["rays"]
+    routes = ROUTES3 if lanes == 3 else ROUTES2
+    ego_routes = [routes[i % len(routes)] for i in range(n)]
+    rng = np.random.default_rng(c["seed"])
+    dims = EP.EGO_DIMS if c["dims"] else None
+    x, y, h = EP.poses(rng, n + K, E=P, num_lanes=lanes, kinds=len(EP.KINDS), fov=c["fov"],
+                       lidar_step=c["lidar_step"], dims=dims, npcs=K)
+    dt = 1.0 / 60.0
+    rec = {k: [] for k in ("init_ego_f", "init_ego_i", "init_npc_f", "init_npc_i", "actions", "obs", "rew", "done",
+                           "status", "flags", "spawned", "ego_f", "ego_i", "npc_count", "npc_f", "npc_i", "lidar")}
+    for p in range(P):
+        env = R.RefEnv(num_lanes=lanes, respawn=False, traffic=bool(c["traffic"]), density=0.0, routes=routes,
+                       rays=rays, fov=c["fov"], max_dist=c["max_dist"], step=c["lidar_step"])
+        env.reset()
+        for s, e in ego_routes:
+            assert env.add_car(s, e, tag=routes.index((s, e))) == 0
+        v = np.zeros(n + K) if p % 2 == 0 else rng.uniform(0.0, 8.0, n + K)
+        f, i = env.cars(0)
+        for k in range(n):
+            f[k, 0], f[k, 1], f[k, 2], f[k, 3] = x[p, k], y[p, k], v[k], h[p, k]
+            if dims:
+                f[k, 13], f[k, 14] = dims[k % len(dims)]
+            env.set_car(k, f[k], i[k])
+        for j in range(K):
+            route = int(rng.integers(0, len(routes)))
+            path = env.route_path(route)
+            g = np.zeros(R.NF, np.float32)
+            g[0], g[1], g[2], g[3] = x[p, n + j], y[p, n + j], v[n + j], h[p, n + j]
+            g[6], g[7], g[9] = path[0, 0], path[0, 1], math.atan2(-(path[1, 1] - path[0, 1]), path[1, 0] - path[0, 0])
+            g[13], g[14] = 54.0, 24.0
+            assert env.add_npc(route, g, np.array([1, 0, int(rng.integers(0, 150)), route], np.int32)) == 0
+        ef, ei = env.cars(0)
+        nf, ni = env.cars(1)
+        assert len(nf) == K
+        rec["init_ego_f"].append(ef), rec["init_ego_i"].append(ei)
+        rec["init_npc_f"].append(nf.reshape(K, R.NF)), rec["init_npc_i"].append(ni.reshape(K, R.NI))
+        steps = {k: [] for k in rec if not k.startswith("init_")}
+        for t in range(2):
+            a = np.zeros((n, 2), np.float32) if t == 0 else rng.uniform(-1.0, 1.0, (n, 2)).astype(np.float32)
+            r = env.step(a, dt)
+            steps["actions"].append(a), steps["obs"].append(r["obs"]), steps["rew"].append(r["rew"])
+            steps["done"].append(r["done"].astype(np.uint8)), steps["status"].append(r["status"].astype(np.uint8))
+            steps["flags"].append([r["terminated"], r["truncated"], r["agents_alive"], r["step"]])
+            steps["spawned"].append(r["spawned"])
+            ef, ei = env.cars(0)
+            nf, ni = env.cars(1)
+            kc = len(nf)
+            steps["ego_f"].append(ef), steps["ego_i"].append(ei), steps["npc_count"].append(kc)
+            pf, pi = np.zeros((K, R.NF), np.float32), np.zeros((K, R.NI), np.int32)
+            pf[:kc], pi[:kc] = nf, ni
+            steps["npc_f"].append(pf), steps["npc_i"].append(pi)
+            steps["lidar"].append(env.lidar())
+        for k, vals in steps.items():
+            rec[k].append(vals)
+        env.close()
+    dtypes = dict(init_ego_i=np.int32, init_npc_i=np.int32, done=np.uint8, status=np.uint8, flags=np.int32,
+                  spawned=np.int32, ego_i=np.int32, npc_count=np.int32, npc_i=np.int32)
+    arrays = {k: np.asarray(vals, dtypes.get(k, np.float32)) for k, vals in rec.items()}
+    if rays <= 96:  # (the observation holds every beam)
+        del arrays["lidar"]
+    assert int((arrays["spawned"] >= 0).sum()) == 0
+    meta = dict(name=name, P=P, seed=c["seed"], kinds=list(EP.KINDS), ego_routes=ego_routes, traffic_routes=routes, dt=dt,
+                **{k: c[k] for k in EP.CONFIG_KEYS}, npcs=K, respawn=False, max_steps=2000,
+                # (the trajectories' names for the same things: oracle_replay.make_oracle reads these)
+                num_lanes=lanes, n_agents=n, use_team=False, density=0.0, reward=list(DEFAULT_REWARD))
+    path = os.path.join(OUT, f"edge_{name}.npz")
+    np.savez_compressed(path, meta=np.array(json.dumps(meta)), kind=np.arange(P, dtype=np.int32) % len(EP.KINDS),
+                        **arrays)
+    st = arrays["status"]
+    print(f"edge_{name:32s} P={P} n={n} npcs={K} R={rays} status={ {int(s): int((st == s).sum()) for s in range(6)} } "
+          f"-> {os.path.getsize(path) // 1024} KB")
+
+
+def gen_edge():
+    for name in EP.FIXTURES:
+        run_edge(name)
+
+
 # (name prefix or scenario name, generator, deterministic).  Traffic with density > 0 draws
 # its spawns from the reference's unseeded RNG (TrafficFlow.cpp:278,324): not reproducible.
 def _core():
@@ -607,7 +695,7 @@ def _traffic():
 
 GROUPS = [("core", _core, True), ("dims", gen_dims, True), ("paths", gen_paths, True), ("lidars", gen_lidars, True),
           ("paths_short", gen_paths_short, True), ("ties", gen_ties, True), ("paths_long", gen_paths_long, True),
-          ("paths_past_end", gen_paths_past_end, True), ("no_ego", gen_no_ego, True),
+          ("paths_past_end", gen_paths_past_end, True), ("no_ego", gen_no_ego, True), ("edge", gen_edge, True),
           ("traffic", _traffic, False), ("dims_traffic", gen_dims_traffic, False),
           ("paths_traffic", gen_paths_traffic, False), ("no_ego_traffic", gen_no_ego_traffic, False)]
 

@@ -22,7 +22,7 @@ def scenario_names(prefix: str = "") -> List[str]:
     out = []
     for p in sorted(glob.glob(os.path.join(GOLDEN_DIR, "*.npz"))):
         n = os.path.basename(p)[:-4]
-        if n.startswith("static_"):
+        if n.startswith("static_") or n.startswith("edge_"):  # (edge_*: pose sets, not trajectories; edge_poses.py)
             continue
         if n.startswith(prefix):
             out.append(n)

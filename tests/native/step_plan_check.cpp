@@ -6,6 +6,12 @@
 //   step_plan_check dump K P S      the rows of slice (step_kernel K, step_pack P, step_split S)
 //   step_plan_check dump named      the named shapes' rows
 //   step_plan_check digest          the digest of the rows on stdin (a dump from elsewhere)
+//   step_plan_check rows            the rows of the shapes on stdin: a line holds a row's first ten
+//                                   numbers, then optionally `world` (StepShape::world) and `plain`
+//                                   (the call's rows are plain, step_row in mev_plan.h; default 1);
+//                                   each row is followed by " | wc step_row serve_row": the key's wc
+//                                   as launched and the rows of kStepKeys / kServeKeys (-1: none)
+//   step_plan_check keys            both key tables: "step|serve ROW TRAFFIC NM KM PK SPLIT ESPLIT P1 NC WC"
 //
 // A row: E N R K lidar_slots traffic dims step_kernel step_pack step_split | path pack split
 // (as the getters report them) | the k_step key TRAFFIC NM KM PK SPLIT ESPLIT P1 NC, grid,
@@ -226,6 +232,33 @@ int main(int argc, char** argv) {
         char line[512];
         while (fgets(line, sizeof line, stdin)) h.add(line, strlen(line));
         printf("0x%016llxull\n", (unsigned long long)h.h);
+        return 0;
+    }
+    if (argc == 2 && !strcmp(argv[1], "rows")) {
+        char line[512];
+        while (fgets(line, sizeof line, stdin)) {
+            StepShape s;
+            int world = 0, plain = 1;
+            if (!parse_shape(line, &s)) return 2;
+            sscanf(line, "%*d %*d %*d %*d %*d %*d %*d %*d %*d %*d %d %d", &world, &plain);
+            s.world = world;
+            std::string r = row_text(s);
+            r.pop_back();
+            const StepPlan pl = plan_step(s);
+            const int row = step_row(pl, plain != 0);
+            printf("%s | %d %d %d\n", r.c_str(), row >= 0 ? kStepKeys[row].wc : 0, row, serve_row(pl));
+        }
+        return 0;
+    }
+    if (argc == 2 && !strcmp(argv[1], "keys")) {
+        auto put = [](const char* tab, int row, const StepKey& k) {
+            printf("%s %d %d %d %d %d %d %d %d %d %d\n", tab, row, (int)k.traffic, k.nm, k.km, k.pk, (int)k.split,
+                   (int)k.esplit, k.p1, k.nc, k.wc);
+        };
+        int i = 0;
+        for (const StepKey& k : kStepKeys) put("step", i++, k);
+        i = 0;
+        for (const StepKey& k : kServeKeys) put("serve", i++, k);
         return 0;
     }
     if (argc == 3 && !strcmp(argv[1], "dump") && !strcmp(argv[2], "named")) {

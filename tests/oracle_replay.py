@@ -28,6 +28,9 @@ def make_oracle(meta, lidar=None):
     """lidar: (rays, max_dist, step_size, rel_angles[:rays]) of a per-car LiDAR (None: meta's)."""
     R = int(meta["rays"]) if lidar is None else int(lidar[0])
     kw = {} if lidar is None else dict(max_dist=float(lidar[1]), step=float(lidar[2]), obs_dim=127)
+    if lidar is None:  # (the edge fixtures' LiDAR: meta fov / max_dist / lidar_step, edge_poses.py)
+        kw.update({b: float(meta[a]) for a, b in (("fov", "fov"), ("max_dist", "max_dist"), ("lidar_step", "step"))
+                   if a in meta})
     env = O.OracleEnv(num_lanes=int(meta["num_lanes"]), n_agents=int(meta["n_agents"]), rays=R,
                       obs_dim=kw.pop("obs_dim", int(meta.get("obs_dim", 127 if R <= 96 else 31 + R))),
                       use_team=bool(meta["use_team"]), respawn=bool(meta["respawn"]), max_steps=int(meta["max_steps"]),

@@ -7,60 +7,33 @@ tests/test_lidar_stress_gpu.py); that step's observation is compared bit for bit
 the C restatement's (oracle/marl_oracle.c), in the smallest shapes that reach each
 LiDAR kernel: the metric's one-wave k_step (8 x 64 beams, the split off), its two-wave
 split, the 128-beam kernel (two pools), 96 beams (the dense phase 1), the early split
-(one agent, four envs per workgroup) and the traffic early split (one ego, 32 NPC slots)."""
+(one agent, four envs per workgroup) and the traffic early split (one ego, 32 NPC slots).
+The poses come from tests/edge_poses.py (its first four kinds).  Each shape also states the rows
+of the kernel tables its handle runs (Handle.step_row(): k_step's, k_serve's): a host-mode step
+of a handle whose plan the persistent server holds (8x64_two_waves, 1x64_traffic_split) is
+answered by that k_serve row whenever the server takes it, not launched; tests/test_edge_rows_gpu.py steps every k_step row
+launched and every k_serve row served."""
 import numpy as np
 import pytest
 
 import golden_replay as G
 from conftest import STEP_KERNELS, use_step_kernel
+from edge_poses import beam_quadrants, poses
 import oracle_replay as ORP
 
 pytestmark = pytest.mark.gpu
 
 E, ROUNDS, RW, CR = 64, 3, 126.0, 84.0  # three lanes: the road's half width, the corner radius
 SHAPES = [
-    dict(name="8x64_one_wave", n=8, rays=64, split=1),
-    dict(name="8x64_two_waves", n=8, rays=64),
-    dict(name="8x128_two_pools", n=8, rays=128, split=1),
-    dict(name="8x96_dense", n=8, rays=96, split=1),
-    dict(name="1x64_early_split", n=1, rays=64, pack=4),
-    dict(name="1x64_traffic_split", n=1, rays=64, traffic=True),
+    # rows: (k_step's row, k_serve's row) with the fused kernel asked for (kStepKeys, kServeKeys in csrc/mev_plan.h);
+    # the default obs_dim makes plain rows of 31 + R floats, so 8 x 64 / 128 in one wave run the WC = 1 kernels
+    dict(name="8x64_one_wave", n=8, rays=64, split=1, rows=(33, -1)),
+    dict(name="8x64_two_waves", n=8, rays=64, rows=(16, 3)),
+    dict(name="8x128_two_pools", n=8, rays=128, split=1, rows=(34, -1)),
+    dict(name="8x96_dense", n=8, rays=96, split=1, rows=(26, -1)),
+    dict(name="1x64_early_split", n=1, rays=64, pack=4, rows=(6, -1)),
+    dict(name="1x64_traffic_split", n=1, rays=64, traffic=True, rows=(0, 0)),
 ]
-
-
-def poses(rng, n):
-    """x, y, heading [E][n]; env e holds poses of kind e % 4: 0 grass edges, 1 disc rims,
-    2 the centre square, 3 off the road / off the screen.  Agent i of an env takes quadrant
-    i % 4 (and the far half of its edge for i >= 4), so few cars of an env overlap."""
-    x, y = np.zeros((E, n)), np.zeros((E, n))
-    ccen = RW + CR
-    for e in range(E):
-        kind = e % 4
-        for i in range(n):
-            j = i if n > 1 else int(rng.integers(0, 8))
-            sx, sy = (1, -1)[j & 1], (1, -1)[(j >> 1) & 1]
-            far = j >= 4
-            if kind == 0:
-                u = RW + rng.uniform(-3, 3)  # the strip's edge; along it: from the corner square to the screen's edge
-                v = rng.uniform(RW + 40, ccen + 40) if far else rng.uniform(ccen + 60, 370)
-                if rng.uniform() < 0.3:  # the corner square's outer edge
-                    u, v = rng.uniform(RW + 5, ccen - 5), ccen + rng.uniform(-3, 3)
-                if rng.uniform() < 0.5:
-                    u, v = v, u
-            elif kind == 1:
-                a, rad = rng.uniform(np.pi, 1.5 * np.pi), CR + rng.uniform(-4, 4)
-                u, v = ccen + rad * np.cos(a), ccen + rad * np.sin(a)
-            elif kind == 2:
-                u, v = rng.uniform(0, ccen, 2)
-            else:
-                u, v = rng.uniform(RW + 10, 400, 2) if far else (rng.uniform(0, RW), rng.uniform(365, 400))
-            x[e, i], y[e, i] = 375 + sx * u, 375 + sy * v
-            if kind == 0 and rng.uniform() < 0.5:
-                x[e, i], y[e, i] = np.round(x[e, i]), np.round(y[e, i])
-    h = rng.uniform(-np.pi, np.pi, (E, n))
-    axis = rng.uniform(size=(E, n)) < 0.4
-    h[axis] = rng.integers(-2, 3, int(axis.sum())) * (np.pi / 2)
-    return x, y, h
 
 
 def oracle_obs(shape, st, e, D):
@@ -74,16 +47,6 @@ def oracle_obs(shape, st, e, D):
     r = o.step(np.zeros((n, 2), np.float32), 1.0 / 60.0, -1)
     o.close()
     return r["obs"]
-
-
-def beam_quadrants(h, rays):
-    """[..., rays] the direction quadrant (0..3 by the signs of dx, dy) of every beam of a car with
-    heading h, -1 within 0.01 rad of an axis (Lidar.cpp:24-26: dx = cos, dy = -sin of h + rel)."""
-    rel = (-180.0 + np.arange(rays) * (360.0 / (rays - 1))) * (np.pi / 180.0)
-    ang = np.asarray(h, np.float64)[..., None] + rel
-    dx, dy = np.cos(ang), -np.sin(ang)
-    q = (dx < 0).astype(int) + 2 * (dy < 0).astype(int)
-    return np.where((np.abs(dx) < 0.01) | (np.abs(dy) < 0.01), -1, q)
 
 
 def check_batch(shape, got, st, D):
@@ -122,6 +85,9 @@ def test_lidar_matches_oracle_at_the_road_bounds_edges(mev, shape, kernel):
             h.set_step_pack(shape["pack"])
         want_split = 2 if ("pack" in shape or shape.get("traffic")) else (0 if shape.get("split") == 1 else 1)
         assert h.step_kernel() == 2 and h.step_split() == want_split, (h.step_kernel(), h.step_split())
+        assert h.step_row() == dict(step=shape["rows"][0], serve=shape["rows"][1], tab=0), h.step_row()
+    else:
+        assert h.step_row() == dict(step=-1, serve=-1, tab=0), h.step_row()
     D = h.D
     stops, quads = 0, set()
     for _ in range(ROUNDS):
