@@ -657,6 +657,110 @@ typedef struct {
 } mev_update_args;
 int mev_update_plans(mev_handle* h, const mev_update_args* args);
 
+/* Closed-loop rollouts: a small MLP policy held by the library, evaluated inside the step kernel's
+ * loop on each env's own observation rows -- observe -> act -> step, T times, in ONE launch.
+ *
+ * A policy has one or two hidden layers of 1..MEV_POLICY_MAX_WIDTH units (hidden[1] == 0: one) and an
+ * output layer of 2 units (throttle, steer); in_dim must equal the handle's obs_dim.  Layer l's weights
+ * are row-major [out][in] (torch.nn.Linear.weight's layout), its biases [out]; with one hidden layer
+ * w[2] / b[2] are not read.  flags: MEV_DEVICE_PTRS or 0.  Host pointers: every weight and bias must be
+ * finite (else MEV_E_INVALID) and the call is synchronous.  Device pointers: no validation, no
+ * synchronisation -- the library repacks the weights into its own layout with a small kernel on the
+ * handle's stream, so a training loop pushes new weights every iteration without a host copy, and a
+ * rollout issued before an update on that stream runs the old weights.  mev_policy_update takes a spec of
+ * the same shape.  A policy belongs to its handle: mev_destroy releases the handle's policies.
+ *
+ * THE ARITHMETIC IS PART OF THE CONTRACT.  For an observation row x[0..D), D = obs_dim, padding columns
+ * included as they stand:
+ *
+ *   layer(W, b, x)[j]: y = b[j]; for k = 0 .. in-1 (ascending): y = fmaf(W[j][k], x[k], y)   (f32, one rounding per k)
+ *   relu(y) = y > 0.0f ? y : 0.0f                                                            (NaN and -0.0f give +0.0f)
+ *   h1 = relu(layer(W0, b0, x)); h2 = relu(layer(W1, b1, h1)) (skipped with one hidden layer); mu = layer(W_last, b_last, h)
+ *   action[k] = fminf(fmaxf(sigma ? mu[k] + sigma[k] * eps[k] : mu[k], lo[k]), hi[k])        (multiply, then add: no FMA here)
+ *
+ * eps is mev_sample_plans' noise word for word: Philox4x32-10 with key noise_seed and counter
+ * (lo32(noise_counter), hi32(noise_counter), e * 64 + i, t) -- the env index e in the candidate's place,
+ * t the 0-based sub-step -- eps[0] from words 0, 1 and eps[1] from words 2, 3.  With sigma == NULL no
+ * noise word is drawn.  The FMA chain is this library's one exception to its no-FMA rule (that rule
+ * matches the reference's SSE build; the policy has no reference counterpart); gfx950 keeps f32
+ * subnormals, so the chain is the same bits as a host loop over fmaf.  The action is computed for every
+ * agent slot, alive or not, from the row as it stands.
+ *
+ * mev_rollout_policy is defined, per env and bit for bit, as this loop, obs_0 being the rows
+ * mev_get_outputs would return before the call:
+ *
+ *   for t = 0 .. T-1:
+ *       a_t = policy(obs_t)                                            (every agent of the env)
+ *       r   = mev_step(actions = a_t, dt, spawn_route[t], flags)       (exactly mev_step, MEV_AUTO_RESET included)
+ *       obs_{t+1} = r.obs;  row t of every *_seq array = r's outputs / a_t / mu_t
+ *
+ * All T sub-steps run for every env: nothing stops at an episode's end.  With MEV_AUTO_RESET an env that
+ * ended is reset before its next sub-step, as mev_step does, so its first action after the reset is
+ * computed from the terminal observation, as in the host loop.  The Philox spawner and the reset route
+ * draw use the handle's counter + t, and the counter advances by T.  Afterwards the handle is exactly
+ * where the T mev_step calls would have left it: state and car sizes, pending-reset flags, the last
+ * outputs (mev_get_outputs, mev_device_outputs, DLPack, snapshots), the Philox counter and the NPC
+ * diagnostics.  With device pointers the last outputs are row T-1 of the caller's *_seq arrays where
+ * given (keep them allocated, as after mev_step).  Every element of every given *_seq array is written.
+ * A resident step server is stopped first; the NPC-aware deal restarts afterwards (inside the call the
+ * envs run in the identity order); mev_kernel_timing does not count the call.  Host pointers are staged
+ * and the call is synchronous; device pointers do not synchronise.
+ *
+ * Supported shapes: every shape the fused kernel can hold (what mev_set_step_kernel(2) accepts) with
+ * obs_dim <= 31 + 128; handles with a written beam list or per-car sizes included (the latter run the
+ * runtime layout; mev_get_rollout_row).  Anything else is MEV_E_INVALID: there is no slower fallback.
+ * Errors (MEV_E_INVALID, the handle untouched): a null policy or one of another handle, in_dim !=
+ * obs_dim, length outside 1..MEV_MAX_ROLLOUT, MEV_GATHER_TO_ROOT or an unknown flag, a non-finite bound
+ * or sigma, lo[k] > hi[k], an unsupported shape.
+ * Measured (python tools/bench_rollout.py -> profiles/rollout_sweep.json; mev_evaluate_plans' method):
+ * device pointers, auto-reset, every *_seq output, medians of five blocks (min-max), against (b) the loop a user
+ * runs without the call -- an eager torch nn.Sequential forward, a clamp and mev_step per sub-step into the same
+ * tensors -- and (c) T x mev_step alone on ready-made actions.  4096 envs x 8 agents x 64 beams, policy 95-64-64-2:
+ * a rollout of T = 16 takes 0.943 ms (0.942-0.944), 58.9 us per sub-step, against (b) 1.528 ms (1.525-1.557) and
+ * (c) 0.422 ms; T = 64: 3.670 (3.666-3.676) against 6.115 (6.057-6.218) and 1.683 ms -- below (b) by more than the
+ * blocks' spreads, 1.6x, with the policy costing 31-33 us per sub-step inside the kernel where the step itself is
+ * 26 us (the estimate was a third of the step; supposed, not profiled: its LDS broadcasts and spilled registers,
+ * not its FMAs, set the pace).  64 envs: 0.547 against 1.527 ms, 2.8x.  The runtime-layout row at 4096 x 8 x 64 (per-car sizes): 1.120
+ * against 1.526 ms; the compile-time row is 11 us per sub-step faster than it.  It LOSES with the wider policy
+ * 95-128-128-2 -- 2.315 ms (2.307-2.320) against (b) 1.559 at T = 16, 9.233 against 6.197 ms at T = 64: the framework's
+ * GEMM wins there -- and at 4096 envs x 1 agent with traffic, 1.745 (1.708-1.763) against 1.526 ms: the call runs
+ * one wave per env where mev_step runs the early split, and a wave's policy pass costs the same for 1 agent as for 8. */
+#define MEV_POLICY_MAX_WIDTH 128
+typedef struct mev_policy mev_policy;
+typedef struct {
+    int32_t in_dim;          /* must equal the handle's obs_dim */
+    int32_t hidden[2];       /* widths 1..MEV_POLICY_MAX_WIDTH; hidden[1] == 0: one hidden layer */
+    const float* w[3];       /* layer l: row-major [out][in] */
+    const float* b[3];       /* [out]; the last used layer has out = 2 (throttle, steer) */
+} mev_policy_spec;
+int mev_policy_create(mev_handle* h, const mev_policy_spec* spec, uint32_t flags, mev_policy** out);
+int mev_policy_update(mev_policy* p, const mev_policy_spec* spec, uint32_t flags);
+int mev_policy_destroy(mev_policy* p);
+
+#define MEV_MAX_ROLLOUT 1024
+typedef struct {
+    const mev_policy* policy;
+    int32_t length;                 /* T, 1..MEV_MAX_ROLLOUT */
+    float dt;
+    const int32_t* spawn_route;     /* optional [T][E], as mev_step_sequence's */
+    const float* sigma;             /* optional [2], host, read by value like dt; NULL: deterministic */
+    float lo[2], hi[2];             /* finite, lo <= hi */
+    uint64_t noise_seed, noise_counter;
+    float* obs_seq;                 /* optional [T][E][N][obs_dim]: the observation AFTER sub-step t */
+    float* actions_seq;             /* optional [T][E][N][2]: the actions sub-step t ran */
+    float* mean_seq;                /* optional [T][E][N][2]: mu before noise and clamp */
+    float* reward_seq;              /* optional [T][E][N] */
+    uint8_t *done_seq, *status_seq; /* optional [T][E][N] */
+    uint8_t *terminated_seq, *truncated_seq; /* optional [T][E] */
+    uint32_t flags;                 /* MEV_DEVICE_PTRS | MEV_AUTO_RESET */
+} mev_rollout_args;
+int mev_rollout_policy(mev_handle* h, const mev_rollout_args* args);
+/* The row of k_rollout's instantiation table (MEV_ROLLOUT_KERNELS, csrc/mev_plan.h) that
+ * mev_rollout_policy runs for this handle: 0 the runtime layout without traffic, 1 / 2 the traffic
+ * layouts of <= 32 / 64 NPC slots, 3 the compile-time row of 8 agents x 64 beams; -1 where the call is
+ * not supported. */
+int mev_get_rollout_row(const mev_handle* h, int32_t* row);
+
 /* Outputs of the last step / reset, from the handle's own device buffers.
  * Lifetime: after a step that wrote caller-owned output buffers (device
  * pointers in mev_step_args), this call, mev_device_outputs and

@@ -52,7 +52,8 @@ EXPORTED = (
     "mev_set_beam_angles", "mev_get_beam_angles", "mev_decode_errors", "mev_step_sequence", "mev_restore_map",
     "mev_evaluate_plans", "mev_evaluate_leaves", "mev_pool_create", "mev_pool_destroy", "mev_pool_slots",
     "mev_pool_capture", "mev_pool_get_state", "mev_expand_plans", "mev_sample_plans", "mev_update_plans",
-    "mev_sample_expand_plans", "mev_get_step_row",
+    "mev_sample_expand_plans", "mev_get_step_row", "mev_policy_create", "mev_policy_update", "mev_policy_destroy",
+    "mev_rollout_policy", "mev_get_rollout_row",
 )
 
 
@@ -138,6 +139,34 @@ class MevUpdateArgs(ctypes.Structure):  # mev_update_args
                 ("elites", ctypes.c_int32), ("inv_temperature", ctypes.c_float), ("sigma_min", ctypes.c_float),
                 ("new_mean", _vp), ("new_sigma", _vp), ("best", _vp), ("best_score", _vp), ("order", _vp),
                 ("weights", _vp), ("flags", ctypes.c_uint32)]
+
+
+MEV_POLICY_MAX_WIDTH = 128
+MEV_MAX_ROLLOUT = 1024
+
+
+class MevPolicySpec(ctypes.Structure):  # mev_policy_spec
+    _fields_ = [("in_dim", ctypes.c_int32), ("hidden", ctypes.c_int32 * 2), ("w", _vp * 3), ("b", _vp * 3)]
+
+
+class MevRolloutArgs(ctypes.Structure):  # mev_rollout_args
+    _fields_ = [("policy", _vp), ("length", ctypes.c_int32), ("dt", ctypes.c_float), ("spawn_route", _vp),
+                ("sigma", ctypes.POINTER(ctypes.c_float)), ("lo", ctypes.c_float * 2), ("hi", ctypes.c_float * 2),
+                ("noise_seed", ctypes.c_uint64), ("noise_counter", ctypes.c_uint64), ("obs_seq", _vp),
+                ("actions_seq", _vp), ("mean_seq", _vp), ("reward_seq", _vp), ("done_seq", _vp), ("status_seq", _vp),
+                ("terminated_seq", _vp), ("truncated_seq", _vp), ("flags", ctypes.c_uint32)]
+
+
+# outputs of rollout_policy: (key, dtype, shape of (T, E, N, D))
+_ROLLOUT_OUTS = (("obs_seq", np.float32, lambda T, E, N, D: (T, E, N, D)),
+                 ("actions_seq", np.float32, lambda T, E, N, D: (T, E, N, 2)),
+                 ("mean_seq", np.float32, lambda T, E, N, D: (T, E, N, 2)),
+                 ("reward_seq", np.float32, lambda T, E, N, D: (T, E, N)),
+                 ("done_seq", np.uint8, lambda T, E, N, D: (T, E, N)),
+                 ("status_seq", np.uint8, lambda T, E, N, D: (T, E, N)),
+                 ("terminated_seq", np.uint8, lambda T, E, N, D: (T, E)),
+                 ("truncated_seq", np.uint8, lambda T, E, N, D: (T, E)))
+ROLLOUT_OUTPUTS = tuple(k for k, _, _ in _ROLLOUT_OUTS)
 
 
 # outputs of evaluate_plans: (key, dtype, shape of (T, C, N))
@@ -245,6 +274,11 @@ def load_library(variant: str = None):
     L.mev_set_env_deal.argtypes = [_vp, ctypes.c_int32]
     L.mev_get_step_split.argtypes = [_vp, i32p]
     L.mev_get_step_row.argtypes = [_vp, i32p, i32p, i32p]
+    L.mev_policy_create.argtypes = [_vp, ctypes.POINTER(MevPolicySpec), ctypes.c_uint32, ctypes.POINTER(_vp)]
+    L.mev_policy_update.argtypes = [_vp, ctypes.POINTER(MevPolicySpec), ctypes.c_uint32]
+    L.mev_policy_destroy.argtypes = [_vp]
+    L.mev_rollout_policy.argtypes = [_vp, ctypes.POINTER(MevRolloutArgs)]
+    L.mev_get_rollout_row.argtypes = [_vp, i32p]
     L.mev_set_serve.argtypes = [_vp, ctypes.c_int32]
     L.mev_serve_stats.argtypes = [_vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64), i32p]
     L.mev_configure.argtypes = [_vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]
@@ -820,6 +854,71 @@ class Handle:
         _check(self._lib.mev_sample_expand_plans(self._h, ctypes.byref(xa)))
         return out
 
+    def policy(self, weights, biases, device: bool = False) -> "Policy":
+        """An MLP policy held by the library (mev_policy_create): weights a list of 2 or 3 arrays [out][in]
+        (torch.nn.Linear.weight's layout; the first takes obs_dim inputs, the last has 2 outputs), biases
+        the matching [out] arrays.  device=True: device tensors / pointers (then no check, no sync)."""
+        return Policy(self, weights, biases, device)
+
+    def rollout_row(self) -> int:
+        """The row of k_rollout's table rollout_policy runs for this handle (mev_get_rollout_row); -1: unsupported."""
+        r = ctypes.c_int32()
+        _check(self._lib.mev_get_rollout_row(self._h, ctypes.byref(r)))
+        return r.value
+
+    def rollout_policy(self, policy: "Policy", T: int, dt: float = 1.0 / 60.0, sigma=None, lo=(-1.0, -1.0),
+                       hi=(1.0, 1.0), seed: int = 0, counter: int = 0, auto_reset: bool = False, spawn_route=None,
+                       outputs=ROLLOUT_OUTPUTS, out: Optional[dict] = None, device: bool = False, flags: int = 0):
+        """Closed-loop rollout (mev_rollout_policy): T sub-steps of observe -> policy -> step in one launch,
+        bit for bit the loop of the stated policy arithmetic and `step`.  sigma: None (deterministic) or
+        two host floats; the noise is sample_plans' from the Philox stream (seed, counter) with the env in
+        the candidate's place.  spawn_route optional [T][E].  Returns a dict with the arrays named in
+        `outputs` (ROLLOUT_OUTPUTS: obs_seq [T][E][N][obs_dim], actions_seq / mean_seq [T][E][N][2],
+        reward_seq / done_seq / status_seq [T][E][N], terminated_seq / truncated_seq [T][E]); `out` may
+        hold preallocated ones.  device=True: device tensors, stream-ordered, no host sync -- the arrays
+        of `out`, or new torch tensors for `outputs`; spawn_route is then a device array too."""
+        T, E, N, D = int(T), self.E, self.N, self.D
+        shapes = {k: (dtype, shape(T, E, N, D)) for k, dtype, shape in _ROLLOUT_OUTS}
+        out = dict(out) if out is not None else {}
+        for k in out:
+            if k not in shapes:
+                raise ValueError(f"unknown rollout output {k!r}")
+        if device:
+            missing = [k for k in outputs if out.get(k) is None] if not out else []
+            if missing:
+                import torch
+                dev = f"cuda:{self.config['device']}"
+                for k in missing:
+                    dtype, shape = shapes[k]
+                    out[k] = torch.empty(shape, dtype=torch.float32 if dtype is np.float32 else torch.uint8, device=dev)
+        else:
+            if spawn_route is not None:
+                spawn_route = np.ascontiguousarray(np.asarray(spawn_route, np.int32))
+                if spawn_route.shape != (T, E):
+                    raise ValueError(f"spawn_route must be [{T}][{E}], got {spawn_route.shape}")
+            if not out:
+                for k in outputs:
+                    out[k] = np.zeros(shapes[k][1], shapes[k][0])
+            for k, v in out.items():
+                if v is not None and (v.shape != shapes[k][1] or v.dtype != shapes[k][0]):
+                    raise ValueError(f"{k} must be {np.dtype(shapes[k][0]).name} {list(shapes[k][1])}, got {v.shape}")
+        a = MevRolloutArgs()
+        a.policy = policy._p if policy is not None else None
+        a.length, a.dt = T, float(dt)
+        a.spawn_route = _ptr(spawn_route)
+        sig = None
+        if sigma is not None:
+            sig = (ctypes.c_float * 2)(*[float(v) for v in sigma])
+            a.sigma = ctypes.cast(sig, ctypes.POINTER(ctypes.c_float))
+        a.lo = (ctypes.c_float * 2)(*[float(v) for v in lo])
+        a.hi = (ctypes.c_float * 2)(*[float(v) for v in hi])
+        a.noise_seed, a.noise_counter = int(seed) & (2**64 - 1), int(counter) & (2**64 - 1)
+        for k in shapes:
+            setattr(a, k, _ptr(out.get(k)))
+        a.flags = (MEV_DEVICE_PTRS if device else 0) | (MEV_AUTO_RESET if auto_reset else 0) | int(flags)
+        _check(self._lib.mev_rollout_policy(self._h, ctypes.byref(a)))
+        return out
+
     def update_plans(self, actions, samples: int, scores=None, returns=None, mode: str = "elites",
                      elites: Optional[int] = None, temperature: float = 1.0, sigma_min: float = 0.0,
                      out: Optional[dict] = None, device: bool = False, groups: Optional[int] = None,
@@ -1213,6 +1312,67 @@ class Pool:
         _check(self._lib.mev_pool_get_state(self._p, _ptr(slots), n, ctypes.byref(st), _ptr(ed),
                                             _ptr(nd) if nd.size else None, _ptr(valid)))
         return arrays, (ed, nd), valid
+
+
+class Policy:
+    """An MLP policy of a handle (mev_policy): 1 or 2 hidden layers of <= MEV_POLICY_MAX_WIDTH units and 2
+    outputs, kept on the device in the library's own layout.  `update` takes new weights of the same
+    shape; Handle.close releases a policy that was not closed."""
+
+    def __init__(self, handle: "Handle", weights, biases, device: bool = False):
+        self._handle = handle
+        self._ptr = None
+        p = _vp()
+        spec, _keep = self._spec(weights, biases, device)
+        _check(handle._lib.mev_policy_create(handle._h, ctypes.byref(spec), MEV_DEVICE_PTRS if device else 0,
+                                             ctypes.byref(p)))
+        self._ptr = p
+
+    def _spec(self, weights, biases, device):
+        weights, biases = list(weights), list(biases)
+        if len(weights) not in (2, 3) or len(biases) != len(weights):
+            raise ValueError("a policy has 2 or 3 layers: as many weight arrays as bias arrays")
+        if not device:
+            weights = [np.ascontiguousarray(w, np.float32) for w in weights]
+            biases = [np.ascontiguousarray(b, np.float32) for b in biases]
+        shapes = [tuple(int(x) for x in w.shape) for w in weights]
+        if any(len(sh) != 2 for sh in shapes) or shapes[-1][0] != 2:
+            raise ValueError(f"weights must be [out][in] arrays, the last with 2 outputs, got {shapes}")
+        for l, (sh, b) in enumerate(zip(shapes, biases)):
+            if tuple(int(x) for x in b.shape) != (sh[0],) or (l and sh[1] != shapes[l - 1][0]):
+                raise ValueError(f"layer {l}: weights {sh} do not fit the bias {tuple(b.shape)} or the layer before")
+        if getattr(self, "shapes", shapes) != shapes:
+            raise ValueError(f"update needs the policy's own shape {self.shapes}, got {shapes}")
+        self.shapes = shapes
+        spec = MevPolicySpec()
+        spec.in_dim = shapes[0][1]
+        spec.hidden[0] = shapes[0][0]
+        spec.hidden[1] = shapes[1][0] if len(shapes) == 3 else 0
+        for l, (w, b) in enumerate(zip(weights, biases)):
+            spec.w[l], spec.b[l] = _ptr(w), _ptr(b)
+        return spec, (weights, biases)
+
+    @property
+    def _p(self):
+        if self._ptr is None or not self._handle._h:
+            raise MevError("the policy (or its handle) is closed")
+        return self._ptr
+
+    def update(self, weights, biases, device: bool = False):
+        """New weights of the same shape (mev_policy_update); device=True: stream-ordered, no host copy."""
+        spec, _keep = self._spec(weights, biases, device)
+        _check(self._handle._lib.mev_policy_update(self._p, ctypes.byref(spec), MEV_DEVICE_PTRS if device else 0))
+
+    def close(self):
+        if self._ptr is not None and self._handle._h:
+            self._handle._lib.mev_policy_destroy(self._ptr)
+        self._ptr = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def car_update(kin, throttle: float, steer: float, dt: float):

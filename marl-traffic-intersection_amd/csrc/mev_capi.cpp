@@ -57,6 +57,13 @@ struct mev_pool {
     mev::PoolState st{};
 };
 
+// A policy (mev_policy_create): its device block and where each layer lies in it (mev::PolicyNet).
+struct mev_policy {
+    mev_handle* h = nullptr;
+    float* block = nullptr;
+    mev::PolicyNet net{};
+};
+
 struct mev_handle {
     mev_config cfg{};
     int D = 0, lidar_slots = 0, P = 0, nroutes = 0;
@@ -246,6 +253,7 @@ struct mev_handle {
     uint8_t* gs_pin = nullptr;  // pinned staging of mev_get_state
     size_t gs_cap = 0;
     std::vector<mev_pool*> pools;  // the handle's state pools (mev_pool_create), released with it
+    std::vector<mev_policy*> policies;  // the handle's policies (mev_policy_create), released with it
     ~mev_handle() {
         if (comm_stream) (void)hipStreamSynchronize(comm_stream);
         free_comm();
@@ -258,6 +266,10 @@ struct mev_handle {
         if (d_stage) (void)hipFree(d_stage);
         if (d_leaf) (void)hipFree(d_leaf);
         for (mev_pool* q : pools) {
+            if (q->block) (void)hipFree(q->block);
+            delete q;
+        }
+        for (mev_policy* q : policies) {
             if (q->block) (void)hipFree(q->block);
             delete q;
         }
@@ -1628,6 +1640,210 @@ int mev_step_sequence(mev_handle* h, const mev_sequence_args* sa) {
     if (a->flags & MEV_GATHER_TO_ROOT) return fail(MEV_E_INVALID, "mev_step_sequence does not gather (MEV_GATHER_TO_ROOT)");
     return step_window(h, a, WindowArgs{sa->length, true, sa->dt_seq, sa->substeps, sa->reward_seq, sa->done_seq,
                                     sa->status_seq});
+}
+
+// ---- closed-loop policy rollouts (include/marlenv.h: mev_policy_*, mev_rollout_policy)
+static int sync_internal(mev_handle* h);  // below, with mev_device_outputs
+// A policy: one device block holding each used layer's transposed weights and bias row (mev::PolicyNet).
+static int policy_shape(const mev_handle* h, const mev_policy_spec* spec, mev::PolicyNet* net) {
+    if (spec->in_dim != h->D)
+        return fail(MEV_E_INVALID, "policy in_dim must equal the handle's obs_dim (" + std::to_string(h->D) + ")");
+    if (spec->hidden[0] < 1 || spec->hidden[0] > MEV_POLICY_MAX_WIDTH || spec->hidden[1] < 0 ||
+        spec->hidden[1] > MEV_POLICY_MAX_WIDTH)
+        return fail(MEV_E_INVALID, "policy hidden widths must be in 1.." + std::to_string(MEV_POLICY_MAX_WIDTH) +
+                                       " (hidden[1] == 0: one hidden layer)");
+    *net = mev::PolicyNet{};
+    net->layers = spec->hidden[1] ? 3 : 2;
+    const int widths[4] = {spec->in_dim, spec->hidden[0], spec->hidden[1] ? spec->hidden[1] : 2, 2};
+    for (int l = 0; l < net->layers; ++l) {
+        net->in[l] = widths[l];
+        net->out[l] = widths[l + 1];
+        net->ld[l] = (widths[l + 1] + mev::WAVE - 1) / mev::WAVE * mev::WAVE;
+        if (!spec->w[l] || !spec->b[l]) return fail(MEV_E_INVALID, "policy layer " + std::to_string(l) + ": null weights or biases");
+    }
+    return MEV_OK;
+}
+
+// the spec's weights into the policy's block: staged (host pointers: checked finite first) and repacked on the stream
+static int policy_load(mev_policy* p, const mev_policy_spec* spec, uint32_t flags) {
+    mev_handle* h = p->h;
+    if (flags & ~MEV_DEVICE_PTRS) return fail(MEV_E_INVALID, "policy flags: MEV_DEVICE_PTRS or 0");
+    mev::PolicyNet net{};
+    if (int r = policy_shape(h, spec, &net)) return r;
+    if (p->net.layers && (net.layers != p->net.layers || memcmp(net.out, p->net.out, sizeof net.out) != 0))
+        return fail(MEV_E_INVALID, "mev_policy_update: the spec's shape differs from the policy's");
+    const bool dev = (flags & MEV_DEVICE_PTRS) != 0;
+    if (!dev)
+        for (int l = 0; l < net.layers; ++l) {
+            const size_t nw = size_t(net.in[l]) * size_t(net.out[l]);
+            for (size_t i = 0; i < nw; ++i)
+                if (!std::isfinite(spec->w[l][i])) return fail(MEV_E_INVALID, "policy layer " + std::to_string(l) + ": a weight is not finite");
+            for (int i = 0; i < net.out[l]; ++i)
+                if (!std::isfinite(spec->b[l][i])) return fail(MEV_E_INVALID, "policy layer " + std::to_string(l) + ": a bias is not finite");
+        }
+    HIP_TRY(hipSetDevice(h->cfg.device));
+    if (int r = serve_stop(h)) return r;  // (the server holds the stream)
+    if (!p->block) {
+        size_t floats = 0;
+        for (int l = 0; l < net.layers; ++l) floats += size_t(net.in[l] + 1) * size_t(net.ld[l]);
+        const hipError_t err = dalloc(&p->block, floats);
+        if (err != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(MEV_E_NOMEM, std::string("device allocation failed: ") + hipGetErrorString(err));
+        }
+    }
+    float* at = p->block;
+    for (int l = 0; l < net.layers; ++l) {
+        net.wt[l] = at;
+        at += size_t(net.in[l] + 1) * size_t(net.ld[l]);
+    }
+    const float* w[3] = {nullptr, nullptr, nullptr};
+    const float* b[3] = {nullptr, nullptr, nullptr};
+    Stage st(h, dev);
+    for (int l = 0; l < net.layers; ++l) {
+        st.in(&w[l], spec->w[l], size_t(net.in[l]) * size_t(net.out[l]));
+        st.in(&b[l], spec->b[l], size_t(net.out[l]));
+    }
+    if (int r = st.upload()) return r;
+    HIP_TRY(mev::launch_policy_repack(net, w, b, h->stream));
+    p->net = net;
+    return st.download();
+}
+
+int mev_policy_create(mev_handle* h, const mev_policy_spec* spec, uint32_t flags, mev_policy** out) {
+    if (!h || !spec || !out) return fail(MEV_E_INVALID, "null argument");
+    *out = nullptr;
+    mev_policy* p = new mev_policy;
+    p->h = h;
+    if (int r = policy_load(p, spec, flags)) {
+        if (p->block) (void)hipFree(p->block);
+        delete p;
+        return r;
+    }
+    h->policies.push_back(p);
+    *out = p;
+    return MEV_OK;
+}
+
+int mev_policy_update(mev_policy* p, const mev_policy_spec* spec, uint32_t flags) {
+    if (!p || !spec) return fail(MEV_E_INVALID, "null argument");
+    return policy_load(p, spec, flags);
+}
+
+int mev_policy_destroy(mev_policy* p) {
+    if (!p) return MEV_OK;
+    mev_handle* h = p->h;
+    (void)hipSetDevice(h->cfg.device);
+    (void)serve_stop(h);
+    (void)hipStreamSynchronize(h->stream);  // (a rollout in flight may still read it)
+    for (size_t i = 0; i < h->policies.size(); ++i)
+        if (h->policies[i] == p) {
+            h->policies.erase(h->policies.begin() + long(i));
+            break;
+        }
+    if (p->block) (void)hipFree(p->block);
+    delete p;
+    return MEV_OK;
+}
+
+static mev::RolloutPlan rollout_plan(const mev_handle* h, int hidden) {
+    return mev::plan_rollout(mev::step_shape(h->sp), h->D, hidden);
+}
+
+int mev_get_rollout_row(const mev_handle* h, int32_t* row) {
+    if (!h || !row) return fail(MEV_E_INVALID, "null argument");
+    *row = rollout_plan(h, 2 * 64).row;
+    return MEV_OK;
+}
+
+// mev_rollout_policy: T sub-steps of policy + fused step in one launch (k_rollout), along step_window's path
+int mev_rollout_policy(mev_handle* h, const mev_rollout_args* a) {
+    if (!h || !a) return fail(MEV_E_INVALID, "null argument");
+    const mev_policy* pol = a->policy;
+    if (!pol) return fail(MEV_E_INVALID, "mev_rollout_policy: policy required");
+    if (pol->h != h) return fail(MEV_E_INVALID, "mev_rollout_policy: the policy belongs to another handle");
+    if (pol->net.in[0] != h->D) return fail(MEV_E_INVALID, "mev_rollout_policy: policy in_dim != obs_dim");
+    if (a->length < 1 || a->length > MEV_MAX_ROLLOUT)
+        return fail(MEV_E_INVALID, "length must be in 1.." + std::to_string(MEV_MAX_ROLLOUT));
+    if (a->flags & MEV_GATHER_TO_ROOT) return fail(MEV_E_INVALID, "mev_rollout_policy does not gather (MEV_GATHER_TO_ROOT)");
+    if (a->flags & ~(MEV_DEVICE_PTRS | MEV_AUTO_RESET)) return fail(MEV_E_INVALID, "mev_rollout_policy: unknown flag");
+    for (int k = 0; k < 2; ++k) {
+        if (!std::isfinite(a->lo[k]) || !std::isfinite(a->hi[k]) || a->lo[k] > a->hi[k])
+            return fail(MEV_E_INVALID, "mev_rollout_policy: lo / hi must be finite with lo <= hi");
+        if (a->sigma && !std::isfinite(a->sigma[k])) return fail(MEV_E_INVALID, "mev_rollout_policy: sigma must be finite");
+    }
+    const int hidden = pol->net.out[0] + (pol->net.layers == 3 ? pol->net.out[1] : 0);
+    const mev::RolloutPlan rp = rollout_plan(h, hidden);
+    if (rp.row < 0)
+        return fail(MEV_E_INVALID, "mev_rollout_policy: unsupported shape (the fused step kernel must hold the env, and obs_dim <= 31 + " +
+                                       std::to_string(MEV_POLICY_MAX_WIDTH) + ")");
+    HIP_TRY(hipSetDevice(h->cfg.device));
+    if (int r = serve_stop(h)) return r;  // (the server holds the stream)
+    if (h->last.lidar_u8 || !h->last.obs)  // a compact gather row: obs_0 decoded into the handle's buffers
+        if (int r = sync_internal(h)) return r;
+    if (!h->sp_valid || memcmp(&h->sp, &h->sp_dev, sizeof(mev::SimParams)) != 0) {  // (as mev_step)
+        HIP_TRY(hipMemcpyAsync(h->d_sp, &h->sp, sizeof(mev::SimParams), hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        memcpy(&h->sp_dev, &h->sp, sizeof(mev::SimParams));
+        h->sp_valid = true;
+    }
+    const bool dev = (a->flags & MEV_DEVICE_PTRS) != 0;
+    const int T = a->length;
+    const size_t E = size_t(h->cfg.num_envs), EN = E * size_t(h->cfg.num_agents), D = size_t(h->D);
+    mev::RolloutArgs ra{};
+    ra.in.dt = a->dt;
+    ra.in.spawn_prob = spawn_prob(h, a->dt);
+    ra.in.auto_reset = (a->flags & MEV_AUTO_RESET) ? 1 : 0;
+    ra.in.rng_counter = h->rng_counter;  // sub-step t: + t (k_rollout)
+    ra.net = pol->net;
+    ra.T = T;
+    ra.pol_off = rp.pol_off;
+    ra.obs0 = h->last.obs;
+    ra.act_scratch = h->d_actions;
+    ra.noisy = a->sigma ? 1 : 0;
+    for (int k = 0; k < 2; ++k) {
+        ra.sigma[k] = a->sigma ? a->sigma[k] : 0.0f;
+        ra.lo[k] = a->lo[k];
+        ra.hi[k] = a->hi[k];
+    }
+    ra.seed_lo = uint32_t(a->noise_seed);
+    ra.seed_hi = uint32_t(a->noise_seed >> 32);
+    ra.ctr_lo = uint32_t(a->noise_counter);
+    ra.ctr_hi = uint32_t(a->noise_counter >> 32);
+    Stage st(h, dev);
+    st.in(&ra.in.spawn_route, a->spawn_route, size_t(T) * E);
+    st.out(&ra.obs_seq, a->obs_seq, size_t(T) * EN * D);
+    st.out(&ra.actions_seq, a->actions_seq, size_t(T) * EN * 2);
+    st.out(&ra.mean_seq, a->mean_seq, size_t(T) * EN * 2);
+    st.out(&ra.reward_seq, a->reward_seq, size_t(T) * EN);
+    st.out(&ra.done_seq, a->done_seq, size_t(T) * EN);
+    st.out(&ra.status_seq, a->status_seq, size_t(T) * EN);
+    st.out(&ra.term_seq, a->terminated_seq, size_t(T) * E);
+    st.out(&ra.trunc_seq, a->truncated_seq, size_t(T) * E);
+    if (int r = st.upload()) return r;
+    h->rng_counter += uint64_t(T);
+    h->deal_valid = false;  // NPC counts change outside the dealt step: the deal restarts
+    HIP_TRY(mev::launch_rollout(h->sp, h->d_sp, rp, ra, h->internal, h->stream));
+    // the last outputs: row T - 1.  Device pointers: tracked where the caller's arrays hold them, as after
+    // mev_step.  Host pointers: the rows live in the staging block, so they are copied into the handle's buffers.
+    const size_t t1 = size_t(T - 1);
+    mev::Outputs last = h->internal;
+    auto keep = [&](auto** slot, auto* seq, size_t per) -> hipError_t {
+        if (!seq) return hipSuccess;
+        if (dev) {
+            *slot = seq + t1 * per;
+            return hipSuccess;
+        }
+        return hipMemcpyAsync(*slot, seq + t1 * per, per * sizeof(**slot), hipMemcpyDeviceToDevice, h->stream);
+    };
+    HIP_TRY(keep(&last.obs, ra.obs_seq, EN * D));
+    HIP_TRY(keep(&last.rew, ra.reward_seq, EN));
+    HIP_TRY(keep(&last.done, ra.done_seq, EN));
+    HIP_TRY(keep(&last.status, ra.status_seq, EN));
+    HIP_TRY(keep(&last.term, ra.term_seq, E));
+    HIP_TRY(keep(&last.trunc, ra.trunc_seq, E));
+    h->last = last;
+    return st.download();
 }
 
 // mev_evaluate_plans (include/marlenv.h): the plan rollout's loop over C candidates that start from

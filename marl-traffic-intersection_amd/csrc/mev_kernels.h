@@ -398,6 +398,38 @@ struct ServeArgs {
 hipError_t launch_serve(const SimParams& p, const SimParams* dp, const ServeArgs& sa, const Outputs& out,
                         hipStream_t s);
 
+// Closed-loop policy rollouts (mev_rollout_policy, k_rollout).  A policy's device block: layer l as
+// wt[l][k * ld[l] + j] = W[l][j][k] (transposed: lane j reads one coalesced line per k) followed by
+// the bias row wt[l][in[l] * ld[l] + j]; ld = out rounded up to 64, the padding zero.  The last
+// used layer has out = 2.
+struct PolicyNet {
+    const float* wt[3];
+    int32_t in[3], out[3], ld[3];
+    int32_t layers;  // 2 or 3
+};
+// repack a policy's [out][in] weights and [out] biases (device arrays) into dst (PolicyNet's layout)
+hipError_t launch_policy_repack(const PolicyNet& dst, const float* const* w, const float* const* b, hipStream_t s);
+// One launch of T sub-steps: per sub-step t the policy on the env's observation rows -- obs0 at t = 0,
+// then the rows sub-step t - 1 wrote -- then the fused step's body with the actions the policy wrote,
+// in.spawn_route ([T][E], nullable) and in.rng_counter advanced to row t.  Each *_seq array (nullable)
+// receives row t of its output; a null one leaves that output in `out` (the handle's own buffers,
+// rewritten every sub-step).  act_scratch [E][N][2] holds the action row when actions_seq is null.
+struct RolloutArgs {
+    StepInputs in;
+    PolicyNet net;
+    int32_t T, pol_off;
+    const float* obs0;  // [E][N][D]
+    float *obs_seq, *actions_seq, *mean_seq, *reward_seq;
+    uint8_t *done_seq, *status_seq, *term_seq, *trunc_seq;
+    float* act_scratch;
+    int32_t noisy;  // sigma given
+    float sigma[2], lo[2], hi[2];
+    uint32_t seed_lo, seed_hi, ctr_lo, ctr_hi;
+};
+// (rp: plan_rollout of p's shape, its row >= 0)
+hipError_t launch_rollout(const SimParams& p, const SimParams* dp, const RolloutPlan& rp, const RolloutArgs& ra,
+                          const Outputs& out, hipStream_t s);
+
 // masked per-env copy of snapshot fields (mev_restore)
 constexpr int kMaxRestoreFields = 48;
 struct RestoreTab {

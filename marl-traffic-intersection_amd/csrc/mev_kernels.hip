@@ -4195,6 +4195,242 @@ __global__ __launch_bounds__(SPLIT ? 2 * WAVE : WAVE, SPLIT ? kSplitWpe : 4) voi
     if (threadIdx.x == 0) __hip_atomic_store(&box->exited[blockIdx.x], sa.epoch, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
+// ------------------------------------------------- closed-loop policy rollouts ---
+// k_rollout (mev_rollout_policy): T sub-steps of one env per wave, each the handle's MLP policy on the
+// env's own observation rows and then k_step's body (mev_step_body.inc, as k_serve runs it) on the
+// actions the policy wrote.  One workgroup owns its env from the first load to the last store, so
+// nothing waits for another workgroup: the loop is bounded by T.
+//
+// The arithmetic is the header's (include/marlenv.h), the one place of the library with FMAs: a dense
+// layer is y = b[j], then y = fmaf(W[j][k], x[k], y) for k ascending -- explicit __builtin_fmaf, the
+// tree is built with -ffp-contract=off.
+//
+// A hidden layer of a group of <= 8 agents: lane j is unit j (widths above 64 take two passes) and keeps
+// the group's 8 chains; x[k] of the 8 agents is two 16-byte LDS broadcasts (the rows lie [k][8]),
+// W[k][j] one coalesced line per k of the transposed weights (PolicyNet).  The weight loads run one
+// batch of kPolicyAhead k ahead of the chains, in two register sets: left to the scheduler, each load
+// was waited for where it was issued, one L2 latency per k.  (A batch's loads past the layer's last
+// k re-read that k and are not used.)  Chains of agents the group does not have run on whatever the
+// LDS holds and are never stored.
+constexpr int kPolicyAhead = 16;
+__device__ __forceinline__ void policy_weights(float (&w)[kPolicyAhead], const __attribute__((address_space(1))) float* wt,
+                                               const int k0, const int in_w, const int ld, const uint32_t j) {
+#pragma unroll
+    for (int u = 0; u < kPolicyAhead; ++u) {
+        const int k = k0 + u < in_w ? k0 + u : in_w - 1;
+        w[u] = ldu(wt, (uint32_t)(k * ld) + j);
+    }
+}
+__device__ __forceinline__ void policy_hidden(const __attribute__((address_space(1))) float* wt, const int in_w,
+                                              const int out_w, const int ld, const float* x, float* y, const int lane) {
+    constexpr int U = kPolicyAhead;
+    for (int j0 = 0; j0 < out_w; j0 += WAVE) {
+        const uint32_t j = (uint32_t)(j0 + lane);  // (< ld: the rows are padded to whole waves)
+        float acc[kPolicyGroup];
+        float wc[U], wn[U];
+        const float b = ldu(wt, (uint32_t)(in_w * ld) + j);
+        policy_weights(wc, wt, 0, in_w, ld, j);
+#pragma unroll
+        for (int a = 0; a < kPolicyGroup; ++a) acc[a] = b;
+        for (int k0 = 0; k0 < in_w; k0 += U) {
+            const bool more = k0 + U < in_w;
+            if (more) policy_weights(wn, wt, k0 + U, in_w, ld, j);
+            __builtin_amdgcn_sched_barrier(0);
+            // (a whole batch without a test per k, so that its LDS reads can run ahead of the chains too)
+            auto chain = [&](const int u) {
+                const float w = wc[u];
+                const float4 x0 = *reinterpret_cast<const float4*>(x + (k0 + u) * kPolicyGroup);
+                const float4 x1 = *reinterpret_cast<const float4*>(x + (k0 + u) * kPolicyGroup + 4);
+                acc[0] = __builtin_fmaf(w, x0.x, acc[0]);
+                acc[1] = __builtin_fmaf(w, x0.y, acc[1]);
+                acc[2] = __builtin_fmaf(w, x0.z, acc[2]);
+                acc[3] = __builtin_fmaf(w, x0.w, acc[3]);
+                acc[4] = __builtin_fmaf(w, x1.x, acc[4]);
+                acc[5] = __builtin_fmaf(w, x1.y, acc[5]);
+                acc[6] = __builtin_fmaf(w, x1.z, acc[6]);
+                acc[7] = __builtin_fmaf(w, x1.w, acc[7]);
+            };
+            if (k0 + U <= in_w) {
+#pragma unroll
+                for (int u = 0; u < U; ++u) chain(u);
+            } else {
+#pragma unroll
+                for (int u = 0; u < U; ++u)
+                    if (k0 + u < in_w) chain(u);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            if (more) {
+#pragma unroll
+                for (int u = 0; u < U; ++u) wc[u] = wn[u];
+            }
+        }
+        if (j < (uint32_t)out_w) {
+            float4 r0, r1;  // relu: NaN and -0.0f give +0.0f
+            r0.x = acc[0] > 0.0f ? acc[0] : 0.0f; r0.y = acc[1] > 0.0f ? acc[1] : 0.0f;
+            r0.z = acc[2] > 0.0f ? acc[2] : 0.0f; r0.w = acc[3] > 0.0f ? acc[3] : 0.0f;
+            r1.x = acc[4] > 0.0f ? acc[4] : 0.0f; r1.y = acc[5] > 0.0f ? acc[5] : 0.0f;
+            r1.z = acc[6] > 0.0f ? acc[6] : 0.0f; r1.w = acc[7] > 0.0f ? acc[7] : 0.0f;
+            *reinterpret_cast<float4*>(y + j * kPolicyGroup) = r0;
+            *reinterpret_cast<float4*>(y + j * kPolicyGroup + 4) = r1;
+        }
+    }
+}
+
+// The policy of env e at sub-step t: for agents in groups of 8, the observation rows (obs, ld floats
+// apart; at most 31 + 128 columns: three per lane) staged in LDS -- every load of the group issued
+// before the first write -- the hidden layers, then the output layer as 2 lanes per agent -- lane 2 a + c
+// the serial chain of component c over the last hidden width, its weights loaded a batch ahead like the
+// hidden layers' -- the noise, the clamp, and the stores of mu (mean_row, nullable) and of the action
+// (act_row) at [e][i][c].
+__device__ __forceinline__ void policy_phase(const RolloutArgs& ra, const float* obs, const int ld, float* act_row,
+                                             float* mean_row, const int e, const int N, const int D, const int t,
+                                             float* scratch, const int lane) {
+    constexpr int U = kPolicyAhead;
+    constexpr int kCols = (kPolicyObsHead + kPolicyMaxWidth + WAVE - 1) / WAVE;  // columns per lane
+    const PolicyNet& net = ra.net;
+    const int L = net.layers;
+    float* xs = scratch;                                  // [D][8]
+    float* h1 = xs + (size_t)D * kPolicyGroup;            // [out[0]][8]
+    float* h2 = h1 + (size_t)net.out[0] * kPolicyGroup;   // [out[1]][8] (three layers)
+    for (int a0 = 0; a0 < N; a0 += kPolicyGroup) {
+        const int G = N - a0 < kPolicyGroup ? N - a0 : kPolicyGroup;
+        if (a0 > 0) wave_lds_sync();  // (the previous group's chains have read their rows)
+        float v[kCols][kPolicyGroup];
+#pragma unroll
+        for (int a = 0; a < kPolicyGroup; ++a) {
+            const int ar = a < G ? a : G - 1;  // (a row the group does not have: its last one again, never used)
+            const __attribute__((address_space(1))) float* row = gmem(obs + ((size_t)e * N + a0 + ar) * ld);
+#pragma unroll
+            for (int q = 0; q < kCols; ++q) {
+                const int c = lane + q * WAVE;
+                v[q][a] = ldu(row, (uint32_t)(c < D ? c : D - 1));
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int q = 0; q < kCols; ++q) {
+            const int c = lane + q * WAVE;
+            if (c < D) {
+                *reinterpret_cast<float4*>(xs + c * kPolicyGroup) = make_float4(v[q][0], v[q][1], v[q][2], v[q][3]);
+                *reinterpret_cast<float4*>(xs + c * kPolicyGroup + 4) = make_float4(v[q][4], v[q][5], v[q][6], v[q][7]);
+            }
+        }
+        wave_lds_sync();
+        policy_hidden(gmem(net.wt[0]), net.in[0], net.out[0], net.ld[0], xs, h1, lane);
+        wave_lds_sync();
+        const float* hl = h1;
+        if (L == 3) {
+            policy_hidden(gmem(net.wt[1]), net.in[1], net.out[1], net.ld[1], h1, h2, lane);
+            wave_lds_sync();
+            hl = h2;
+        }
+        const int a = lane >> 1, c = lane & 1;
+        const bool on = a < G;
+        const int al = on ? a : 0;
+        const __attribute__((address_space(1))) float* wl = gmem(net.wt[L - 1]);
+        const int in_w = net.in[L - 1], ldl = net.ld[L - 1];
+        float mu = ldu(wl, (uint32_t)(in_w * ldl + c));
+        float wc[U], wn[U];
+        policy_weights(wc, wl, 0, in_w, ldl, (uint32_t)c);
+        for (int k0 = 0; k0 < in_w; k0 += U) {
+            const bool more = k0 + U < in_w;
+            if (more) policy_weights(wn, wl, k0 + U, in_w, ldl, (uint32_t)c);
+            __builtin_amdgcn_sched_barrier(0);
+            float hv[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) hv[u] = hl[(k0 + u < in_w ? k0 + u : in_w - 1) * kPolicyGroup + al];
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+                if (k0 + u < in_w) mu = __builtin_fmaf(wc[u], hv[u], mu);
+            __builtin_amdgcn_sched_barrier(0);
+            if (more) {
+#pragma unroll
+                for (int u = 0; u < U; ++u) wc[u] = wn[u];
+            }
+        }
+        const int i = a0 + al;
+        float x = mu;
+        if (ra.noisy) {
+            uint32_t w[4];
+            philox4(ra.ctr_lo, ra.ctr_hi, (uint32_t)e * 64u + (uint32_t)i, (uint32_t)t, ra.seed_lo, ra.seed_hi, w);
+            const uint32_t w0 = c ? w[2] : w[0], w1 = c ? w[3] : w[1];
+            const uint32_t bs = __builtin_amdgcn_sad_u8(w1, 0u, __builtin_amdgcn_sad_u8(w0, 0u, 0u));
+            const float eps = ((float)bs - 1020.0f) * 0x1.39897ep-8f;
+            x = mu + ra.sigma[c] * eps;  // (multiply, then add: no FMA here)
+        }
+        const float act = fminf(fmaxf(x, ra.lo[c]), ra.hi[c]);
+        if (on) {
+            const uint32_t o = 2u * (uint32_t)(e * N + i) + (uint32_t)c;
+            if (mean_row) gmem(mean_row)[o] = mu;
+            gmem(act_row)[o] = act;
+        }
+    }
+}
+
+// P1 / NC: the beams and agents per env at compile time, as k_step's (the row's key, mev_plan.h)
+template <bool TRAFFIC, bool TAB, int NM, int KM, int RP1, int RNC>
+__global__ __launch_bounds__(WAVE, 4) void k_rollout(const SimParams* __restrict__ pp, RolloutArgs ra, Outputs out0) {
+    constexpr int PK = 1;
+    constexpr bool SPLIT = false, ESPLIT = false, WC = false;
+    constexpr int P1 = RP1, NC = RNC;
+    extern __shared__ __align__(16) unsigned char step_lds[];
+    const int lane = threadIdx.x & (WAVE - 1);
+    const int env = xcd_env((int)blockIdx.x, (int)gridDim.x);  // (the body's own e: in.deal == 0)
+    const int N = NC ? NC : pp->N;
+    const int D = pp->D;
+    const size_t E = (size_t)pp->E, EN = E * N;
+    float* scratch = reinterpret_cast<float*>(step_lds + ra.pol_off);
+    const float* obs = ra.obs0;
+    int obs_ld = D;
+    for (int t = 0; t < ra.T; ++t) {
+        // this sub-step's rows: the caller's arrays' row t, else the handle's buffers
+        Outputs out = out0;
+        if (ra.obs_seq) { out.obs = ra.obs_seq + (size_t)t * EN * D; out.obs_ld = D; }
+        if (ra.reward_seq) out.rew = ra.reward_seq + (size_t)t * EN;
+        if (ra.done_seq) out.done = ra.done_seq + (size_t)t * EN;
+        if (ra.status_seq) out.status = ra.status_seq + (size_t)t * EN;
+        if (ra.term_seq) out.term = ra.term_seq + (size_t)t * E;
+        if (ra.trunc_seq) out.trunc = ra.trunc_seq + (size_t)t * E;
+        float* act_row = ra.actions_seq ? ra.actions_seq + (size_t)t * EN * 2 : ra.act_scratch;
+        float* mean_row = ra.mean_seq ? ra.mean_seq + (size_t)t * EN * 2 : nullptr;
+        __builtin_amdgcn_s_setprio(kPrioCars);
+        policy_phase(ra, obs, obs_ld, act_row, mean_row, env, N, D, t, scratch, lane);
+        // the actions this wave wrote, read back by its own lanes in the body; the scratch is the body's again
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+        StepInputs in = ra.in;
+        in.actions = act_row;
+        in.spawn_route = ra.in.spawn_route ? ra.in.spawn_route + (size_t)t * E : nullptr;
+        in.rng_counter = ra.in.rng_counter + (uint64_t)t;
+        [&]() {  // one step: k_step's body (its returns end the lambda)
+#include "mev_step_body.inc"
+        }();
+        // the state and the rows this wave wrote, read back by its own lanes in the next sub-step
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+        obs = out.obs;
+        obs_ld = out.obs_ld;
+    }
+}
+
+// dst layer l: (in + 1) rows of ld floats, row k < in the weights W[j][k] over j, row `in` the biases
+__global__ __launch_bounds__(256) void k_policy_repack(PolicyNet net, const float* w0, const float* w1, const float* w2,
+                                                       const float* b0, const float* b1, const float* b2) {
+    const int l = blockIdx.y;
+    if (l >= net.layers) return;
+    const float* w = l == 0 ? w0 : l == 1 ? w1 : w2;
+    const float* b = l == 0 ? b0 : l == 1 ? b1 : b2;
+    const int in_w = net.in[l], out_w = net.out[l], ld = net.ld[l];
+    float* dst = const_cast<float*>(net.wt[l]);
+    const int n = (in_w + 1) * ld;
+    for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < n; idx += gridDim.x * blockDim.x) {
+        const int k = idx / ld, j = idx - k * ld;
+        dst[idx] = j >= out_w ? 0.0f : k < in_w ? w[(size_t)j * in_w + k] : b[j];
+    }
+}
+
 
 // ------------------------------------------------- reset / re-observe ---
 // IntersectionEnv::reset + add_car_with_route (cpp/IntersectionEnv.cpp:66-131)
@@ -4356,6 +4592,29 @@ hipError_t launch_step_window(const SimParams& p, const StepInputs& in, const Ou
     if (n < 1 || (rows && n > kMaxSeq)) return hipErrorInvalidValue;
     const Window w{n, substeps, rows};
     return launch_part(p, in, out, 0, p.E, s, nullptr, &w);
+}
+
+// k_rollout's instantiations in the order of MEV_ROLLOUT_KERNELS (mev_plan.h): kRolloutFns[row][!TAB]
+using RolloutFn = void (*)(const SimParams*, RolloutArgs, Outputs);
+#define MEV_ROLLOUT_FNS(T, NM, KM, P1, NC) {k_rollout<T, true, NM, KM, P1, NC>, k_rollout<T, false, NM, KM, P1, NC>},
+static const RolloutFn kRolloutFns[][2] = {MEV_ROLLOUT_KERNELS(MEV_ROLLOUT_FNS)};
+#undef MEV_ROLLOUT_FNS
+static_assert(sizeof kRolloutFns / sizeof kRolloutFns[0] == kRolloutRows, "one kernel pair per rollout row");
+
+hipError_t launch_rollout(const SimParams& p, const SimParams* dp, const RolloutPlan& rp, const RolloutArgs& ra,
+                          const Outputs& out, hipStream_t s) {
+    if (rp.row < 0 || rp.row >= kRolloutRows || ra.T < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(kRolloutFns[rp.row][!p.dist_tab], dim3(rp.grid), dim3(rp.block), rp.lds, s, dp, ra, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_policy_repack(const PolicyNet& dst, const float* const* w, const float* const* b, hipStream_t s) {
+    int n = 0;
+    for (int l = 0; l < dst.layers; ++l)
+        if ((dst.in[l] + 1) * dst.ld[l] > n) n = (dst.in[l] + 1) * dst.ld[l];
+    hipLaunchKernelGGL(k_policy_repack, dim3((unsigned)((n + 255) / 256), (unsigned)dst.layers), dim3(256), 0, s, dst,
+                       w[0], w[1], w[2], b[0], b[1], b[2]);
+    return hipGetLastError();
 }
 
 // the hand-off scratch of `chunk` candidates: each array at a 256-byte boundary

@@ -273,4 +273,48 @@ inline int step_row(const StepPlan& pl, bool plain_rows) {
 }
 inline int serve_row(const StepPlan& pl) { return pl.serve_fits ? serve_row(pl.serve.key) : -1; }
 
+// ---- mev_rollout_policy (k_rollout, mev_kernels.hip): the fused step in a loop with an MLP policy in
+// front of it, one wave per env.  The compiled rows: X(TRAFFIC, NM, KM, P1, NC), each for both TAB --
+// the three runtime layouts, which also run per-car sizes and written beam lists, and 8 agents x 64
+// beams without traffic with the counts at compile time.
+constexpr int kPolicyMaxWidth = 128;  // == MEV_POLICY_MAX_WIDTH
+constexpr int kPolicyGroup = 8;       // agents per policy pass (the LDS rows are [k][8])
+constexpr int kPolicyObsHead = 31;   // == OBS_HEAD (mev_world.h): the columns before the LiDAR block
+#define MEV_ROLLOUT_KERNELS(X) \
+    X(false, 0, MAXK, 0, 0)    \
+    X(true, 0, 32, 0, 0)       \
+    X(true, 0, 64, 0, 0)       \
+    X(false, 8, MAXK, 64, 8)
+constexpr int kRolloutRows = 4;
+constexpr int kRolloutRowFixed = 3;  // the compile-time row
+struct RolloutPlan {
+    int row;                    // in MEV_ROLLOUT_KERNELS' order; -1: the shape is not supported
+    unsigned grid, block, lds;  // one wave per env; the dynamic LDS, the policy's scratch included
+    int pol_off;                // where in the dynamic LDS the policy's scratch starts
+};
+// obs_dim: the handle's D (<= 31 + 128); hidden: the policy's hidden widths summed (the scratch holds 8
+// observation rows and 8 rows of each hidden layer).  The scratch lies in the step's LiDAR area, which
+// is dead between sub-steps, growing the launch's LDS where the area is smaller; where that would pass
+// a workgroup's 64 KB it lies at the start of the block instead (the car part's arrays are dead too).
+inline RolloutPlan plan_rollout(StepShape s, int obs_dim, int hidden = 2 * 64) {
+    RolloutPlan r{-1, 0, 0, 0, 0};
+    s.step_kernel = 2;
+    s.step_pack = s.step_split = 0;
+    if (plan_step(s).path != 2 || obs_dim < kPolicyObsHead || obs_dim > kPolicyObsHead + kPolicyMaxWidth) return r;
+    if (hidden < 1 || hidden > 2 * kPolicyMaxWidth) return r;
+    const bool fixed = !s.traffic && !s.dims && s.N == 8 && s.R == 64 && s.lidar_slots == 64;
+    const int npc_cap = s.K <= 32 ? 32 : 64;
+    r.row = s.traffic ? (npc_cap == 32 ? 1 : 2) : fixed ? kRolloutRowFixed : 0;
+    const unsigned dyn = fixed ? (unsigned)FixedLayout<8>::bytes : (unsigned)step_layout(s).bytes;
+    const unsigned lidar = fixed ? (unsigned)FixedLayout<8>::lidar : (unsigned)step_layout(s).lidar;
+    const unsigned stat = !s.traffic ? 0u : npc_cap == 32 ? (unsigned)sizeof(NpcLDST<32, true>) : (unsigned)sizeof(NpcLDST<64, true>);
+    const unsigned need = (unsigned)(kPolicyGroup * (obs_dim + hidden)) * 4u;
+    r.pol_off = (int)lds_al(lidar);
+    if (stat + r.pol_off + need > 64u * 1024u) r.pol_off = 0;
+    r.lds = dyn > r.pol_off + need ? dyn : r.pol_off + need;
+    r.grid = (unsigned)s.E;
+    r.block = WAVE;
+    return r;
+}
+
 }  // namespace mev

@@ -391,6 +391,82 @@ class VecIntersectionEnv:
             self._out_eval[(T, C, "actions")] = ao
         return dict(o, actions_out=ao)
 
+    @staticmethod
+    def _policy_arrays(module_or_arrays):
+        """(weights, biases) of an nn.Sequential(Linear, ReLU, Linear[, ReLU, Linear]) -- its parameters'
+        own tensors -- or of a (weights, biases) pair of array lists."""
+        m = module_or_arrays
+        if hasattr(m, "children"):
+            layers = list(m.children())
+            lin = layers[0::2]
+            ok = (len(layers) in (3, 5) and all(type(x).__name__ == "Linear" and x.bias is not None for x in lin)
+                  and all(type(x).__name__ == "ReLU" for x in layers[1::2]))
+            if not ok:
+                raise ValueError("a policy module is nn.Sequential(Linear, ReLU, Linear[, ReLU, Linear]) with biases")
+            return [x.weight for x in lin], [x.bias for x in lin]
+        weights, biases = m
+        return list(weights), list(biases)
+
+    def _policy_inputs(self, module_or_arrays):
+        weights, biases = self._policy_arrays(module_or_arrays)
+        if self.backend != "torch":
+            host = lambda x: x.detach().cpu().numpy() if hasattr(x, "detach") else x
+            return [host(w) for w in weights], [host(b) for b in biases], False
+        self._bind_stream()
+        t = self._torch
+        dev = lambda x: self._dev_tensor(x.detach() if hasattr(x, "detach") else x, t.float32)
+        return [dev(w) for w in weights], [dev(b) for b in biases], True
+
+    def make_policy(self, module_or_arrays):
+        """An MLP policy on the device (Handle.policy) from an nn.Sequential(Linear, ReLU, Linear[, ReLU,
+        Linear]) or a (weights, biases) pair of array lists ([out][in] and [out]; the last layer has 2
+        outputs: throttle, steer).  `policy.refresh(module_or_arrays)` pushes new weights of the same shape.
+        torch backend: the weights are read on the current stream by a small kernel, no host copy, no sync."""
+        w, b, device = self._policy_inputs(module_or_arrays)
+        pol = self._h.policy(w, b, device=device)
+
+        def refresh(source=module_or_arrays):
+            w, b, device = self._policy_inputs(source)
+            pol.update(w, b, device=device)
+
+        pol.refresh = refresh
+        return pol
+
+    def rollout(self, policy, T: int, dt: float = 1.0 / 60.0, sigma=None, lo=(-1.0, -1.0), hi=(1.0, 1.0), seed: int = 0,
+                counter: int = 0, spawn_route=None, outputs=_capi.ROLLOUT_OUTPUTS, copy: bool = False):
+        """T steps of observe -> policy -> step in one launch (Handle.rollout_policy), auto-reset as this env
+        was made: a dict of obs_seq [T, E, N, obs_dim] (the observation after each sub-step), actions_seq,
+        mean_seq [T, E, N, 2], reward_seq, done_seq, status_seq [T, E, N], terminated_seq, truncated_seq
+        [T, E] -- those named in `outputs`.  sigma: None, or two floats for Gaussian-like exploration noise
+        from the Philox stream (seed, counter): pass a new counter per call.  torch backend: device tensors
+        (kept per (T, outputs) and rewritten by the next call unless copy=True), stream-ordered, no host sync."""
+        T = int(T)
+        key = (T, tuple(outputs), "rollout")
+        o = self._out_eval.get(key)
+        if self.backend == "torch":
+            t = self._torch
+            self._bind_stream()
+            if o is None:
+                o = self._out_eval[key] = {}
+                E, N, D = self.num_envs, self.num_agents, self.obs_dim
+                for k, dtype, shape in _capi._ROLLOUT_OUTS:
+                    if k in outputs:
+                        o[k] = t.zeros(shape(T, E, N, D), dtype=t.float32 if dtype is np.float32 else t.uint8,
+                                       device=self._out["obs"].device)
+            sp = None
+            if spawn_route is not None:
+                sp = self._dev_tensor(spawn_route, t.int32)
+                if tuple(sp.shape) != (T, self.num_envs):
+                    raise ValueError(f"spawn_route must be [{T}][{self.num_envs}], got {tuple(sp.shape)}")
+            self._h.rollout_policy(policy, T, dt, sigma, lo, hi, seed, counter, self.auto_reset, sp, out=o, device=True)
+            return {k: v.clone() for k, v in o.items()} if copy else o
+        if o is None:
+            E, N, D = self.num_envs, self.num_agents, self.obs_dim
+            o = self._out_eval[key] = {k: np.zeros(shape(T, E, N, D), dtype) for k, dtype, shape in _capi._ROLLOUT_OUTS
+                                       if k in outputs}
+        self._h.rollout_policy(policy, T, dt, sigma, lo, hi, seed, counter, self.auto_reset, spawn_route, out=o)
+        return {k: v.copy() for k, v in o.items()} if copy else o
+
     def update_plans(self, actions, samples: int, scores=None, returns=None, mode: str = "elites", elites=None,
                      temperature: float = 1.0, sigma_min: float = 0.0):
         """Rank each group's candidates and refit the sampling distribution (Handle.update_plans):
