@@ -761,6 +761,90 @@ int mev_rollout_policy(mev_handle* h, const mev_rollout_args* args);
  * not supported. */
 int mev_get_rollout_row(const mev_handle* h, int32_t* row);
 
+/* Actor-critic rollouts: a value head on the policy's trunk, and the advantages on the device.
+ *
+ * value head of a policy: v = layer(wv, bv, h_last)[0], the same FMA chain as every other layer
+ * (y = bv[0]; for k ascending: y = fmaf(wv[k], h_last[k], y)); wv [H_last], bv [1], h_last the last hidden
+ * layer's activations after the ReLU.  wv == NULL detaches the head.  flags / validation / stream order
+ * exactly as mev_policy_update: host pointers are checked finite and the call is synchronous, device
+ * pointers are read by a small kernel on the handle's stream.  mev_policy_update leaves an attached head
+ * as it is; a new policy has none.
+ *
+ * mev_rollout_policy_values is mev_rollout_policy -- every output of `rollout`, the handle's state, last
+ * outputs, Philox counter and NPC diagnostics bit for bit the same for the same arguments -- that also
+ * writes value_seq [T+1][E][N]: row t = V(obs_t), obs_0 being the rows mev_get_outputs returns before the
+ * call and obs_{t+1} the observation after sub-step t.  The value is computed for every agent slot, alive
+ * or not, from the row as it stands, like the action.  Row t + 1 of an env that ended at t is the value of
+ * the TERMINAL observation (the next action is computed from that same row; with MEV_AUTO_RESET the reset
+ * happens inside sub-step t + 1).  Row T costs one more pass of the hidden layers after the last sub-step,
+ * with no step and no noise word.  With obs_seq NULL the rows are read from the handle's buffer in place.
+ * Every element of value_seq is written.  Host pointers are staged and the call is synchronous; device
+ * pointers do not synchronise.  Errors (MEV_E_INVALID, the handle untouched): a null value_seq, a policy
+ * without a value head, and everything mev_rollout_policy refuses. */
+int mev_policy_set_value_head(mev_policy* p, const float* wv, const float* bv, uint32_t flags);
+int mev_policy_has_value_head(const mev_policy* p, int32_t* has);
+
+typedef struct {
+    mev_rollout_args rollout;   /* exactly as mev_rollout_policy */
+    float* value_seq;           /* required, [T+1][E][N]: row t = V(obs_t); obs_0 = the rows mev_get_outputs
+                                   returns before the call, obs_{t+1} = the observation after sub-step t */
+} mev_rollout_values_args;
+int mev_rollout_policy_values(mev_handle* h, const mev_rollout_values_args* args);
+
+/* mev_gae: generalised advantage estimation over a rollout's arrays, one reverse scan on the device.
+ * THE ARITHMETIC IS THE CONTRACT: f32, multiply, then add, no FMA, per (e, i) and for t descending, with
+ * c the f32 product gamma * lambda, computed once:
+ *
+ *   stop  = done[t][e][i] | terminated[t][e]                       (absent arrays read as 0)
+ *   cut   = stop | truncated[t][e]
+ *   nv    = stop ? 0.0f : V[t+1]
+ *   delta = (r[t] + gamma * nv) - V[t]
+ *   adv   = cut ? delta : delta + c * adv_next                     (adv_next of t = T-1 is 0.0f)
+ *   masked (MEV_GAE_MASK_RESET_STEPS, and (t > 0 ? terminated[t-1][e] | truncated[t-1][e]
+ *                                                : ended_before ? ended_before[e] : 0)):
+ *           adv = 0.0f, valid = 0      (its predecessor is cut anyway, so nothing flows through it)
+ *   ret   = adv + V[t];  adv_next = adv
+ *
+ * Truncation bootstraps from V[t+1] -- the value of the terminal observation, which is what
+ * mev_rollout_policy_values writes there -- and cuts the trace; termination and an agent's own done (a
+ * per-agent end inside a running env, a respawn in the same step included) do neither.  The masked rows
+ * are this library's auto-reset steps: the env ended at t - 1, so the action of t was computed from the
+ * terminal observation and the step ran on the reset env; such a transition belongs to no episode, and
+ * `valid` tells a loss which rows to leave out.  ended_before says the same of row 0: the env's
+ * terminated | truncated of the step before the window.
+ * Like mev_update_plans the call reads and writes only its arguments; the handle supplies E, N, the device
+ * and the stream, and a resident step server is stopped first.  Host pointers are staged and the call is
+ * synchronous; device pointers do not synchronise.  Errors (MEV_E_INVALID): null rewards or values, no
+ * output pointer at all, length outside 1..MEV_MAX_ROLLOUT, a non-finite gamma or lambda, an unknown flag.
+ * Measured (python tools/bench_actor_critic.py -> profiles/actor_critic_sweep.json; tools/bench_rollout.py's
+ * method: device pointers, auto-reset, medians of five blocks (min-max)), 4096 envs x 8 agents x 64 beams, policy
+ * 95-64-64-2 with a value head: (a) mev_rollout_policy_values, T = 16, 0.890 ms (0.883-0.891) against (b)
+ * mev_rollout_policy on the same build 0.945 ms (0.944-0.945): the value instantiation is FASTER than the plain one, by
+ * 3.4 us per sub-step (T = 64: 3.404 against 3.688 ms) -- not because a third chain is free but because its kernel spills
+ * 132 VGPRs where the plain one spills 185 (the code object; why the allocator does better is supposed, not profiled) --
+ * where (c) an eager torch forward of trunk + head over the (T + 1) E N observation rows takes 0.357 ms (0.357-0.367;
+ * T = 64: 1.324 ms).  64 envs: (a) 0.537, (b) 0.553, (c) 0.164 ms.  (d) mev_gae takes 0.011 ms (0.011-0.011) at T = 16
+ * and 0.027 ms at T = 64 against (e) the eager torch GAE loop's 1.384 ms (1.379-1.393) and 5.344 ms: 128x and 197x; 64
+ * envs 0.007 against 1.257 ms.  All beyond the blocks' spreads.  mev_rollout_policy itself is unchanged: its kernels are a
+ * template instantiation of their own with the parent's register figures, 0.937 ms (0.936-0.937) on this build against
+ * 0.937 ms (0.937-0.938) on the commit before it, same session. */
+#define MEV_GAE_MASK_RESET_STEPS 0x100u
+typedef struct {
+    const float* reward_seq;        /* [T][E][N] */
+    const float* value_seq;         /* [T+1][E][N] */
+    const uint8_t* done_seq;        /* optional [T][E][N] */
+    const uint8_t* terminated_seq;  /* optional [T][E] */
+    const uint8_t* truncated_seq;   /* optional [T][E] */
+    const uint8_t* ended_before;    /* optional [E]: the env's last step BEFORE the window ended (MASK flag) */
+    int32_t length;                 /* T, 1..MEV_MAX_ROLLOUT */
+    float gamma, lambda;            /* finite */
+    float* advantages;              /* optional [T][E][N] */
+    float* returns;                 /* optional [T][E][N]: advantages + value_seq[t] */
+    uint8_t* valid;                 /* optional [T][E][N]: 0 for a masked transition, else 1 */
+    uint32_t flags;                 /* MEV_DEVICE_PTRS | MEV_GAE_MASK_RESET_STEPS */
+} mev_gae_args;
+int mev_gae(mev_handle* h, const mev_gae_args* args);
+
 /* Outputs of the last step / reset, from the handle's own device buffers.
  * Lifetime: after a step that wrote caller-owned output buffers (device
  * pointers in mev_step_args), this call, mev_device_outputs and

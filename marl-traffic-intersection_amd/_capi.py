@@ -53,7 +53,8 @@ EXPORTED = (
     "mev_evaluate_plans", "mev_evaluate_leaves", "mev_pool_create", "mev_pool_destroy", "mev_pool_slots",
     "mev_pool_capture", "mev_pool_get_state", "mev_expand_plans", "mev_sample_plans", "mev_update_plans",
     "mev_sample_expand_plans", "mev_get_step_row", "mev_policy_create", "mev_policy_update", "mev_policy_destroy",
-    "mev_rollout_policy", "mev_get_rollout_row",
+    "mev_rollout_policy", "mev_get_rollout_row", "mev_policy_set_value_head", "mev_policy_has_value_head",
+    "mev_rollout_policy_values", "mev_gae",
 )
 
 
@@ -157,6 +158,20 @@ class MevRolloutArgs(ctypes.Structure):  # mev_rollout_args
                 ("terminated_seq", _vp), ("truncated_seq", _vp), ("flags", ctypes.c_uint32)]
 
 
+class MevRolloutValuesArgs(ctypes.Structure):  # mev_rollout_values_args
+    _fields_ = [("rollout", MevRolloutArgs), ("value_seq", _vp)]
+
+
+MEV_GAE_MASK_RESET_STEPS = 0x100
+
+
+class MevGaeArgs(ctypes.Structure):  # mev_gae_args
+    _fields_ = [("reward_seq", _vp), ("value_seq", _vp), ("done_seq", _vp), ("terminated_seq", _vp),
+                ("truncated_seq", _vp), ("ended_before", _vp), ("length", ctypes.c_int32), ("gamma", ctypes.c_float),
+                ("lam", ctypes.c_float), ("advantages", _vp), ("returns", _vp), ("valid", _vp),
+                ("flags", ctypes.c_uint32)]
+
+
 # outputs of rollout_policy: (key, dtype, shape of (T, E, N, D))
 _ROLLOUT_OUTS = (("obs_seq", np.float32, lambda T, E, N, D: (T, E, N, D)),
                  ("actions_seq", np.float32, lambda T, E, N, D: (T, E, N, 2)),
@@ -167,6 +182,9 @@ _ROLLOUT_OUTS = (("obs_seq", np.float32, lambda T, E, N, D: (T, E, N, D)),
                  ("terminated_seq", np.uint8, lambda T, E, N, D: (T, E)),
                  ("truncated_seq", np.uint8, lambda T, E, N, D: (T, E)))
 ROLLOUT_OUTPUTS = tuple(k for k, _, _ in _ROLLOUT_OUTS)
+# ... and of mev_rollout_policy_values, which rollout_policy calls when value_seq is asked for
+_VALUE_OUT = ("value_seq", np.float32, lambda T, E, N, D: (T + 1, E, N))
+_GAE_OUTS = (("advantages", np.float32), ("returns", np.float32), ("valid", np.uint8))
 
 
 # outputs of evaluate_plans: (key, dtype, shape of (T, C, N))
@@ -279,6 +297,10 @@ def load_library(variant: str = None):
     L.mev_policy_destroy.argtypes = [_vp]
     L.mev_rollout_policy.argtypes = [_vp, ctypes.POINTER(MevRolloutArgs)]
     L.mev_get_rollout_row.argtypes = [_vp, i32p]
+    L.mev_policy_set_value_head.argtypes = [_vp, _vp, _vp, ctypes.c_uint32]
+    L.mev_policy_has_value_head.argtypes = [_vp, i32p]
+    L.mev_rollout_policy_values.argtypes = [_vp, ctypes.POINTER(MevRolloutValuesArgs)]
+    L.mev_gae.argtypes = [_vp, ctypes.POINTER(MevGaeArgs)]
     L.mev_set_serve.argtypes = [_vp, ctypes.c_int32]
     L.mev_serve_stats.argtypes = [_vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64), i32p]
     L.mev_configure.argtypes = [_vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]
@@ -876,9 +898,13 @@ class Handle:
         `outputs` (ROLLOUT_OUTPUTS: obs_seq [T][E][N][obs_dim], actions_seq / mean_seq [T][E][N][2],
         reward_seq / done_seq / status_seq [T][E][N], terminated_seq / truncated_seq [T][E]); `out` may
         hold preallocated ones.  device=True: device tensors, stream-ordered, no host sync -- the arrays
-        of `out`, or new torch tensors for `outputs`; spawn_route is then a device array too."""
+        of `out`, or new torch tensors for `outputs`; spawn_route is then a device array too.
+        With "value_seq" among the outputs (or in `out`) the call is mev_rollout_policy_values: the policy
+        needs a value head (Policy.set_value_head) and value_seq [T + 1][E][N] holds V(obs_t), row T the
+        bootstrap value; everything else is the same bits."""
         T, E, N, D = int(T), self.E, self.N, self.D
-        shapes = {k: (dtype, shape(T, E, N, D)) for k, dtype, shape in _ROLLOUT_OUTS}
+        shapes = {k: (dtype, shape(T, E, N, D)) for k, dtype, shape in _ROLLOUT_OUTS + (_VALUE_OUT,)}
+        values = "value_seq" in outputs if out is None or not out else "value_seq" in out
         out = dict(out) if out is not None else {}
         for k in out:
             if k not in shapes:
@@ -913,10 +939,71 @@ class Handle:
         a.lo = (ctypes.c_float * 2)(*[float(v) for v in lo])
         a.hi = (ctypes.c_float * 2)(*[float(v) for v in hi])
         a.noise_seed, a.noise_counter = int(seed) & (2**64 - 1), int(counter) & (2**64 - 1)
-        for k in shapes:
+        for k in ROLLOUT_OUTPUTS:
             setattr(a, k, _ptr(out.get(k)))
         a.flags = (MEV_DEVICE_PTRS if device else 0) | (MEV_AUTO_RESET if auto_reset else 0) | int(flags)
-        _check(self._lib.mev_rollout_policy(self._h, ctypes.byref(a)))
+        if values:
+            va = MevRolloutValuesArgs()
+            va.rollout, va.value_seq = a, _ptr(out.get("value_seq"))
+            _check(self._lib.mev_rollout_policy_values(self._h, ctypes.byref(va)))
+        else:
+            _check(self._lib.mev_rollout_policy(self._h, ctypes.byref(a)))
+        return out
+
+    def gae(self, reward_seq, value_seq, done_seq=None, terminated_seq=None, truncated_seq=None, ended_before=None,
+            gamma: float = 0.99, lam: float = 0.95, mask_reset_steps: bool = False,
+            outputs=("advantages", "returns"), out: Optional[dict] = None, device: bool = False, flags: int = 0):
+        """Generalised advantage estimation (mev_gae) over a rollout's arrays: reward_seq [T][E][N], value_seq
+        [T + 1][E][N], optional done_seq [T][E][N], terminated_seq / truncated_seq [T][E], ended_before [E].
+        An agent's done or the env's termination stops the bootstrap and the trace, a truncation bootstraps
+        and cuts the trace; mask_reset_steps zeroes the transitions that follow an env's end (the auto-reset
+        steps) and clears their `valid`.  Returns the arrays named in `outputs` ("advantages", "returns",
+        "valid", each [T][E][N]); `out` may hold preallocated ones.  device=True: device tensors,
+        stream-ordered, no host sync."""
+        E, N = self.E, self.N
+        names = {k: dtype for k, dtype in _GAE_OUTS}
+        out = dict(out) if out is not None else {}
+        for k in list(out) + (list(outputs) if not out else []):
+            if k not in names:
+                raise ValueError(f"unknown gae output {k!r}")
+        ins = dict(reward_seq=reward_seq, value_seq=value_seq, done_seq=done_seq, terminated_seq=terminated_seq,
+                   truncated_seq=truncated_seq, ended_before=ended_before)
+        if device:
+            T = int(reward_seq.shape[0])
+            if not out:
+                import torch
+                for k in outputs:
+                    out[k] = torch.empty((T, E, N), dtype=torch.float32 if names[k] is np.float32 else torch.uint8,
+                                         device=f"cuda:{self.config['device']}")
+        else:
+            reward_seq = np.asarray(reward_seq)
+            T = int(reward_seq.shape[0]) if reward_seq.ndim == 3 else 0
+            want = dict(reward_seq=((T, E, N), np.float32), value_seq=((T + 1, E, N), np.float32),
+                        done_seq=((T, E, N), np.uint8), terminated_seq=((T, E), np.uint8),
+                        truncated_seq=((T, E), np.uint8), ended_before=((E,), np.uint8))
+            for k, (shape, dtype) in want.items():
+                if ins[k] is None:
+                    continue
+                v = np.asarray(ins[k])
+                if v.dtype == np.bool_:
+                    v = v.astype(np.uint8)
+                ins[k] = np.ascontiguousarray(v, dtype)
+                if ins[k].shape != shape:
+                    raise ValueError(f"{k} must be {list(shape)}, got {ins[k].shape}")
+            if not out:
+                for k in outputs:
+                    out[k] = np.zeros((T, E, N), names[k])
+            for k, v in out.items():
+                if v is not None and (v.shape != (T, E, N) or v.dtype != names[k]):
+                    raise ValueError(f"{k} must be {np.dtype(names[k]).name} {[T, E, N]}, got {v.shape}")
+        ga = MevGaeArgs()
+        for k, v in ins.items():
+            setattr(ga, k, _ptr(v))
+        ga.length, ga.gamma, ga.lam = T, float(gamma), float(lam)
+        for k in names:
+            setattr(ga, k, _ptr(out.get(k)))
+        ga.flags = (MEV_DEVICE_PTRS if device else 0) | (MEV_GAE_MASK_RESET_STEPS if mask_reset_steps else 0) | int(flags)
+        _check(self._lib.mev_gae(self._h, ctypes.byref(ga)))
         return out
 
     def update_plans(self, actions, samples: int, scores=None, returns=None, mode: str = "elites",
@@ -1362,6 +1449,33 @@ class Policy:
         """New weights of the same shape (mev_policy_update); device=True: stream-ordered, no host copy."""
         spec, _keep = self._spec(weights, biases, device)
         _check(self._handle._lib.mev_policy_update(self._p, ctypes.byref(spec), MEV_DEVICE_PTRS if device else 0))
+
+    def set_value_head(self, w, b, device: bool = False):
+        """Attach a value head on the last hidden layer (mev_policy_set_value_head): w [H_last] (or [1][H_last],
+        nn.Linear(H_last, 1).weight), b [1]; w None detaches it.  device=True: stream-ordered, no host copy.
+        `update` leaves an attached head as it is."""
+        if w is not None:
+            H = self.shapes[-1][1]
+            if not device:
+                w = np.ascontiguousarray(w, np.float32).reshape(-1)
+                b = np.ascontiguousarray(b, np.float32).reshape(-1)
+            n = 1
+            for x in w.shape:
+                n *= int(x)
+            nb = 1
+            for x in b.shape:
+                nb *= int(x)
+            if n != H or nb != 1:
+                raise ValueError(f"a value head has {H} weights and 1 bias, got {tuple(w.shape)} and {tuple(b.shape)}")
+        _check(self._handle._lib.mev_policy_set_value_head(self._p, _ptr(w) if w is not None else None,
+                                                           _ptr(b) if w is not None else None,
+                                                           MEV_DEVICE_PTRS if device else 0))
+
+    @property
+    def has_value_head(self) -> bool:
+        has = ctypes.c_int32()
+        _check(self._handle._lib.mev_policy_has_value_head(self._p, ctypes.byref(has)))
+        return bool(has.value)
 
     def close(self):
         if self._ptr is not None and self._handle._h:

@@ -62,6 +62,7 @@ struct mev_policy {
     mev_handle* h = nullptr;
     float* block = nullptr;
     mev::PolicyNet net{};
+    bool has_value = false;  // a value head is attached (mev_policy_set_value_head): column 2 of the last layer's block
 };
 
 struct mev_handle {
@@ -1705,9 +1706,41 @@ static int policy_load(mev_policy* p, const mev_policy_spec* spec, uint32_t flag
         st.in(&b[l], spec->b[l], size_t(net.out[l]));
     }
     if (int r = st.upload()) return r;
-    HIP_TRY(mev::launch_policy_repack(net, w, b, h->stream));
+    HIP_TRY(mev::launch_policy_repack(net, w, b, p->has_value, h->stream));
     p->net = net;
     return st.download();
+}
+
+// mev_policy_set_value_head: the head's column of the last layer's block, staged and written on the stream
+// as policy_load does the layers (which leave that column alone while a head is attached)
+int mev_policy_set_value_head(mev_policy* p, const float* wv, const float* bv, uint32_t flags) {
+    if (!p) return fail(MEV_E_INVALID, "null argument");
+    mev_handle* h = p->h;
+    if (flags & ~MEV_DEVICE_PTRS) return fail(MEV_E_INVALID, "policy flags: MEV_DEVICE_PTRS or 0");
+    if (wv && !bv) return fail(MEV_E_INVALID, "value head: null bias");
+    const bool dev = (flags & MEV_DEVICE_PTRS) != 0;
+    const size_t n = size_t(p->net.in[p->net.layers - 1]);
+    if (wv && !dev) {
+        for (size_t i = 0; i < n; ++i)
+            if (!std::isfinite(wv[i])) return fail(MEV_E_INVALID, "value head: a weight is not finite");
+        if (!std::isfinite(bv[0])) return fail(MEV_E_INVALID, "value head: the bias is not finite");
+    }
+    HIP_TRY(hipSetDevice(h->cfg.device));
+    if (int r = serve_stop(h)) return r;  // (the server holds the stream)
+    const float *dw = nullptr, *db = nullptr;
+    Stage st(h, dev);
+    st.in(&dw, wv, n);
+    st.in(&db, wv ? bv : nullptr, 1);
+    if (int r = st.upload()) return r;
+    HIP_TRY(mev::launch_value_head_repack(p->net, dw, db, h->stream));
+    p->has_value = wv != nullptr;
+    return st.download();
+}
+
+int mev_policy_has_value_head(const mev_policy* p, int32_t* has) {
+    if (!p || !has) return fail(MEV_E_INVALID, "null argument");
+    *has = p->has_value ? 1 : 0;
+    return MEV_OK;
 }
 
 int mev_policy_create(mev_handle* h, const mev_policy_spec* spec, uint32_t flags, mev_policy** out) {
@@ -1756,9 +1789,9 @@ int mev_get_rollout_row(const mev_handle* h, int32_t* row) {
     return MEV_OK;
 }
 
-// mev_rollout_policy: T sub-steps of policy + fused step in one launch (k_rollout), along step_window's path
-int mev_rollout_policy(mev_handle* h, const mev_rollout_args* a) {
-    if (!h || !a) return fail(MEV_E_INVALID, "null argument");
+// mev_rollout_policy: T sub-steps of policy + fused step in one launch (k_rollout), along step_window's path.
+// value_seq (mev_rollout_policy_values, checked there): non-null runs k_rollout's value instantiation.
+static int rollout(mev_handle* h, const mev_rollout_args* a, float* value_seq) {
     const mev_policy* pol = a->policy;
     if (!pol) return fail(MEV_E_INVALID, "mev_rollout_policy: policy required");
     if (pol->h != h) return fail(MEV_E_INVALID, "mev_rollout_policy: the policy belongs to another handle");
@@ -1820,6 +1853,7 @@ int mev_rollout_policy(mev_handle* h, const mev_rollout_args* a) {
     st.out(&ra.status_seq, a->status_seq, size_t(T) * EN);
     st.out(&ra.term_seq, a->terminated_seq, size_t(T) * E);
     st.out(&ra.trunc_seq, a->truncated_seq, size_t(T) * E);
+    st.out(&ra.value_seq, value_seq, size_t(T + 1) * EN);
     if (int r = st.upload()) return r;
     h->rng_counter += uint64_t(T);
     h->deal_valid = false;  // NPC counts change outside the dealt step: the deal restarts
@@ -1843,6 +1877,54 @@ int mev_rollout_policy(mev_handle* h, const mev_rollout_args* a) {
     HIP_TRY(keep(&last.term, ra.term_seq, E));
     HIP_TRY(keep(&last.trunc, ra.trunc_seq, E));
     h->last = last;
+    return st.download();
+}
+
+int mev_rollout_policy(mev_handle* h, const mev_rollout_args* a) {
+    if (!h || !a) return fail(MEV_E_INVALID, "null argument");
+    return rollout(h, a, nullptr);
+}
+
+int mev_rollout_policy_values(mev_handle* h, const mev_rollout_values_args* va) {
+    if (!h || !va) return fail(MEV_E_INVALID, "null argument");
+    if (!va->value_seq) return fail(MEV_E_INVALID, "mev_rollout_policy_values: value_seq required");
+    if (va->rollout.policy && !va->rollout.policy->has_value)
+        return fail(MEV_E_INVALID, "mev_rollout_policy_values: the policy has no value head (mev_policy_set_value_head)");
+    return rollout(h, &va->rollout, va->value_seq);
+}
+
+// mev_gae (include/marlenv.h): k_gae's reverse scan.  Reads and writes its arguments only; host pointers go
+// through the handle's staging block.
+int mev_gae(mev_handle* h, const mev_gae_args* ga) {
+    if (!h || !ga) return fail(MEV_E_INVALID, "null argument");
+    if (!ga->reward_seq || !ga->value_seq) return fail(MEV_E_INVALID, "mev_gae: reward_seq and value_seq required");
+    if (!ga->advantages && !ga->returns && !ga->valid) return fail(MEV_E_INVALID, "mev_gae needs at least one output");
+    if (ga->length < 1 || ga->length > MEV_MAX_ROLLOUT)
+        return fail(MEV_E_INVALID, "length must be in 1.." + std::to_string(MEV_MAX_ROLLOUT));
+    if (!std::isfinite(ga->gamma) || !std::isfinite(ga->lambda)) return fail(MEV_E_INVALID, "mev_gae: gamma and lambda must be finite");
+    if (ga->flags & ~uint32_t(MEV_DEVICE_PTRS | MEV_GAE_MASK_RESET_STEPS)) return fail(MEV_E_INVALID, "mev_gae: unknown flag");
+    const bool dev = (ga->flags & MEV_DEVICE_PTRS) != 0;
+    const size_t T = size_t(ga->length), E = size_t(h->cfg.num_envs), EN = E * size_t(h->cfg.num_agents);
+    HIP_TRY(hipSetDevice(h->cfg.device));
+    if (int r = serve_stop(h)) return r;  // (the server holds the stream)
+    mev::GaeArgs g{};
+    g.T = ga->length; g.E = h->cfg.num_envs; g.N = h->cfg.num_agents;
+    g.mask = (ga->flags & MEV_GAE_MASK_RESET_STEPS) ? 1 : 0;
+    g.gamma = ga->gamma;
+    const float c = ga->gamma * ga->lambda;  // (one f32 product)
+    g.c = c;
+    Stage st(h, dev);
+    st.in(&g.reward, ga->reward_seq, T * EN);
+    st.in(&g.value, ga->value_seq, (T + 1) * EN);
+    st.in(&g.done, ga->done_seq, T * EN);
+    st.in(&g.term, ga->terminated_seq, T * E);
+    st.in(&g.trunc, ga->truncated_seq, T * E);
+    st.in(&g.ended_before, g.mask ? ga->ended_before : nullptr, E);
+    st.out(&g.adv, ga->advantages, T * EN);
+    st.out(&g.ret, ga->returns, T * EN);
+    st.out(&g.valid, ga->valid, T * EN);
+    if (int r = st.upload()) return r;
+    HIP_TRY(mev::launch_gae(g, h->stream));
     return st.download();
 }
 

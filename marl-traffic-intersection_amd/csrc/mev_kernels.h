@@ -401,14 +401,19 @@ hipError_t launch_serve(const SimParams& p, const SimParams* dp, const ServeArgs
 // Closed-loop policy rollouts (mev_rollout_policy, k_rollout).  A policy's device block: layer l as
 // wt[l][k * ld[l] + j] = W[l][j][k] (transposed: lane j reads one coalesced line per k) followed by
 // the bias row wt[l][in[l] * ld[l] + j]; ld = out rounded up to 64, the padding zero.  The last
-// used layer has out = 2.
+// used layer has out = 2; column 2 of its block holds the value head (mev_policy_set_value_head: wv[k] in
+// row k, bv[0] in the bias row), zero while none is attached.
 struct PolicyNet {
     const float* wt[3];
     int32_t in[3], out[3], ld[3];
     int32_t layers;  // 2 or 3
 };
 // repack a policy's [out][in] weights and [out] biases (device arrays) into dst (PolicyNet's layout)
-hipError_t launch_policy_repack(const PolicyNet& dst, const float* const* w, const float* const* b, hipStream_t s);
+// keep_head: the value head's column is left as it stands
+hipError_t launch_policy_repack(const PolicyNet& dst, const float* const* w, const float* const* b, bool keep_head,
+                                hipStream_t s);
+// the value head's column from wv [in of the last layer] and bv [1] (device arrays); wv null: zeros
+hipError_t launch_value_head_repack(const PolicyNet& dst, const float* wv, const float* bv, hipStream_t s);
 // One launch of T sub-steps: per sub-step t the policy on the env's observation rows -- obs0 at t = 0,
 // then the rows sub-step t - 1 wrote -- then the fused step's body with the actions the policy wrote,
 // in.spawn_route ([T][E], nullable) and in.rng_counter advanced to row t.  Each *_seq array (nullable)
@@ -425,10 +430,29 @@ struct RolloutArgs {
     int32_t noisy;  // sigma given
     float sigma[2], lo[2], hi[2];
     uint32_t seed_lo, seed_hi, ctr_lo, ctr_hi;
+    // non-null: the value instantiation (mev_rollout_policy_values).  [T + 1][E][N]: row t = the value head on the
+    // rows the policy of sub-step t reads, row T on the rows the last sub-step wrote.
+    float* value_seq;
 };
 // (rp: plan_rollout of p's shape, its row >= 0)
 hipError_t launch_rollout(const SimParams& p, const SimParams* dp, const RolloutPlan& rp, const RolloutArgs& ra,
                           const Outputs& out, hipStream_t s);
+
+// mev_gae (k_gae): the reverse scan of mev_gae.h's gae_step over T rows per (e, i).  c = gamma * lambda in f32.
+struct GaeArgs {
+    const float* reward;          // [T][E][N]
+    const float* value;           // [T + 1][E][N]
+    const uint8_t* done;          // [T][E][N] (nullable)
+    const uint8_t* term;          // [T][E] (nullable)
+    const uint8_t* trunc;         // [T][E] (nullable)
+    const uint8_t* ended_before;  // [E] (nullable), read with mask
+    int32_t T, E, N, mask;
+    float gamma, c;
+    float* adv;      // [T][E][N] (nullable)
+    float* ret;      // [T][E][N] (nullable)
+    uint8_t* valid;  // [T][E][N] (nullable)
+};
+hipError_t launch_gae(const GaeArgs& a, hipStream_t s);
 
 // masked per-env copy of snapshot fields (mev_restore)
 constexpr int kMaxRestoreFields = 48;

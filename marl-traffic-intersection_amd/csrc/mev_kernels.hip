@@ -20,6 +20,7 @@
 #include "mev_world.h"
 #include "mev_nsort.h"
 #include "mev_roadbound.h"
+#include "mev_gae.h"
 
 namespace mev {
 
@@ -4282,9 +4283,15 @@ __device__ __forceinline__ void policy_hidden(const __attribute__((address_space
 // the serial chain of component c over the last hidden width, its weights loaded a batch ahead like the
 // hidden layers' -- the noise, the clamp, and the stores of mu (mean_row, nullable) and of the action
 // (act_row) at [e][i][c].
+// VALUE (mev_rollout_policy_values): the output layer is 4 lanes per agent -- lane 4 a + c, c < 2 the chains
+// above with the same operands in the same order, c == 2 the value head's chain over column 2 of the last
+// layer's block (k_value_head_repack), stored to value_row at [e][i]; the fourth lane repeats column 2 and
+// stores nothing.  With step == false (the bootstrap row T: no sub-step follows) no noise word is drawn
+// and only the value is stored.
+template <bool VALUE>
 __device__ __forceinline__ void policy_phase(const RolloutArgs& ra, const float* obs, const int ld, float* act_row,
-                                             float* mean_row, const int e, const int N, const int D, const int t,
-                                             float* scratch, const int lane) {
+                                             float* mean_row, float* value_row, const bool step, const int e,
+                                             const int N, const int D, const int t, float* scratch, const int lane) {
     constexpr int U = kPolicyAhead;
     constexpr int kCols = (kPolicyObsHead + kPolicyMaxWidth + WAVE - 1) / WAVE;  // columns per lane
     const PolicyNet& net = ra.net;
@@ -4324,7 +4331,8 @@ __device__ __forceinline__ void policy_phase(const RolloutArgs& ra, const float*
             wave_lds_sync();
             hl = h2;
         }
-        const int a = lane >> 1, c = lane & 1;
+        const int a = VALUE ? lane >> 2 : lane >> 1, c = VALUE ? (lane & 3) < 2 ? lane & 3 : 2 : lane & 1;
+        const int ck = c & 1;  // (the component whose sigma and bounds a lane reads: the value lanes use none of it)
         const bool on = a < G;
         const int al = on ? a : 0;
         const __attribute__((address_space(1))) float* wl = gmem(net.wt[L - 1]);
@@ -4350,25 +4358,30 @@ __device__ __forceinline__ void policy_phase(const RolloutArgs& ra, const float*
         }
         const int i = a0 + al;
         float x = mu;
-        if (ra.noisy) {
+        if (ra.noisy && (!VALUE || step)) {
             uint32_t w[4];
             philox4(ra.ctr_lo, ra.ctr_hi, (uint32_t)e * 64u + (uint32_t)i, (uint32_t)t, ra.seed_lo, ra.seed_hi, w);
-            const uint32_t w0 = c ? w[2] : w[0], w1 = c ? w[3] : w[1];
+            const uint32_t w0 = ck ? w[2] : w[0], w1 = ck ? w[3] : w[1];
             const uint32_t bs = __builtin_amdgcn_sad_u8(w1, 0u, __builtin_amdgcn_sad_u8(w0, 0u, 0u));
             const float eps = ((float)bs - 1020.0f) * 0x1.39897ep-8f;
-            x = mu + ra.sigma[c] * eps;  // (multiply, then add: no FMA here)
+            x = mu + ra.sigma[ck] * eps;  // (multiply, then add: no FMA here)
         }
-        const float act = fminf(fmaxf(x, ra.lo[c]), ra.hi[c]);
-        if (on) {
+        const float act = fminf(fmaxf(x, ra.lo[ck]), ra.hi[ck]);
+        if (on && (!VALUE || (step && (lane & 3) < 2))) {
             const uint32_t o = 2u * (uint32_t)(e * N + i) + (uint32_t)c;
             if (mean_row) gmem(mean_row)[o] = mu;
             gmem(act_row)[o] = act;
         }
+        if constexpr (VALUE)
+            if (on && (lane & 3) == 2) gmem(value_row)[(uint32_t)(e * N + i)] = mu;
     }
 }
 
 // P1 / NC: the beams and agents per env at compile time, as k_step's (the row's key, mev_plan.h)
-template <bool TRAFFIC, bool TAB, int NM, int KM, int RP1, int RNC>
+// VALUE: mev_rollout_policy_values -- row t of value_seq from the policy phase of sub-step t, and after the
+// last sub-step one more policy phase on the rows it wrote (hidden layers and the value chain, no step) for
+// row T.  A flag of the instantiation, not of the launch: mev_rollout_policy runs the code it ran before.
+template <bool TRAFFIC, bool TAB, int NM, int KM, int RP1, int RNC, bool VALUE>
 __global__ __launch_bounds__(WAVE, 4) void k_rollout(const SimParams* __restrict__ pp, RolloutArgs ra, Outputs out0) {
     constexpr int PK = 1;
     constexpr bool SPLIT = false, ESPLIT = false, WC = false;
@@ -4382,7 +4395,8 @@ __global__ __launch_bounds__(WAVE, 4) void k_rollout(const SimParams* __restrict
     float* scratch = reinterpret_cast<float*>(step_lds + ra.pol_off);
     const float* obs = ra.obs0;
     int obs_ld = D;
-    for (int t = 0; t < ra.T; ++t) {
+    const int rows = VALUE ? ra.T + 1 : ra.T;
+    for (int t = 0; t < rows; ++t) {
         // this sub-step's rows: the caller's arrays' row t, else the handle's buffers
         Outputs out = out0;
         if (ra.obs_seq) { out.obs = ra.obs_seq + (size_t)t * EN * D; out.obs_ld = D; }
@@ -4394,7 +4408,9 @@ __global__ __launch_bounds__(WAVE, 4) void k_rollout(const SimParams* __restrict
         float* act_row = ra.actions_seq ? ra.actions_seq + (size_t)t * EN * 2 : ra.act_scratch;
         float* mean_row = ra.mean_seq ? ra.mean_seq + (size_t)t * EN * 2 : nullptr;
         __builtin_amdgcn_s_setprio(kPrioCars);
-        policy_phase(ra, obs, obs_ld, act_row, mean_row, env, N, D, t, scratch, lane);
+        policy_phase<VALUE>(ra, obs, obs_ld, act_row, mean_row, VALUE ? ra.value_seq + (size_t)t * EN : nullptr,
+                            !VALUE || t < ra.T, env, N, D, t, scratch, lane);
+        if (VALUE && t == ra.T) break;  // (the bootstrap row: no sub-step follows)
         // the actions this wave wrote, read back by its own lanes in the body; the scratch is the body's again
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
         __builtin_amdgcn_wave_barrier();
@@ -4416,8 +4432,10 @@ __global__ __launch_bounds__(WAVE, 4) void k_rollout(const SimParams* __restrict
 }
 
 // dst layer l: (in + 1) rows of ld floats, row k < in the weights W[j][k] over j, row `in` the biases
+// (keep_head: column out of the last layer, where an attached value head lives, is left as it is)
 __global__ __launch_bounds__(256) void k_policy_repack(PolicyNet net, const float* w0, const float* w1, const float* w2,
-                                                       const float* b0, const float* b1, const float* b2) {
+                                                       const float* b0, const float* b1, const float* b2,
+                                                       const int keep_head) {
     const int l = blockIdx.y;
     if (l >= net.layers) return;
     const float* w = l == 0 ? w0 : l == 1 ? w1 : w2;
@@ -4427,7 +4445,82 @@ __global__ __launch_bounds__(256) void k_policy_repack(PolicyNet net, const floa
     const int n = (in_w + 1) * ld;
     for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < n; idx += gridDim.x * blockDim.x) {
         const int k = idx / ld, j = idx - k * ld;
+        if (keep_head && l == net.layers - 1 && j == out_w) continue;  // (an attached value head's column)
         dst[idx] = j >= out_w ? 0.0f : k < in_w ? w[(size_t)j * in_w + k] : b[j];
+    }
+}
+
+// The value head (mev_policy_set_value_head): column 2 of the last layer's block -- wv[k] in row k, bv[0] in
+// the bias row -- or zeros (wv null: detached), as k_policy_repack leaves the padding.
+__global__ __launch_bounds__(256) void k_value_head_repack(PolicyNet net, const float* wv, const float* bv) {
+    const int l = net.layers - 1;
+    const int in_w = net.in[l], ld = net.ld[l];
+    float* dst = const_cast<float*>(net.wt[l]);
+    for (int k = blockIdx.x * blockDim.x + threadIdx.x; k <= in_w; k += gridDim.x * blockDim.x)
+        dst[(size_t)k * ld + net.out[l]] = !wv ? 0.0f : k < in_w ? wv[k] : bv[0];
+}
+
+// mev_gae: one lane per (e, i), the T rows in descending order through gae_step (mev_gae.h).  A row's
+// loads do not depend on the chain, so they run one batch of kGaeAhead rows ahead of it in two register
+// sets, as policy_weights does; each row's loads and stores are coalesced over g = e N + i.  (A batch's
+// rows below 0 re-read row 0 and are not used.)
+constexpr int kGaeAhead = 8;
+struct GaeBatch {
+    float r[kGaeAhead], v[kGaeAhead];
+    uint8_t done[kGaeAhead], term[kGaeAhead], trunc[kGaeAhead], pterm[kGaeAhead], ptrunc[kGaeAhead];
+};
+__device__ __forceinline__ void gae_load(GaeBatch& b, const GaeArgs& a, const int t0, const size_t EN, const size_t g,
+                                         const size_t e) {
+#pragma unroll
+    for (int u = 0; u < kGaeAhead; ++u) {
+        const size_t t = (size_t)(t0 - u > 0 ? t0 - u : 0);
+        b.r[u] = a.reward[t * EN + g];
+        b.v[u] = a.value[t * EN + g];
+        b.done[u] = a.done ? a.done[t * EN + g] : (uint8_t)0;
+        b.term[u] = a.term ? a.term[t * (size_t)a.E + e] : (uint8_t)0;
+        b.trunc[u] = a.trunc ? a.trunc[t * (size_t)a.E + e] : (uint8_t)0;
+        b.pterm[u] = 0;
+        b.ptrunc[u] = 0;
+        if (a.mask) {  // the row before: the env's end that makes row t a reset step
+            if (t > 0) {
+                b.pterm[u] = a.term ? a.term[(t - 1) * (size_t)a.E + e] : (uint8_t)0;
+                b.ptrunc[u] = a.trunc ? a.trunc[(t - 1) * (size_t)a.E + e] : (uint8_t)0;
+            } else {
+                b.pterm[u] = a.ended_before ? a.ended_before[e] : (uint8_t)0;
+            }
+        }
+    }
+}
+__global__ __launch_bounds__(WAVE) void k_gae(GaeArgs a) {
+    constexpr int U = kGaeAhead;
+    const size_t EN = (size_t)a.E * (size_t)a.N;
+    const size_t g = (size_t)blockIdx.x * WAVE + threadIdx.x;
+    if (g >= EN) return;
+    const size_t e = g / (size_t)a.N;
+    float v_next = a.value[(size_t)a.T * EN + g];
+    float adv_next = 0.0f;
+    GaeBatch cur, nxt;
+    gae_load(cur, a, a.T - 1, EN, g, e);
+    for (int t0 = a.T - 1; t0 >= 0; t0 -= U) {
+        const bool more = t0 - U >= 0;
+        if (more) gae_load(nxt, a, t0 - U, EN, g, e);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int t = t0 - u;
+            if (t >= 0) {
+                const GaeRow o = gae_step(cur.r[u], cur.v[u], v_next, cur.done[u], cur.term[u], cur.trunc[u],
+                                          (cur.pterm[u] | cur.ptrunc[u]) != 0, a.gamma, a.c, adv_next);
+                const size_t at = (size_t)t * EN + g;
+                if (a.adv) a.adv[at] = o.adv;
+                if (a.ret) a.ret[at] = o.ret;
+                if (a.valid) a.valid[at] = o.valid;
+                adv_next = o.adv;
+                v_next = cur.v[u];
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        if (more) cur = nxt;
     }
 }
 
@@ -4594,26 +4687,43 @@ hipError_t launch_step_window(const SimParams& p, const StepInputs& in, const Ou
     return launch_part(p, in, out, 0, p.E, s, nullptr, &w);
 }
 
-// k_rollout's instantiations in the order of MEV_ROLLOUT_KERNELS (mev_plan.h): kRolloutFns[row][!TAB]
+// k_rollout's instantiations in the order of MEV_ROLLOUT_KERNELS (mev_plan.h): kRolloutFns[row][!TAB][VALUE]
 using RolloutFn = void (*)(const SimParams*, RolloutArgs, Outputs);
-#define MEV_ROLLOUT_FNS(T, NM, KM, P1, NC) {k_rollout<T, true, NM, KM, P1, NC>, k_rollout<T, false, NM, KM, P1, NC>},
-static const RolloutFn kRolloutFns[][2] = {MEV_ROLLOUT_KERNELS(MEV_ROLLOUT_FNS)};
+#define MEV_ROLLOUT_FNS(T, NM, KM, P1, NC)                                                   \
+    {{k_rollout<T, true, NM, KM, P1, NC, false>, k_rollout<T, true, NM, KM, P1, NC, true>},   \
+     {k_rollout<T, false, NM, KM, P1, NC, false>, k_rollout<T, false, NM, KM, P1, NC, true>}},
+static const RolloutFn kRolloutFns[][2][2] = {MEV_ROLLOUT_KERNELS(MEV_ROLLOUT_FNS)};
 #undef MEV_ROLLOUT_FNS
 static_assert(sizeof kRolloutFns / sizeof kRolloutFns[0] == kRolloutRows, "one kernel pair per rollout row");
 
 hipError_t launch_rollout(const SimParams& p, const SimParams* dp, const RolloutPlan& rp, const RolloutArgs& ra,
                           const Outputs& out, hipStream_t s) {
     if (rp.row < 0 || rp.row >= kRolloutRows || ra.T < 1) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(kRolloutFns[rp.row][!p.dist_tab], dim3(rp.grid), dim3(rp.block), rp.lds, s, dp, ra, out);
+    hipLaunchKernelGGL(kRolloutFns[rp.row][!p.dist_tab][ra.value_seq != nullptr], dim3(rp.grid), dim3(rp.block), rp.lds, s, dp, ra, out);
     return hipGetLastError();
 }
 
-hipError_t launch_policy_repack(const PolicyNet& dst, const float* const* w, const float* const* b, hipStream_t s) {
+hipError_t launch_policy_repack(const PolicyNet& dst, const float* const* w, const float* const* b, bool keep_head,
+                                hipStream_t s) {
     int n = 0;
     for (int l = 0; l < dst.layers; ++l)
         if ((dst.in[l] + 1) * dst.ld[l] > n) n = (dst.in[l] + 1) * dst.ld[l];
     hipLaunchKernelGGL(k_policy_repack, dim3((unsigned)((n + 255) / 256), (unsigned)dst.layers), dim3(256), 0, s, dst,
-                       w[0], w[1], w[2], b[0], b[1], b[2]);
+                       w[0], w[1], w[2], b[0], b[1], b[2], keep_head ? 1 : 0);
+    return hipGetLastError();
+}
+
+hipError_t launch_value_head_repack(const PolicyNet& dst, const float* wv, const float* bv, hipStream_t s) {
+    if (dst.layers < 2 || dst.ld[dst.layers - 1] <= dst.out[dst.layers - 1] || (wv && !bv)) return hipErrorInvalidValue;
+    const int n = dst.in[dst.layers - 1] + 1;
+    hipLaunchKernelGGL(k_value_head_repack, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, dst, wv, bv);
+    return hipGetLastError();
+}
+
+hipError_t launch_gae(const GaeArgs& a, hipStream_t s) {
+    if (a.T < 1 || a.E < 1 || a.N < 1 || !a.reward || !a.value || (!a.adv && !a.ret && !a.valid)) return hipErrorInvalidValue;
+    const size_t EN = (size_t)a.E * (size_t)a.N;
+    hipLaunchKernelGGL(k_gae, dim3((unsigned)((EN + WAVE - 1) / WAVE)), dim3(WAVE), 0, s, a);
     return hipGetLastError();
 }
 

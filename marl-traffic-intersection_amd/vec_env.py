@@ -417,17 +417,38 @@ class VecIntersectionEnv:
         dev = lambda x: self._dev_tensor(x.detach() if hasattr(x, "detach") else x, t.float32)
         return [dev(w) for w in weights], [dev(b) for b in biases], True
 
-    def make_policy(self, module_or_arrays):
+    def _value_inputs(self, value):
+        """(w, b, device) of a value head: an nn.Linear(H_last, 1) -- its parameters' own tensors -- or a (w, b) pair."""
+        w, b = (value.weight, value.bias) if hasattr(value, "weight") else value
+        if b is None:
+            raise ValueError("a value head is nn.Linear(H_last, 1) with a bias, or a (w, b) pair")
+        if self.backend != "torch":
+            host = lambda x: x.detach().cpu().numpy() if hasattr(x, "detach") else x
+            return host(w), host(b), False
+        self._bind_stream()
+        t = self._torch
+        dev = lambda x: self._dev_tensor(x.detach() if hasattr(x, "detach") else x, t.float32)
+        return dev(w), dev(b), True
+
+    def make_policy(self, module_or_arrays, value=None):
         """An MLP policy on the device (Handle.policy) from an nn.Sequential(Linear, ReLU, Linear[, ReLU,
         Linear]) or a (weights, biases) pair of array lists ([out][in] and [out]; the last layer has 2
-        outputs: throttle, steer).  `policy.refresh(module_or_arrays)` pushes new weights of the same shape.
+        outputs: throttle, steer).  value: a critic head on the same trunk, nn.Linear(H_last, 1) or a (w, b)
+        pair ([H_last] or [1][H_last], and [1]); `rollout` can then return value_seq.
+        `policy.refresh(module_or_arrays, value)` pushes new weights of the same shape, the head's included.
         torch backend: the weights are read on the current stream by a small kernel, no host copy, no sync."""
         w, b, device = self._policy_inputs(module_or_arrays)
         pol = self._h.policy(w, b, device=device)
+        if value is not None:
+            vw, vb, device = self._value_inputs(value)
+            pol.set_value_head(vw, vb, device=device)
 
-        def refresh(source=module_or_arrays):
+        def refresh(source=module_or_arrays, value=value):
             w, b, device = self._policy_inputs(source)
             pol.update(w, b, device=device)
+            if value is not None:
+                vw, vb, device = self._value_inputs(value)
+                pol.set_value_head(vw, vb, device=device)
 
         pol.refresh = refresh
         return pol
@@ -439,17 +460,22 @@ class VecIntersectionEnv:
         mean_seq [T, E, N, 2], reward_seq, done_seq, status_seq [T, E, N], terminated_seq, truncated_seq
         [T, E] -- those named in `outputs`.  sigma: None, or two floats for Gaussian-like exploration noise
         from the Philox stream (seed, counter): pass a new counter per call.  torch backend: device tensors
-        (kept per (T, outputs) and rewritten by the next call unless copy=True), stream-ordered, no host sync."""
+        (kept per (T, outputs) and rewritten by the next call unless copy=True), stream-ordered, no host sync.
+        With "value_seq" among the outputs (a policy made with value=...): value_seq [T + 1, E, N], V of the
+        observation before each sub-step and of the last one, and `ended_before` [E], whether the env's step
+        before this call ended it -- the dict is what `gae` takes."""
         T = int(T)
         key = (T, tuple(outputs), "rollout")
         o = self._out_eval.get(key)
+        values = "value_seq" in outputs
+        outs = _capi._ROLLOUT_OUTS + ((_capi._VALUE_OUT,) if values else ())
         if self.backend == "torch":
             t = self._torch
             self._bind_stream()
             if o is None:
                 o = self._out_eval[key] = {}
                 E, N, D = self.num_envs, self.num_agents, self.obs_dim
-                for k, dtype, shape in _capi._ROLLOUT_OUTS:
+                for k, dtype, shape in outs:
                     if k in outputs:
                         o[k] = t.zeros(shape(T, E, N, D), dtype=t.float32 if dtype is np.float32 else t.uint8,
                                        device=self._out["obs"].device)
@@ -458,14 +484,47 @@ class VecIntersectionEnv:
                 sp = self._dev_tensor(spawn_route, t.int32)
                 if tuple(sp.shape) != (T, self.num_envs):
                     raise ValueError(f"spawn_route must be [{T}][{self.num_envs}], got {tuple(sp.shape)}")
+            eb = None
+            if values:  # (read on the stream before the call rewrites the handle's last outputs; a fresh tensor)
+                last = {k: t.empty(self.num_envs, dtype=t.uint8, device=self._out["obs"].device)
+                        for k in ("terminated", "truncated")}
+                self._h.get_outputs(last, device=True)
+                eb = last["terminated"] | last["truncated"]
             self._h.rollout_policy(policy, T, dt, sigma, lo, hi, seed, counter, self.auto_reset, sp, out=o, device=True)
-            return {k: v.clone() for k, v in o.items()} if copy else o
+            r = {k: v.clone() for k, v in o.items()} if copy else dict(o)
+            if values:
+                r["ended_before"] = eb
+            return r
         if o is None:
             E, N, D = self.num_envs, self.num_agents, self.obs_dim
-            o = self._out_eval[key] = {k: np.zeros(shape(T, E, N, D), dtype) for k, dtype, shape in _capi._ROLLOUT_OUTS
-                                       if k in outputs}
+            o = self._out_eval[key] = {k: np.zeros(shape(T, E, N, D), dtype) for k, dtype, shape in outs if k in outputs}
+        eb = None
+        if values:
+            last = self._h.get_outputs()
+            eb = ((last["terminated"] != 0) | (last["truncated"] != 0)).astype(np.uint8)
         self._h.rollout_policy(policy, T, dt, sigma, lo, hi, seed, counter, self.auto_reset, spawn_route, out=o)
-        return {k: v.copy() for k, v in o.items()} if copy else o
+        r = {k: v.copy() for k, v in o.items()} if copy else dict(o)
+        if values:
+            r["ended_before"] = eb
+        return r
+
+    def gae(self, traj, gamma: float = 0.99, lam: float = 0.95, mask_reset_steps: bool = True):
+        """Advantages of a `rollout` dict that holds reward_seq and value_seq (Handle.gae): done_seq,
+        terminated_seq, truncated_seq and ended_before are used where the dict has them.  Returns
+        `advantages`, `returns` and `valid` [T, E, N]; with mask_reset_steps the transitions that follow an
+        env's end (this env's auto-reset steps, whose action came from the terminal observation) get
+        advantage 0 and valid 0.  Fresh arrays every call; torch: stream-ordered, no host sync."""
+        names = ("done_seq", "terminated_seq", "truncated_seq", "ended_before")
+        opt = {k: traj.get(k) for k in names}
+        outputs = ("advantages", "returns", "valid")
+        if self.backend != "torch":
+            return self._h.gae(traj["reward_seq"], traj["value_seq"], gamma=gamma, lam=lam,
+                               mask_reset_steps=mask_reset_steps, outputs=outputs, **opt)
+        t = self._torch
+        self._bind_stream()
+        opt = {k: None if v is None else self._dev_tensor(v, t.uint8) for k, v in opt.items()}
+        return self._h.gae(self._dev_tensor(traj["reward_seq"], t.float32), self._dev_tensor(traj["value_seq"], t.float32),
+                           gamma=gamma, lam=lam, mask_reset_steps=mask_reset_steps, outputs=outputs, device=True, **opt)
 
     def update_plans(self, actions, samples: int, scores=None, returns=None, mode: str = "elites", elites=None,
                      temperature: float = 1.0, sigma_min: float = 0.0):
