@@ -791,6 +791,75 @@ typedef struct {
 } mev_rollout_values_args;
 int mev_rollout_policy_values(mev_handle* h, const mev_rollout_values_args* args);
 
+/* mev_rollout_policy_repeat: closed-loop rollouts with frame skip -- T DECISIONS in one launch, each one policy
+ * pass and then mev_step_repeat with that action held for up to n = repeat sub-steps.  It is defined, per env and
+ * bit for bit, as this loop, obs_0 being the rows mev_get_outputs would return before the call:
+ *
+ *   for t = 0 .. T-1:
+ *       a_t = policy(obs_t)                    (the stated FMA chains; noise word index t = the DECISION index,
+ *                                               counter (lo32, hi32, e * 64 + i, t); value_seq[t] = V(obs_t) if asked)
+ *       r   = mev_step_repeat(actions = a_t, repeat = n, dt, spawn_route rows [t][0..n), flags)
+ *                                              (exactly mev_step_repeat: reward summed in f32 in sub-step order, done
+ *                                               latched, status latched at the latest done else sub-step k's,
+ *                                               terminated / truncated of sub-step k, the env stopping at its first
+ *                                               ended sub-step, MEV_AUTO_RESET only at the decision's first sub-step)
+ *       obs_{t+1} = r.obs                      (head and ONE LiDAR cast, from the state the env stopped at)
+ *       row t of obs_seq / reward_seq / done_seq / status_seq / terminated_seq / truncated_seq = r's outputs
+ *       row t of actions_seq / mean_seq = a_t / mu_t;   substeps_seq[t][e] = r.substeps[e]
+ *   value_seq[T] = V(obs_T)                    (if asked: one more trunk pass, no noise word, no step)
+ *
+ * Every *_seq row is one decision; rollout.spawn_route, if given, is [T][repeat][E].  Sub-step s of decision t
+ * uses the handle's Philox counter + t * n + s (the NPC spawner), an auto-reset's route draw its decision's first
+ * sub-step's counter, and the counter advances by T * n whatever the envs did: mev_step_repeat's rule, T times.
+ * Afterwards the handle is exactly where the T mev_step_repeat calls would have left it: state and car sizes,
+ * pending-reset flags, the last outputs (with device pointers: row T-1 of the caller's arrays where given), the
+ * Philox counter and the NPC diagnostics.  Every element of every given *_seq array is written; a null array
+ * leaves that output in the handle's own buffers.  value_seq is optional here (NULL: no value row is computed)
+ * and needs a value head.  With repeat = 1 every output equals mev_rollout_policy's bit for bit, and with
+ * value_seq mev_rollout_policy_values'.  The actor-critic calls work at the decision level unchanged: value_seq
+ * rows are V of the observation each decision was made from, and mev_gae on the summed rewards applies gamma and
+ * lambda per decision.
+ * Supported shapes, the step-server stop, the identity env order, staging, synchronisation and "not counted by
+ * mev_kernel_timing" are all as mev_rollout_policy: every row for which mev_get_rollout_row is >= 0 runs, with no
+ * slower fallback.  Errors (MEV_E_INVALID, the handle untouched): everything mev_rollout_policy refuses, repeat
+ * outside 1..MEV_MAX_REPEAT, T * repeat above MEV_MAX_ROLLOUT_SUBSTEPS, a non-null value_seq on a policy without a
+ * value head.
+ * How it runs: the kernel of mev_rollout_policy with the repeat as a flag of the instantiation;
+ * inside a decision each sub-step is a whole fused step without the LiDAR (the state goes through L2 between
+ * sub-steps, as in the plain call), and the sub-step the env stops at casts the LiDAR from its own LDS.
+ * Estimated beforehand, from other calls' numbers: the policy pass (31-33 us) and the LiDAR once per decision, and
+ * 8.4 us for each further sub-step's car part.  Measured (python tools/bench_rollout_repeat.py ->
+ * profiles/rollout_repeat_sweep.json; tools/bench_rollout.py's method: device pointers, auto-reset, every
+ * *_seq output plus value_seq and substeps_seq, medians of five alternated blocks (min-max)), 4096 envs x 8 agents x 64
+ * beams, policy 95-64-64-2 with a value head, T = 16 decisions, (a) the call against (b) what a user runs today for the
+ * same semantics -- an eager torch forward, a clamp and mev_step_repeat per decision into the same tensors -- and (c)
+ * mev_rollout_policy_values over T * n sub-steps (other semantics, orientation only), ms per call:
+ *   n = 1: (a) 0.776 (0.775-0.802)  (b) 1.952 (1.948-1.955)  (c) 0.843      n = 2: (a) 0.992 (0.991-0.993)  (b) 2.044 (2.033-2.114)  (c) 1.649
+ *   n = 4: (a) 1.431 (1.430-1.436)  (b) 2.145 (2.140-2.148)  (c) 3.235      n = 8: (a) 2.328 (2.326-2.332)  (b) 2.705 (2.699-2.714)  (c) 6.422
+ * -- below (b) by more than both blocks' spreads at every n, 2.5x to 1.16x: a decision costs 48.5 us plus 13.5-13.9 us per
+ * further sub-step, where (b) is launch-bound at 122-134 us per decision up to n = 4.  The estimate of the further
+ * sub-step was low by 5 us: each one is a whole fused step without the LiDAR -- the state's round trip through L2 and an
+ * observation head that the next sub-step overwrites included -- not k_cars_repeat's looped car part.  64 envs, n = 4:
+ * 0.911 against 2.054 ms.  The runtime-layout row (one car 55 x 24), n = 4: 1.591 against 2.096 ms.  It LOSES at 4096 envs
+ * x 1 agent with traffic 0.5, n = 4: 4.220 (3.993-4.387) against 3.221 ms (3.140-3.329) -- as mev_rollout_policy loses there
+ * (above): one wave per env, and a wave's policy pass costs the same for 1 agent as for 8.
+ * A first version with the sub-steps as a loop INSIDE the loop of decisions was
+ * bit-exact and slower throughout (n = 1: 1.187 ms, n = 4: 1.994 ms, a tie with (b), n = 8: 3.120 ms, a loss): its kernels
+ * spilt 236 VGPRs where the flat loop's spill 105 (profiles/rollout_repeat_sweep_nested.json).  The existing calls are
+ * unchanged: their kernels keep the parent's register figures to the byte, and mev_rollout_policy's first row took
+ * 0.944 / 0.941 ms on this build against 0.941 / 0.942 ms on the commit before it in one session (two alternated pairs of
+ * processes; each block's spread is 0.001 ms, so the processes differ by more than the blocks, in both directions);
+ * bench.py's config 3 1.2747 / 1.2750 against 1.2743 / 1.2728 G agent-steps/s. */
+#define MEV_MAX_ROLLOUT_SUBSTEPS 4096   /* T * repeat of one launch: at the measured <= 60 us per sub-step about 0.25 s */
+typedef struct {
+    mev_rollout_args rollout;  /* as mev_rollout_policy, except: every *_seq row is one DECISION (above);
+                                  rollout.spawn_route, if given, is [T][repeat][E] */
+    float*   value_seq;        /* optional [T+1][E][N], as mev_rollout_policy_values'; needs a value head */
+    int32_t  repeat;           /* n, 1..MEV_MAX_REPEAT; T * n <= MEV_MAX_ROLLOUT_SUBSTEPS */
+    int32_t* substeps_seq;     /* optional [T][E]: sub-steps decision t ran in env e */
+} mev_rollout_repeat_args;
+int mev_rollout_policy_repeat(mev_handle* h, const mev_rollout_repeat_args* args);
+
 /* mev_gae: generalised advantage estimation over a rollout's arrays, one reverse scan on the device.
  * THE ARITHMETIC IS THE CONTRACT: f32, multiply, then add, no FMA, per (e, i) and for t descending, with
  * c the f32 product gamma * lambda, computed once:

@@ -54,7 +54,7 @@ EXPORTED = (
     "mev_pool_capture", "mev_pool_get_state", "mev_expand_plans", "mev_sample_plans", "mev_update_plans",
     "mev_sample_expand_plans", "mev_get_step_row", "mev_policy_create", "mev_policy_update", "mev_policy_destroy",
     "mev_rollout_policy", "mev_get_rollout_row", "mev_policy_set_value_head", "mev_policy_has_value_head",
-    "mev_rollout_policy_values", "mev_gae",
+    "mev_rollout_policy_values", "mev_gae", "mev_rollout_policy_repeat",
 )
 
 
@@ -162,6 +162,13 @@ class MevRolloutValuesArgs(ctypes.Structure):  # mev_rollout_values_args
     _fields_ = [("rollout", MevRolloutArgs), ("value_seq", _vp)]
 
 
+MEV_MAX_ROLLOUT_SUBSTEPS = 4096
+
+
+class MevRolloutRepeatArgs(ctypes.Structure):  # mev_rollout_repeat_args
+    _fields_ = [("rollout", MevRolloutArgs), ("value_seq", _vp), ("repeat", ctypes.c_int32), ("substeps_seq", _vp)]
+
+
 MEV_GAE_MASK_RESET_STEPS = 0x100
 
 
@@ -184,6 +191,8 @@ _ROLLOUT_OUTS = (("obs_seq", np.float32, lambda T, E, N, D: (T, E, N, D)),
 ROLLOUT_OUTPUTS = tuple(k for k, _, _ in _ROLLOUT_OUTS)
 # ... and of mev_rollout_policy_values, which rollout_policy calls when value_seq is asked for
 _VALUE_OUT = ("value_seq", np.float32, lambda T, E, N, D: (T + 1, E, N))
+# ... and of mev_rollout_policy_repeat, which it calls with repeat > 1 or when substeps_seq is asked for
+_SUBSTEPS_OUT = ("substeps_seq", np.int32, lambda T, E, N, D: (T, E))
 _GAE_OUTS = (("advantages", np.float32), ("returns", np.float32), ("valid", np.uint8))
 
 
@@ -300,6 +309,7 @@ def load_library(variant: str = None):
     L.mev_policy_set_value_head.argtypes = [_vp, _vp, _vp, ctypes.c_uint32]
     L.mev_policy_has_value_head.argtypes = [_vp, i32p]
     L.mev_rollout_policy_values.argtypes = [_vp, ctypes.POINTER(MevRolloutValuesArgs)]
+    L.mev_rollout_policy_repeat.argtypes = [_vp, ctypes.POINTER(MevRolloutRepeatArgs)]
     L.mev_gae.argtypes = [_vp, ctypes.POINTER(MevGaeArgs)]
     L.mev_set_serve.argtypes = [_vp, ctypes.c_int32]
     L.mev_serve_stats.argtypes = [_vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64), i32p]
@@ -890,7 +900,8 @@ class Handle:
 
     def rollout_policy(self, policy: "Policy", T: int, dt: float = 1.0 / 60.0, sigma=None, lo=(-1.0, -1.0),
                        hi=(1.0, 1.0), seed: int = 0, counter: int = 0, auto_reset: bool = False, spawn_route=None,
-                       outputs=ROLLOUT_OUTPUTS, out: Optional[dict] = None, device: bool = False, flags: int = 0):
+                       outputs=ROLLOUT_OUTPUTS, out: Optional[dict] = None, device: bool = False, flags: int = 0,
+                       repeat: int = 1):
         """Closed-loop rollout (mev_rollout_policy): T sub-steps of observe -> policy -> step in one launch,
         bit for bit the loop of the stated policy arithmetic and `step`.  sigma: None (deterministic) or
         two host floats; the noise is sample_plans' from the Philox stream (seed, counter) with the env in
@@ -901,10 +912,18 @@ class Handle:
         of `out`, or new torch tensors for `outputs`; spawn_route is then a device array too.
         With "value_seq" among the outputs (or in `out`) the call is mev_rollout_policy_values: the policy
         needs a value head (Policy.set_value_head) and value_seq [T + 1][E][N] holds V(obs_t), row T the
-        bootstrap value; everything else is the same bits."""
-        T, E, N, D = int(T), self.E, self.N, self.D
-        shapes = {k: (dtype, shape(T, E, N, D)) for k, dtype, shape in _ROLLOUT_OUTS + (_VALUE_OUT,)}
-        values = "value_seq" in outputs if out is None or not out else "value_seq" in out
+        bootstrap value; everything else is the same bits.
+        repeat > 1, or "substeps_seq" among the outputs, makes the call mev_rollout_policy_repeat: T DECISIONS,
+        each one policy pass and then `step_repeat` with that action held for up to `repeat` sub-steps -- every
+        *_seq row is then a decision's (summed reward, latched done / status, one LiDAR cast), the noise word
+        index is the decision, spawn_route is [T][repeat][E], T * repeat <= MEV_MAX_ROLLOUT_SUBSTEPS, and
+        substeps_seq [T][E] (int32) holds the sub-steps each decision ran.  With repeat = 1 the outputs are
+        those of the other two calls bit for bit."""
+        T, E, N, D, repeat = int(T), self.E, self.N, self.D, int(repeat)
+        shapes = {k: (dtype, shape(T, E, N, D)) for k, dtype, shape in _ROLLOUT_OUTS + (_VALUE_OUT, _SUBSTEPS_OUT)}
+        named = outputs if out is None or not out else out
+        values = "value_seq" in named
+        held = repeat != 1 or "substeps_seq" in named  # (today's calls take today's path)
         out = dict(out) if out is not None else {}
         for k in out:
             if k not in shapes:
@@ -916,12 +935,14 @@ class Handle:
                 dev = f"cuda:{self.config['device']}"
                 for k in missing:
                     dtype, shape = shapes[k]
-                    out[k] = torch.empty(shape, dtype=torch.float32 if dtype is np.float32 else torch.uint8, device=dev)
+                    tdt = torch.float32 if dtype is np.float32 else torch.int32 if dtype is np.int32 else torch.uint8
+                    out[k] = torch.empty(shape, dtype=tdt, device=dev)
         else:
             if spawn_route is not None:
                 spawn_route = np.ascontiguousarray(np.asarray(spawn_route, np.int32))
-                if spawn_route.shape != (T, E):
-                    raise ValueError(f"spawn_route must be [{T}][{E}], got {spawn_route.shape}")
+                want = (T, repeat, E) if held else (T, E)
+                if spawn_route.shape != want and not (held and repeat == 1 and spawn_route.shape == (T, E)):
+                    raise ValueError(f"spawn_route must be {list(want)}, got {spawn_route.shape}")
             if not out:
                 for k in outputs:
                     out[k] = np.zeros(shapes[k][1], shapes[k][0])
@@ -942,7 +963,14 @@ class Handle:
         for k in ROLLOUT_OUTPUTS:
             setattr(a, k, _ptr(out.get(k)))
         a.flags = (MEV_DEVICE_PTRS if device else 0) | (MEV_AUTO_RESET if auto_reset else 0) | int(flags)
-        if values:
+        if held:
+            ra = MevRolloutRepeatArgs()
+            ra.rollout, ra.value_seq, ra.repeat = a, _ptr(out.get("value_seq")), repeat
+            ra.substeps_seq = _ptr(out.get("substeps_seq"))
+            if values and ra.value_seq is None:
+                raise ValueError("value_seq is named but not given")
+            _check(self._lib.mev_rollout_policy_repeat(self._h, ctypes.byref(ra)))
+        elif values:
             va = MevRolloutValuesArgs()
             va.rollout, va.value_seq = a, _ptr(out.get("value_seq"))
             _check(self._lib.mev_rollout_policy_values(self._h, ctypes.byref(va)))

@@ -1791,7 +1791,10 @@ int mev_get_rollout_row(const mev_handle* h, int32_t* row) {
 
 // mev_rollout_policy: T sub-steps of policy + fused step in one launch (k_rollout), along step_window's path.
 // value_seq (mev_rollout_policy_values, checked there): non-null runs k_rollout's value instantiation.
-static int rollout(mev_handle* h, const mev_rollout_args* a, float* value_seq) {
+// rep (mev_rollout_policy_repeat, checked there; null: the two calls above): T decisions of up to rep->repeat
+// sub-steps each -- spawn_route staged as [T * n][E], the Philox counter advanced by T * n, spawn_prob once from
+// dt as mev_step_repeat computes it -- through k_rollout's REPEAT instantiations.
+static int rollout(mev_handle* h, const mev_rollout_args* a, float* value_seq, const mev_rollout_repeat_args* rep = nullptr) {
     const mev_policy* pol = a->policy;
     if (!pol) return fail(MEV_E_INVALID, "mev_rollout_policy: policy required");
     if (pol->h != h) return fail(MEV_E_INVALID, "mev_rollout_policy: the policy belongs to another handle");
@@ -1822,12 +1825,14 @@ static int rollout(mev_handle* h, const mev_rollout_args* a, float* value_seq) {
     }
     const bool dev = (a->flags & MEV_DEVICE_PTRS) != 0;
     const int T = a->length;
+    const size_t n = rep ? size_t(rep->repeat) : 1;  // sub-steps per row
     const size_t E = size_t(h->cfg.num_envs), EN = E * size_t(h->cfg.num_agents), D = size_t(h->D);
-    mev::RolloutArgs ra{};
+    mev::RolloutRepeatArgs ra{};
+    ra.repeat = int32_t(n);
     ra.in.dt = a->dt;
     ra.in.spawn_prob = spawn_prob(h, a->dt);
     ra.in.auto_reset = (a->flags & MEV_AUTO_RESET) ? 1 : 0;
-    ra.in.rng_counter = h->rng_counter;  // sub-step t: + t (k_rollout)
+    ra.in.rng_counter = h->rng_counter;  // sub-step t: + t (k_rollout; REPEAT: sub-step s of decision t + t n + s)
     ra.net = pol->net;
     ra.T = T;
     ra.pol_off = rp.pol_off;
@@ -1844,7 +1849,7 @@ static int rollout(mev_handle* h, const mev_rollout_args* a, float* value_seq) {
     ra.ctr_lo = uint32_t(a->noise_counter);
     ra.ctr_hi = uint32_t(a->noise_counter >> 32);
     Stage st(h, dev);
-    st.in(&ra.in.spawn_route, a->spawn_route, size_t(T) * E);
+    st.in(&ra.in.spawn_route, a->spawn_route, size_t(T) * n * E);
     st.out(&ra.obs_seq, a->obs_seq, size_t(T) * EN * D);
     st.out(&ra.actions_seq, a->actions_seq, size_t(T) * EN * 2);
     st.out(&ra.mean_seq, a->mean_seq, size_t(T) * EN * 2);
@@ -1854,10 +1859,12 @@ static int rollout(mev_handle* h, const mev_rollout_args* a, float* value_seq) {
     st.out(&ra.term_seq, a->terminated_seq, size_t(T) * E);
     st.out(&ra.trunc_seq, a->truncated_seq, size_t(T) * E);
     st.out(&ra.value_seq, value_seq, size_t(T + 1) * EN);
+    st.out(&ra.substeps_seq, rep ? rep->substeps_seq : nullptr, size_t(T) * E);
     if (int r = st.upload()) return r;
-    h->rng_counter += uint64_t(T);
+    h->rng_counter += uint64_t(T) * uint64_t(n);
     h->deal_valid = false;  // NPC counts change outside the dealt step: the deal restarts
-    HIP_TRY(mev::launch_rollout(h->sp, h->d_sp, rp, ra, h->internal, h->stream));
+    if (rep) HIP_TRY(mev::launch_rollout_repeat(h->sp, h->d_sp, rp, ra, h->internal, h->stream));
+    else HIP_TRY(mev::launch_rollout(h->sp, h->d_sp, rp, ra, h->internal, h->stream));
     // the last outputs: row T - 1.  Device pointers: tracked where the caller's arrays hold them, as after
     // mev_step.  Host pointers: the rows live in the staging block, so they are copied into the handle's buffers.
     const size_t t1 = size_t(T - 1);
@@ -1891,6 +1898,17 @@ int mev_rollout_policy_values(mev_handle* h, const mev_rollout_values_args* va) 
     if (va->rollout.policy && !va->rollout.policy->has_value)
         return fail(MEV_E_INVALID, "mev_rollout_policy_values: the policy has no value head (mev_policy_set_value_head)");
     return rollout(h, &va->rollout, va->value_seq);
+}
+
+int mev_rollout_policy_repeat(mev_handle* h, const mev_rollout_repeat_args* ra) {
+    if (!h || !ra) return fail(MEV_E_INVALID, "null argument");
+    if (ra->repeat < 1 || ra->repeat > MEV_MAX_REPEAT)
+        return fail(MEV_E_INVALID, "repeat must be in 1.." + std::to_string(MEV_MAX_REPEAT));
+    if (int64_t(ra->rollout.length) * int64_t(ra->repeat) > MEV_MAX_ROLLOUT_SUBSTEPS)
+        return fail(MEV_E_INVALID, "length * repeat must be at most " + std::to_string(MEV_MAX_ROLLOUT_SUBSTEPS));
+    if (ra->value_seq && ra->rollout.policy && !ra->rollout.policy->has_value)
+        return fail(MEV_E_INVALID, "mev_rollout_policy_repeat: the policy has no value head (mev_policy_set_value_head)");
+    return rollout(h, &ra->rollout, ra->value_seq, ra);
 }
 
 // mev_gae (include/marlenv.h): k_gae's reverse scan.  Reads and writes its arguments only; host pointers go

@@ -437,6 +437,20 @@ struct RolloutArgs {
 // (rp: plan_rollout of p's shape, its row >= 0)
 hipError_t launch_rollout(const SimParams& p, const SimParams* dp, const RolloutPlan& rp, const RolloutArgs& ra,
                           const Outputs& out, hipStream_t s);
+// mev_rollout_policy_repeat (k_rollout's REPEAT instantiations): T DECISIONS, each one policy phase (noise word
+// index t) and then up to `repeat` sub-steps of the fused step's body on the held action row -- sub-step s with
+// in.spawn_route row t * repeat + s ([T * repeat][E]), in.rng_counter + t * repeat + s, and in.auto_reset at
+// s == 0 only -- the env stopping at its first ended sub-step.  Row t of the *_seq arrays is the decision's:
+// the reward summed in sub-step order, done and status latched (RepCarry's rules), the flags and the
+// observation of the sub-step it stopped at.  A struct of its own on top of RolloutArgs, so that the kernel
+// argument segment of the instantiations without REPEAT is what it was; `value_seq` stays the base's last
+// field and chooses the value instantiation as it does there.
+struct RolloutRepeatArgs : RolloutArgs {
+    int32_t repeat;         // n, 1..MEV_MAX_REPEAT
+    int32_t* substeps_seq;  // [T][E] sub-steps decision t ran in env e (nullable)
+};
+hipError_t launch_rollout_repeat(const SimParams& p, const SimParams* dp, const RolloutPlan& rp,
+                                 const RolloutRepeatArgs& ra, const Outputs& out, hipStream_t s);
 
 // mev_gae (k_gae): the reverse scan of mev_gae.h's gae_step over T rows per (e, i).  c = gamma * lambda in f32.
 struct GaeArgs {

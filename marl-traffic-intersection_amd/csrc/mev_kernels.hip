@@ -4381,8 +4381,28 @@ __device__ __forceinline__ void policy_phase(const RolloutArgs& ra, const float*
 // VALUE: mev_rollout_policy_values -- row t of value_seq from the policy phase of sub-step t, and after the
 // last sub-step one more policy phase on the rows it wrote (hidden layers and the value chain, no step) for
 // row T.  A flag of the instantiation, not of the launch: mev_rollout_policy runs the code it ran before.
-template <bool TRAFFIC, bool TAB, int NM, int KM, int RP1, int RNC, bool VALUE>
-__global__ __launch_bounds__(WAVE, 4) void k_rollout(const SimParams* __restrict__ pp, RolloutArgs ra, Outputs out0) {
+// REPEAT (mev_rollout_policy_repeat): t counts DECISIONS.  After decision t's policy phase (noise word index t)
+// the wave runs up to ra.repeat sub-steps of the body on the held action row, each a whole fused step up to
+// and including cars_post -- the state goes back to the wave's own loads through L2 behind the fences below,
+// as between two sub-steps of the plain call -- with in.auto_reset at the first one only.  The body's hook
+// ends a sub-step that is neither the window's last nor the env's end before the LiDAR (cars_post's own stop
+// test for REP, wave-uniform); the one the env stops at casts as ever, from its own LDS.  Every sub-step's
+// cars_post writes its reward / done / status, flags and head into row t; after each, lane = agent reads
+// its three values back and folds them by RepCarry's rules (acc = s == 0 ? r : acc + r; the latest done's
+// status), and after the stop stores the sums over them.  The flags, state and head of row t are then the
+// stop's own.  Nothing is carried across the body but those three registers, the sub-step and the stop bit:
+// every sub-step reads its arguments as a sub-step of the plain call does.
+// The sub-steps of all decisions are ONE flat loop -- s == 0 runs the policy phase of decision t first -- and
+// not a loop of sub-steps inside the loop of decisions: nested, the same statements spilt 236 VGPRs to 916
+// bytes of scratch on the compile-time row with VALUE (flat: 105 and 412; the plain call: 132 and 524) and a
+// decision of ONE sub-step took 74 us where the plain call's sub-step takes 53.
+// The argument struct grows by a derived type (RolloutRepeatArgs) for REPEAT alone, and the plain call's loop
+// below is untouched.
+template <bool REPEAT>
+using RolloutKernArgs = typename std::conditional<REPEAT, RolloutRepeatArgs, RolloutArgs>::type;
+template <bool TRAFFIC, bool TAB, int NM, int KM, int RP1, int RNC, bool VALUE, bool REPEAT = false>
+__global__ __launch_bounds__(WAVE, 4) void k_rollout(const SimParams* __restrict__ pp, RolloutKernArgs<REPEAT> ra,
+                                                     Outputs out0) {
     constexpr int PK = 1;
     constexpr bool SPLIT = false, ESPLIT = false, WC = false;
     constexpr int P1 = RP1, NC = RNC;
@@ -4396,6 +4416,77 @@ __global__ __launch_bounds__(WAVE, 4) void k_rollout(const SimParams* __restrict
     const float* obs = ra.obs0;
     int obs_ld = D;
     const int rows = VALUE ? ra.T + 1 : ra.T;
+    if constexpr (REPEAT) {
+        const int n = ra.repeat;
+        float acc = 0.0f;                      // lane = agent: the decision's reward sum,
+        uint32_t any_done = 0u, latched = 0u;  // its done latch and the status at its latest done
+        for (int t = 0, s = 0; t < rows;) {  // sub-step s of decision t; s == 0 starts with the policy phase
+            // this decision's rows: the caller's arrays' row t, else the handle's buffers
+            Outputs out = out0;
+            if (ra.obs_seq) { out.obs = ra.obs_seq + (size_t)t * EN * D; out.obs_ld = D; }
+            if (ra.reward_seq) out.rew = ra.reward_seq + (size_t)t * EN;
+            if (ra.done_seq) out.done = ra.done_seq + (size_t)t * EN;
+            if (ra.status_seq) out.status = ra.status_seq + (size_t)t * EN;
+            if (ra.term_seq) out.term = ra.term_seq + (size_t)t * E;
+            if (ra.trunc_seq) out.trunc = ra.trunc_seq + (size_t)t * E;
+            float* act_row = ra.actions_seq ? ra.actions_seq + (size_t)t * EN * 2 : ra.act_scratch;
+            if (s == 0) {
+                // the actions the policy writes are read back by this wave's own lanes in the body (the fences)
+                float* mean_row = ra.mean_seq ? ra.mean_seq + (size_t)t * EN * 2 : nullptr;
+                __builtin_amdgcn_s_setprio(kPrioCars);
+                policy_phase<VALUE>(ra, obs, obs_ld, act_row, mean_row, VALUE ? ra.value_seq + (size_t)t * EN : nullptr,
+                                    !VALUE || t < ra.T, env, N, D, t, scratch, lane);
+                if (VALUE && t == ra.T) break;  // (the bootstrap row: no sub-step follows)
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+                __builtin_amdgcn_wave_barrier();
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+            }
+            const size_t q = (size_t)t * (size_t)n + (size_t)s;  // the sub-step's spawn_route row and counter offset
+            StepInputs in = ra.in;
+            in.actions = act_row;
+            in.spawn_route = ra.in.spawn_route ? ra.in.spawn_route + q * E : nullptr;
+            in.rng_counter = ra.in.rng_counter + (uint64_t)q;
+            if (s > 0) in.auto_reset = 0;  // (mev_step_repeat: only at the window's first sub-step)
+            bool stop = true;  // (wave-uniform) the env ended, or the window's last sub-step
+            [&]() {  // one sub-step: k_step's body, without the LiDAR unless the decision stops here
+#define MEV_STEP_BODY_AFTER_CARS             \
+    stop = cx.ended || s + 1 >= n; \
+    if (!stop) return;
+#include "mev_step_body.inc"
+#undef MEV_STEP_BODY_AFTER_CARS
+            }();
+            // the state and the rows this wave wrote, read back by its own lanes below and in the next sub-step
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+            if (lane < N) {  // RepCarry's rules on what this sub-step's cars_post stored (lane = agent)
+                const size_t g = (size_t)env * N + lane;
+                const float r = out.rew[g];
+                const uint32_t d = out.done[g], st = out.status[g];
+                acc = s == 0 ? r : acc + r;
+                if (d || s == 0) {  // (s == 0: the decision's first values; later: the latest done's)
+                    any_done = d;
+                    latched = st;
+                }
+                if (stop && s > 0) {  // (a decision of one sub-step holds its values already)
+                    out.rew[g] = acc;
+                    out.done[g] = (uint8_t)any_done;
+                    out.status[g] = (uint8_t)(any_done ? latched : st);
+                }
+            }
+            if (stop) {
+                if (lane == 0 && ra.substeps_seq) ra.substeps_seq[(size_t)t * E + env] = s + 1;
+                obs = out.obs;
+                obs_ld = out.obs_ld;
+                ++t;
+                s = 0;
+            } else {
+                ++s;
+            }
+        }
+        return;
+    }
+    // the plain calls: one sub-step per row
     for (int t = 0; t < rows; ++t) {
         // this sub-step's rows: the caller's arrays' row t, else the handle's buffers
         Outputs out = out0;
@@ -4687,7 +4778,8 @@ hipError_t launch_step_window(const SimParams& p, const StepInputs& in, const Ou
     return launch_part(p, in, out, 0, p.E, s, nullptr, &w);
 }
 
-// k_rollout's instantiations in the order of MEV_ROLLOUT_KERNELS (mev_plan.h): kRolloutFns[row][!TAB][VALUE]
+// k_rollout's instantiations in the order of MEV_ROLLOUT_KERNELS (mev_plan.h): kRolloutFns[row][!TAB][VALUE], and
+// those with REPEAT -- the same rows, their own argument type -- in kRolloutRepeatFns[row][!TAB][VALUE]
 using RolloutFn = void (*)(const SimParams*, RolloutArgs, Outputs);
 #define MEV_ROLLOUT_FNS(T, NM, KM, P1, NC)                                                   \
     {{k_rollout<T, true, NM, KM, P1, NC, false>, k_rollout<T, true, NM, KM, P1, NC, true>},   \
@@ -4695,6 +4787,24 @@ using RolloutFn = void (*)(const SimParams*, RolloutArgs, Outputs);
 static const RolloutFn kRolloutFns[][2][2] = {MEV_ROLLOUT_KERNELS(MEV_ROLLOUT_FNS)};
 #undef MEV_ROLLOUT_FNS
 static_assert(sizeof kRolloutFns / sizeof kRolloutFns[0] == kRolloutRows, "one kernel pair per rollout row");
+
+using RolloutRepeatFn = void (*)(const SimParams*, RolloutRepeatArgs, Outputs);
+#define MEV_ROLLOUT_REPEAT_FNS(T, NM, KM, P1, NC)                                                          \
+    {{k_rollout<T, true, NM, KM, P1, NC, false, true>, k_rollout<T, true, NM, KM, P1, NC, true, true>},   \
+     {k_rollout<T, false, NM, KM, P1, NC, false, true>, k_rollout<T, false, NM, KM, P1, NC, true, true>}},
+static const RolloutRepeatFn kRolloutRepeatFns[][2][2] = {MEV_ROLLOUT_KERNELS(MEV_ROLLOUT_REPEAT_FNS)};
+#undef MEV_ROLLOUT_REPEAT_FNS
+static_assert(sizeof kRolloutRepeatFns / sizeof kRolloutRepeatFns[0] == kRolloutRows, "one kernel pair per rollout row");
+static_assert(std::is_base_of<RolloutArgs, RolloutRepeatArgs>::value && std::is_trivially_copyable<RolloutRepeatArgs>::value,
+              "RolloutRepeatArgs: RolloutArgs, then the repeat's fields");
+
+hipError_t launch_rollout_repeat(const SimParams& p, const SimParams* dp, const RolloutPlan& rp,
+                                 const RolloutRepeatArgs& ra, const Outputs& out, hipStream_t s) {
+    if (rp.row < 0 || rp.row >= kRolloutRows || ra.T < 1 || ra.repeat < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(kRolloutRepeatFns[rp.row][!p.dist_tab][ra.value_seq != nullptr], dim3(rp.grid), dim3(rp.block), rp.lds,
+                       s, dp, ra, out);
+    return hipGetLastError();
+}
 
 hipError_t launch_rollout(const SimParams& p, const SimParams* dp, const RolloutPlan& rp, const RolloutArgs& ra,
                           const Outputs& out, hipStream_t s) {

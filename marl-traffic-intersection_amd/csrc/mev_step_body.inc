@@ -4,7 +4,10 @@
 // scope: the template parameters TRAFFIC, TAB, NM, KM, PK, SPLIT, ESPLIT, P1, NC, WC and
 // pp (const SimParams*), in (StepInputs), out (Outputs).  Kept textually in the
 // kernel: passing the step to an inlined function changed k_step's code (1.2 %
-// slower at config 3, profiles/r3_ab_step_body.txt).
+// slower at config 3, profiles/r3_ab_step_body.txt).  An includer may define
+// MEV_STEP_BODY_AFTER_CARS: statements that run after cars_post / deal_append and before
+// the LiDAR, with the car part's CarsCtx `cx` in scope (k_rollout's frame skip returns
+// there from a sub-step that needs no cast); undefined, the body is what it was.
     static_assert(!SPLIT || !TRAFFIC || ESPLIT, "split waves with traffic: the early split");
     static_assert(!WC || (!TRAFFIC && !TAB && NM > 0 && PK == 1 && !SPLIT && P1 >= WAVE && NC > 0),
                   "the world at compile time: one wave per env, the counts at compile time, no table");
@@ -225,6 +228,9 @@
     }
 #endif
     deal_append<TRAFFIC>(p, in, cx, e);
+#if defined(MEV_STEP_BODY_AFTER_CARS)  // an includer's hook after the car part (k_rollout's frame skip); else nothing
+    MEV_STEP_BODY_AFTER_CARS
+#endif
 #if defined(MEV_EXP_STOP) && MEV_EXP_STOP == 0  // (stop0 keeps the deal: the env order stays the product's)
     return;
 #endif

@@ -454,7 +454,7 @@ class VecIntersectionEnv:
         return pol
 
     def rollout(self, policy, T: int, dt: float = 1.0 / 60.0, sigma=None, lo=(-1.0, -1.0), hi=(1.0, 1.0), seed: int = 0,
-                counter: int = 0, spawn_route=None, outputs=_capi.ROLLOUT_OUTPUTS, copy: bool = False):
+                counter: int = 0, spawn_route=None, outputs=_capi.ROLLOUT_OUTPUTS, copy: bool = False, repeat: int = 1):
         """T steps of observe -> policy -> step in one launch (Handle.rollout_policy), auto-reset as this env
         was made: a dict of obs_seq [T, E, N, obs_dim] (the observation after each sub-step), actions_seq,
         mean_seq [T, E, N, 2], reward_seq, done_seq, status_seq [T, E, N], terminated_seq, truncated_seq
@@ -463,12 +463,19 @@ class VecIntersectionEnv:
         (kept per (T, outputs) and rewritten by the next call unless copy=True), stream-ordered, no host sync.
         With "value_seq" among the outputs (a policy made with value=...): value_seq [T + 1, E, N], V of the
         observation before each sub-step and of the last one, and `ended_before` [E], whether the env's step
-        before this call ended it -- the dict is what `gae` takes."""
-        T = int(T)
+        before this call ended it -- the dict is what `gae` takes.
+        repeat = n > 1 (Handle.rollout_policy's): T decisions, each action held for up to n sub-steps as
+        `step` holds it with frame_skip=n -- rewards summed, done and status latched, one LiDAR cast, the env
+        stopping at its end; every row is a decision's, spawn_route is [T, repeat, E], and "substeps_seq"
+        among the outputs gives the sub-steps each decision ran [T, E] (int32).  `repeat` does NOT default to
+        the constructor's frame_skip -- this call never repeated -- so pass repeat=env.frame_skip to roll out
+        as `step` steps.  `gae` on such a dict applies gamma and lambda per decision."""
+        T, repeat = int(T), int(repeat)
         key = (T, tuple(outputs), "rollout")
         o = self._out_eval.get(key)
         values = "value_seq" in outputs
-        outs = _capi._ROLLOUT_OUTS + ((_capi._VALUE_OUT,) if values else ())
+        outs = _capi._ROLLOUT_OUTS + ((_capi._VALUE_OUT,) if values else ()) + (_capi._SUBSTEPS_OUT,)
+        route_shape = (T, repeat, self.num_envs) if repeat != 1 or "substeps_seq" in outputs else (T, self.num_envs)
         if self.backend == "torch":
             t = self._torch
             self._bind_stream()
@@ -477,20 +484,21 @@ class VecIntersectionEnv:
                 E, N, D = self.num_envs, self.num_agents, self.obs_dim
                 for k, dtype, shape in outs:
                     if k in outputs:
-                        o[k] = t.zeros(shape(T, E, N, D), dtype=t.float32 if dtype is np.float32 else t.uint8,
-                                       device=self._out["obs"].device)
+                        tdt = t.float32 if dtype is np.float32 else t.int32 if dtype is np.int32 else t.uint8
+                        o[k] = t.zeros(shape(T, E, N, D), dtype=tdt, device=self._out["obs"].device)
             sp = None
             if spawn_route is not None:
                 sp = self._dev_tensor(spawn_route, t.int32)
-                if tuple(sp.shape) != (T, self.num_envs):
-                    raise ValueError(f"spawn_route must be [{T}][{self.num_envs}], got {tuple(sp.shape)}")
+                if tuple(sp.shape) != route_shape:
+                    raise ValueError(f"spawn_route must be {list(route_shape)}, got {tuple(sp.shape)}")
             eb = None
             if values:  # (read on the stream before the call rewrites the handle's last outputs; a fresh tensor)
                 last = {k: t.empty(self.num_envs, dtype=t.uint8, device=self._out["obs"].device)
                         for k in ("terminated", "truncated")}
                 self._h.get_outputs(last, device=True)
                 eb = last["terminated"] | last["truncated"]
-            self._h.rollout_policy(policy, T, dt, sigma, lo, hi, seed, counter, self.auto_reset, sp, out=o, device=True)
+            self._h.rollout_policy(policy, T, dt, sigma, lo, hi, seed, counter, self.auto_reset, sp, out=o, device=True,
+                                   repeat=repeat)
             r = {k: v.clone() for k, v in o.items()} if copy else dict(o)
             if values:
                 r["ended_before"] = eb
@@ -502,7 +510,8 @@ class VecIntersectionEnv:
         if values:
             last = self._h.get_outputs()
             eb = ((last["terminated"] != 0) | (last["truncated"] != 0)).astype(np.uint8)
-        self._h.rollout_policy(policy, T, dt, sigma, lo, hi, seed, counter, self.auto_reset, spawn_route, out=o)
+        self._h.rollout_policy(policy, T, dt, sigma, lo, hi, seed, counter, self.auto_reset, spawn_route, out=o,
+                               repeat=repeat)
         r = {k: v.copy() for k, v in o.items()} if copy else dict(o)
         if values:
             r["ended_before"] = eb
@@ -513,7 +522,8 @@ class VecIntersectionEnv:
         terminated_seq, truncated_seq and ended_before are used where the dict has them.  Returns
         `advantages`, `returns` and `valid` [T, E, N]; with mask_reset_steps the transitions that follow an
         env's end (this env's auto-reset steps, whose action came from the terminal observation) get
-        advantage 0 and valid 0.  Fresh arrays every call; torch: stream-ordered, no host sync."""
+        advantage 0 and valid 0.  Fresh arrays every call; torch: stream-ordered, no host sync.
+        On a `rollout(..., repeat=n)` dict the rows are decisions: gamma and lambda then apply per decision."""
         names = ("done_seq", "terminated_seq", "truncated_seq", "ended_before")
         opt = {k: traj.get(k) for k in names}
         outputs = ("advantages", "returns", "valid")
