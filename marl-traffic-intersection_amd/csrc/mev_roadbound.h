@@ -162,10 +162,28 @@ MEV_HD float road_safe_uniform(float fx, float fy, float dx, float dy, float idx
 // infinite) only arise where "never" is meant or on the short side: a NaN needs
 // a coordinate exactly on a line (0 * inf), min/max drop it, and a comparison
 // with it is false, which keeps a quadrant the ray only touches.
-MEV_HD float road_entry_safe(float fx, float fy, float dx, float dy, float idx, float idy, float iadx, float iady,
-                             float rwm, float ccen, float crf) {
-    (void)idx;
-    (void)idy;
+// REG: what the caller knows about the point, as a mask.  Bit 0 (kRegX): |rx| < rwm; bit 1 (kRegY):
+// |ry| < rwm.  3 is the centre cross, 1 a vertical arm, 2 a horizontal arm, 0 nothing: the general form.
+// With |rx| < rwm the reflected x = +-rx is never below -rwm, whatever the sign of dx: xn is false, so
+// (-,-) and (-,+) cannot be met (v4 = v2 = false, xg = true), txm is not needed, and rwm - x > 0 makes
+// txp positive (or +inf), so inx = txp without the max.  |ry| < rwm likewise; with both only (+,+) is
+// left: m1 = t1, o1 = m2 = never.  Every other operation is the general form's own, in its order and
+// with its comparison forms, so every mask's result has the general form's bits.
+//
+// The products that feed a sum (ue, ve, bq, cq, disc) are fused: the bound only has to be safe, not to
+// round like anything in the reference (the build's -ffp-contract=off is for the reference's
+// arithmetic), and a fused operation rounds once where the unfused pair rounds twice, so its error is
+// no larger and the margins above hold as argued.  cq is also reassociated, ocx^2 + (ocy^2 - rg^2) in
+// two fused steps where it was (ocx^2 + ocy^2) - rg^2: each step's rounding is at most half an ulp of a
+// value below 2^18 px^2 (< 0.01 px^2: a change of the disc's radius below 1e-4 px at rg = 86 px), far
+// inside the same margins; tests/native/roadbound_check.cpp checks the safety of exactly this code.  Not symmetric in x and y any more (ocx * a is the
+// fused product of bq, ocy * b the rounded one), which is why the arms are two cases of one body and
+// not one case called with swapped axes.
+constexpr int kRegX = 1, kRegY = 2;
+template <int REG>
+MEV_HD float road_entry_region(float fx, float fy, float dx, float dy, float iadx, float iady, float rwm, float ccen,
+                               float crf) {
+    constexpr bool xin = (REG & kRegX) != 0, yin = (REG & kRegY) != 0;
     const float never = 1.0e6f;
     const float rx = fx - 375.0f, ry = fy - 375.0f;
     const float sqm = ccen - 1.55f, rg = crf + 2.0f;
@@ -174,9 +192,9 @@ MEV_HD float road_entry_safe(float fx, float fy, float dx, float dy, float idx, 
     // the times at which x and y reach +rwm, -rwm and sqm
     const float txp = (rwm - x) * iadx, txm = (-rwm - x) * iadx, txs = (sqm - x) * iadx;
     const float typ = (rwm - y) * iady, tym = (-rwm - y) * iady, tys = (sqm - y) * iady;
-    const float inx = rb_max(txp, 0.0f), iny = rb_max(typ, 0.0f);  // x > rwm, y > rwm from then on
+    const float inx = xin ? txp : rb_max(txp, 0.0f), iny = yin ? typ : rb_max(typ, 0.0f);  // x > rwm, y > rwm from then on
     const float t1 = rb_max(inx, iny);                             // (+,+): entered at t1, never left
-    const bool xn = x < -rwm, yn = y < -rwm;
+    const bool xn = !xin && x < -rwm, yn = !yin && y < -rwm;
     const bool v4 = xn && yn;        // (-,-): from 0 until x or y reaches -rwm
     const bool v2 = xn && iny < txm;  // (-,+): from iny until x reaches -rwm
     const bool v3 = yn && inx < tym;  // (+,-): from inx until y reaches -rwm
@@ -187,11 +205,11 @@ MEV_HD float road_entry_safe(float fx, float fy, float dx, float dy, float idx, 
     const float m1 = v4 ? 0.0f : mA, o1 = v4 ? rb_min(txm, tym) : oA, m2 = v4 ? mA : mB;
     const bool xg = !(v4 || v2), yg = !(v4 || v3);
     // from its entry point e: u = |ex|, v = |ey| there
-    const float ue = fabs_f(x + a * m1), ve = fabs_f(y + b * m1);
+    const float ue = fabs_f(__builtin_fmaf(a, m1, x)), ve = fabs_f(__builtin_fmaf(b, m1, y));
     const float ocx = ue - ccen, ocy = ve - ccen;
-    const float bq = ocx * (xg ? a : -a) + ocy * (yg ? b : -b);
-    const float cq = ocx * ocx + ocy * ocy - rg * rg;
-    const float disc = bq * bq - cq;
+    const float bq = __builtin_fmaf(ocx, xg ? a : -a, ocy * (yg ? b : -b));
+    const float cq = __builtin_fmaf(ocx, ocx, __builtin_fmaf(ocy, ocy, -(rg * rg)));
+    const float disc = __builtin_fmaf(bq, bq, -cq);
     const float troot = lidar_keep(-bq - rb_sqrt(disc));
     const float tdisc = cq <= 0.0f ? 0.0f : ((disc < 0.0f || bq >= 0.0f) ? never : troot);
     const float tcorner = rb_min(m1 + tdisc, rb_min(xg ? txs : never, yg ? tys : never));
@@ -200,6 +218,29 @@ MEV_HD float road_entry_safe(float fx, float fy, float dx, float dy, float idx, 
     const float tx = ((dx > 0.0f ? 373.5f : 374.5f) - x) * iadx;  // 748.5 - fx or fx - 0.5
     const float ty = ((dy > 0.0f ? 373.5f : 374.5f) - y) * iady;
     return rb_min(road, rb_min(tx, ty));
+}
+
+MEV_HD float road_entry_safe(float fx, float fy, float dx, float dy, float idx, float idy, float iadx, float iady,
+                             float rwm, float ccen, float crf) {
+    (void)idx;
+    (void)idy;
+    return road_entry_region<0>(fx, fy, dx, dy, iadx, iady, rwm, ccen, crf);
+}
+
+// road_entry_safe from a point every lane of the wave shares (phase 1: the car centre of the pass's
+// agent; road_safe_uniform's contract): which grass quadrants a ray can start in depends on the point
+// alone.  A car on the road is in the centre cross or in an arm unless it sits on a corner fillet;
+// anything else takes the general form.  The same bits as road_entry_safe.
+MEV_HD float road_entry_safe_uniform(float fx, float fy, float dx, float dy, float idx, float idy, float iadx,
+                                     float iady, float rwm, float ccen, float crf) {
+    (void)idx;
+    (void)idy;
+    // (the very comparisons the general form makes; a NaN coordinate takes the general form)
+    const bool xin = rb_uniform(fabs_f(fx - 375.0f) < rwm), yin = rb_uniform(fabs_f(fy - 375.0f) < rwm);
+    if (xin && yin) return road_entry_region<kRegX | kRegY>(fx, fy, dx, dy, iadx, iady, rwm, ccen, crf);
+    if (xin) return road_entry_region<kRegX>(fx, fy, dx, dy, iadx, iady, rwm, ccen, crf);
+    if (yin) return road_entry_region<kRegY>(fx, fy, dx, dy, iadx, iady, rwm, ccen, crf);
+    return road_entry_region<0>(fx, fy, dx, dy, iadx, iady, rwm, ccen, crf);
 }
 
 }  // namespace mev
