@@ -860,6 +860,66 @@ typedef struct {
 } mev_rollout_repeat_args;
 int mev_rollout_policy_repeat(mev_handle* h, const mev_rollout_repeat_args* args);
 
+/* mev_rollout_policies: a policy per agent slot in one rollout -- self-play against frozen copies, a population
+ * with a policy per env, cross-play of two checkpoints, independent learners.  It is mev_rollout_policy_repeat's
+ * defining loop (above) with one line changed: agent slot (e, i) is driven by policies[assign[e][i]],
+ *
+ *   a_t[e][i], mu_t[e][i] = policy_p(obs_t[e][i]),  p = assign[e][i]       (the stated FMA chains, that policy's own layers)
+ *   action[k] = fminf(fmaxf(sigma ? mu[k] + sigma[p][k] * eps[k] : mu[k], lo[k]), hi[k])    (multiply, then add)
+ *   value_seq[t][e][i] = V_p(obs_t[e][i])                                   (if asked; row T included)
+ *
+ * The noise word is unchanged -- counter (lo32, hi32, e * 64 + i, t), t the decision -- and does not depend on p.
+ * Everything else is mev_rollout_policy_repeat's, word for word: `repeat` with its summed, latched rows and
+ * substeps_seq, spawn_route as [T][repeat][E], the Philox counter advancing by T * n, auto-reset at a decision's first
+ * sub-step, every element of every given *_seq array written, the handle left exactly where T mev_step_repeat calls
+ * would leave it.  The assignment belongs to the SLOT (e, i): it holds for the whole call, across respawns and
+ * auto-resets.  The policies may differ in depth and widths (one or two hidden layers, 1..128 units each).  With
+ * count == 1 and assign all zero every output equals mev_rollout_policy_repeat's bit for bit; with repeat == 1 also
+ * the plain calls'.
+ * `policies` and `sigma` are ALWAYS host arrays, read before the call returns (sigma by value, like dt; NULL: no
+ * noise word is drawn); `assign` is a host or a device array as base.rollout.flags says and is staged like every
+ * host-mode array.  Host pointers: an assign entry >= count -> MEV_E_RANGE, nothing changed; synchronous.  Device
+ * pointers: such an entry is read as count - 1; not synchronous.  Supported shapes, the step-server stop and "not
+ * counted by mev_kernel_timing" as mev_rollout_policy; the LDS scratch is sized by the largest sum of hidden widths
+ * among the listed policies.
+ * Errors (MEV_E_INVALID, the handle untouched): everything mev_rollout_policy_repeat refuses; a non-NULL
+ * base.rollout.policy or base.rollout.sigma; null policies or assign; count outside 1..MEV_MAX_ROLLOUT_POLICIES; a
+ * null entry, an entry of another handle or one whose in_dim != obs_dim; a non-finite sigma value; value_seq given
+ * while a listed policy has no value head; a shape for which mev_get_rollout_row is negative.
+ * How it runs: k_rollout's flat frame-skip loop with one more flag of the instantiation.  Per group
+ * of up to 8 agents the observation rows are staged in LDS once; then, for each policy that at least one agent of
+ * the group has (a wave-uniform test), the single-policy chains run for the whole group with that policy's layers
+ * and only its own agents' lanes store.  The cost is one policy pass per DISTINCT policy present in a group: a
+ * per-env assignment costs what one policy costs.
+ * Estimated beforehand (supposed, not measured): one policy pass of 31-33 us per distinct policy present in an env on
+ * top of the step, so that eight policies in one env might lose.  Measured (python tools/bench_rollout_multi.py ->
+ * profiles/rollout_multi_sweep.json; tools/bench_rollout_repeat.py's method: device pointers,
+ * auto-reset, every *_seq output plus value_seq and substeps_seq, medians of five alternated blocks (min-max)), 4096
+ * envs x 8 agents x 64 beams, policies 95-64-64-2 with value heads, T = 16 decisions, (a) the call against (b) what a
+ * user runs today for the same semantics -- an eager torch forward of each of the P policies over all rows, a gather
+ * by assign, a clamp and mev_step_repeat per decision into the same tensors -- and (c) mev_rollout_policy_repeat with
+ * one policy (orientation only), ms per call at n = 1 / n = 4:
+ *   P = 1:                      (a) 0.819 / 1.506  (b) 2.272 / 2.333   (c) 0.795 / 1.437
+ *   P = 2, 4 / 4 in every env:  (a) 1.083 / 1.749  (b) 3.798 / 3.823   (c) 0.808 / 1.443
+ *   P = 2 by env parity:        (a) 0.819 / 1.509  (b) 4.088 / 4.027   (c) 0.807 / 1.447
+ *   P = 8, one per agent:       (a) 2.738 / 3.356  (b) 13.102 / 13.166 (c) 0.807 / 1.461
+ * and 64 envs, 4 / 4, n = 4: (a) 1.135 (b) 3.814 -- (a) below (b) by more than both blocks' spreads at all nine
+ * points, no loss.  A further distinct policy in an env costs 17-19 us per decision, not 31-33: the rows are staged
+ * once per group (supposed from the structure, not profiled).  The existing calls are unchanged: their kernels keep
+ * the parent's register figures to the byte, and mev_rollout_policy_repeat's first row took 0.781 / 0.781 ms on this
+ * build against 0.780 / 0.780 ms on the commit before it in one session (a block's spread is 0.002-0.003 ms). */
+#define MEV_MAX_ROLLOUT_POLICIES 8
+typedef struct {
+    mev_rollout_repeat_args base;       /* exactly as mev_rollout_policy_repeat, except:
+                                           base.rollout.policy and base.rollout.sigma must be NULL */
+    const mev_policy* const* policies;  /* [count]; ALWAYS a host array, read before the call returns */
+    int32_t count;                      /* P, 1..MEV_MAX_ROLLOUT_POLICIES */
+    const uint8_t* assign;              /* [E][N]: agent slot (e, i) is driven by policies[assign[e][i]];
+                                           host or device as base.rollout.flags says */
+    const float* sigma;                 /* optional [P][2]; ALWAYS host, by value like dt; NULL: no noise word drawn */
+} mev_rollout_multi_args;
+int mev_rollout_policies(mev_handle* h, const mev_rollout_multi_args* args);
+
 /* mev_gae: generalised advantage estimation over a rollout's arrays, one reverse scan on the device.
  * THE ARITHMETIC IS THE CONTRACT: f32, multiply, then add, no FMA, per (e, i) and for t descending, with
  * c the f32 product gamma * lambda, computed once:

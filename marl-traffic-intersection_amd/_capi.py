@@ -54,7 +54,7 @@ EXPORTED = (
     "mev_pool_capture", "mev_pool_get_state", "mev_expand_plans", "mev_sample_plans", "mev_update_plans",
     "mev_sample_expand_plans", "mev_get_step_row", "mev_policy_create", "mev_policy_update", "mev_policy_destroy",
     "mev_rollout_policy", "mev_get_rollout_row", "mev_policy_set_value_head", "mev_policy_has_value_head",
-    "mev_rollout_policy_values", "mev_gae", "mev_rollout_policy_repeat",
+    "mev_rollout_policy_values", "mev_gae", "mev_rollout_policy_repeat", "mev_rollout_policies",
 )
 
 
@@ -167,6 +167,14 @@ MEV_MAX_ROLLOUT_SUBSTEPS = 4096
 
 class MevRolloutRepeatArgs(ctypes.Structure):  # mev_rollout_repeat_args
     _fields_ = [("rollout", MevRolloutArgs), ("value_seq", _vp), ("repeat", ctypes.c_int32), ("substeps_seq", _vp)]
+
+
+MEV_MAX_ROLLOUT_POLICIES = 8
+
+
+class MevRolloutMultiArgs(ctypes.Structure):  # mev_rollout_multi_args
+    _fields_ = [("base", MevRolloutRepeatArgs), ("policies", ctypes.POINTER(_vp)), ("count", ctypes.c_int32),
+                ("assign", _vp), ("sigma", ctypes.POINTER(ctypes.c_float))]
 
 
 MEV_GAE_MASK_RESET_STEPS = 0x100
@@ -310,6 +318,7 @@ def load_library(variant: str = None):
     L.mev_policy_has_value_head.argtypes = [_vp, i32p]
     L.mev_rollout_policy_values.argtypes = [_vp, ctypes.POINTER(MevRolloutValuesArgs)]
     L.mev_rollout_policy_repeat.argtypes = [_vp, ctypes.POINTER(MevRolloutRepeatArgs)]
+    L.mev_rollout_policies.argtypes = [_vp, ctypes.POINTER(MevRolloutMultiArgs)]
     L.mev_gae.argtypes = [_vp, ctypes.POINTER(MevGaeArgs)]
     L.mev_set_serve.argtypes = [_vp, ctypes.c_int32]
     L.mev_serve_stats.argtypes = [_vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64), i32p]
@@ -901,7 +910,7 @@ class Handle:
     def rollout_policy(self, policy: "Policy", T: int, dt: float = 1.0 / 60.0, sigma=None, lo=(-1.0, -1.0),
                        hi=(1.0, 1.0), seed: int = 0, counter: int = 0, auto_reset: bool = False, spawn_route=None,
                        outputs=ROLLOUT_OUTPUTS, out: Optional[dict] = None, device: bool = False, flags: int = 0,
-                       repeat: int = 1):
+                       repeat: int = 1, _multi=None):
         """Closed-loop rollout (mev_rollout_policy): T sub-steps of observe -> policy -> step in one launch,
         bit for bit the loop of the stated policy arithmetic and `step`.  sigma: None (deterministic) or
         two host floats; the noise is sample_plans' from the Philox stream (seed, counter) with the env in
@@ -924,6 +933,7 @@ class Handle:
         named = outputs if out is None or not out else out
         values = "value_seq" in named
         held = repeat != 1 or "substeps_seq" in named  # (today's calls take today's path)
+        held = held or _multi is not None  # (rollout_policies: the frame-skip call's arguments)
         out = dict(out) if out is not None else {}
         for k in out:
             if k not in shapes:
@@ -969,7 +979,12 @@ class Handle:
             ra.substeps_seq = _ptr(out.get("substeps_seq"))
             if values and ra.value_seq is None:
                 raise ValueError("value_seq is named but not given")
-            _check(self._lib.mev_rollout_policy_repeat(self._h, ctypes.byref(ra)))
+            if _multi is not None:
+                ma = MevRolloutMultiArgs()
+                ma.base, (ma.policies, ma.count, ma.assign, ma.sigma) = ra, _multi
+                _check(self._lib.mev_rollout_policies(self._h, ctypes.byref(ma)))
+            else:
+                _check(self._lib.mev_rollout_policy_repeat(self._h, ctypes.byref(ra)))
         elif values:
             va = MevRolloutValuesArgs()
             va.rollout, va.value_seq = a, _ptr(out.get("value_seq"))
@@ -977,6 +992,39 @@ class Handle:
         else:
             _check(self._lib.mev_rollout_policy(self._h, ctypes.byref(a)))
         return out
+
+    def rollout_policies(self, policies, assign, T: int, dt: float = 1.0 / 60.0, sigma=None, lo=(-1.0, -1.0),
+                         hi=(1.0, 1.0), seed: int = 0, counter: int = 0, auto_reset: bool = False, spawn_route=None,
+                         outputs=ROLLOUT_OUTPUTS, out: Optional[dict] = None, device: bool = False, flags: int = 0,
+                         repeat: int = 1):
+        """A policy per agent slot in one rollout (mev_rollout_policies): rollout_policy(..., repeat=repeat) with
+        agent slot (e, i) driven by policies[assign[e][i]] for the whole call -- that policy's own layers, sigma row
+        and value head; the noise word does not depend on the policy.  policies: 1..MEV_MAX_ROLLOUT_POLICIES Policy
+        objects of this handle (depths and widths may differ); assign: uint8 [E][N] (a device tensor with
+        device=True, where an entry >= len(policies) is read as the last policy; on the host it raises
+        IndexRangeError); sigma: None or host floats [P][2].  Returns the same dict as rollout_policy; "value_seq"
+        (every listed policy then needs a value head) and "substeps_seq" are available the same way.  One policy
+        and assign all zero give rollout_policy's bits."""
+        policies = list(policies) if policies is not None else None
+        count = len(policies) if policies is not None else 0
+        table = None
+        if policies is not None:
+            table = (_vp * max(count, 1))(*[p._p if p is not None else None for p in policies])
+        if not device and assign is not None:
+            assign = np.ascontiguousarray(assign)
+            if assign.dtype != np.uint8 or assign.shape != (self.E, self.N):
+                raise ValueError(f"assign must be uint8 {[self.E, self.N]}, got {assign.dtype} {list(assign.shape)}")
+        sig = None
+        if sigma is not None:
+            flat = np.asarray(sigma, np.float32).reshape(-1)
+            if flat.size != 2 * count:
+                raise ValueError(f"sigma must be [{count}][2]")
+            sig = (ctypes.c_float * max(flat.size, 1))(*flat.tolist())
+        multi = (ctypes.cast(table, ctypes.POINTER(_vp)) if table is not None else None, count, _ptr(assign),
+                 ctypes.cast(sig, ctypes.POINTER(ctypes.c_float)) if sig is not None else None)
+        return self.rollout_policy(None, T, dt=dt, sigma=None, lo=lo, hi=hi, seed=seed, counter=counter,
+                                   auto_reset=auto_reset, spawn_route=spawn_route, outputs=outputs, out=out,
+                                   device=device, flags=flags, repeat=repeat, _multi=multi)
 
     def gae(self, reward_seq, value_seq, done_seq=None, terminated_seq=None, truncated_seq=None, ended_before=None,
             gamma: float = 0.99, lam: float = 0.95, mask_reset_steps: bool = False,

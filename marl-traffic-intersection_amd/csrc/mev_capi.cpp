@@ -9,6 +9,7 @@
 #include <rccl/rccl.h>
 #include <string.h>
 
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <cmath>
@@ -1794,11 +1795,34 @@ int mev_get_rollout_row(const mev_handle* h, int32_t* row) {
 // rep (mev_rollout_policy_repeat, checked there; null: the two calls above): T decisions of up to rep->repeat
 // sub-steps each -- spawn_route staged as [T * n][E], the Philox counter advanced by T * n, spawn_prob once from
 // dt as mev_step_repeat computes it -- through k_rollout's REPEAT instantiations.
-static int rollout(mev_handle* h, const mev_rollout_args* a, float* value_seq, const mev_rollout_repeat_args* rep = nullptr) {
+// multi (mev_rollout_policies, checked there; a, value_seq and rep are its base's): the policy of a->policy gives
+// way to multi's table, one entry per agent slot by `assign` (staged like every array) with its own sigma row --
+// through k_rollout's MULTI instantiations, the scratch sized by the widest listed policy.
+static int rollout(mev_handle* h, const mev_rollout_args* a, float* value_seq, const mev_rollout_repeat_args* rep = nullptr,
+                   const mev_rollout_multi_args* multi = nullptr) {
     const mev_policy* pol = a->policy;
-    if (!pol) return fail(MEV_E_INVALID, "mev_rollout_policy: policy required");
-    if (pol->h != h) return fail(MEV_E_INVALID, "mev_rollout_policy: the policy belongs to another handle");
-    if (pol->net.in[0] != h->D) return fail(MEV_E_INVALID, "mev_rollout_policy: policy in_dim != obs_dim");
+    int hidden = 0;  // the hidden widths summed: the LDS scratch
+    auto hidden_of = [](const mev_policy* p) { return p->net.out[0] + (p->net.layers == 3 ? p->net.out[1] : 0); };
+    if (multi) {
+        for (int p = 0; p < multi->count; ++p) {
+            const mev_policy* q = multi->policies[p];
+            const std::string at = "mev_rollout_policies: policies[" + std::to_string(p) + "]";
+            if (!q) return fail(MEV_E_INVALID, at + " is null");
+            if (q->h != h) return fail(MEV_E_INVALID, at + " belongs to another handle");
+            if (q->net.in[0] != h->D) return fail(MEV_E_INVALID, at + ": in_dim != obs_dim");
+            if (value_seq && !q->has_value)
+                return fail(MEV_E_INVALID, at + " has no value head (mev_policy_set_value_head)");
+            for (int k = 0; k < 2; ++k)
+                if (multi->sigma && !std::isfinite(multi->sigma[2 * p + k]))
+                    return fail(MEV_E_INVALID, "mev_rollout_policies: sigma must be finite");
+            hidden = std::max(hidden, hidden_of(q));
+        }
+    } else {
+        if (!pol) return fail(MEV_E_INVALID, "mev_rollout_policy: policy required");
+        if (pol->h != h) return fail(MEV_E_INVALID, "mev_rollout_policy: the policy belongs to another handle");
+        if (pol->net.in[0] != h->D) return fail(MEV_E_INVALID, "mev_rollout_policy: policy in_dim != obs_dim");
+        hidden = hidden_of(pol);
+    }
     if (a->length < 1 || a->length > MEV_MAX_ROLLOUT)
         return fail(MEV_E_INVALID, "length must be in 1.." + std::to_string(MEV_MAX_ROLLOUT));
     if (a->flags & MEV_GATHER_TO_ROOT) return fail(MEV_E_INVALID, "mev_rollout_policy does not gather (MEV_GATHER_TO_ROOT)");
@@ -1808,11 +1832,17 @@ static int rollout(mev_handle* h, const mev_rollout_args* a, float* value_seq, c
             return fail(MEV_E_INVALID, "mev_rollout_policy: lo / hi must be finite with lo <= hi");
         if (a->sigma && !std::isfinite(a->sigma[k])) return fail(MEV_E_INVALID, "mev_rollout_policy: sigma must be finite");
     }
-    const int hidden = pol->net.out[0] + (pol->net.layers == 3 ? pol->net.out[1] : 0);
     const mev::RolloutPlan rp = rollout_plan(h, hidden);
     if (rp.row < 0)
         return fail(MEV_E_INVALID, "mev_rollout_policy: unsupported shape (the fused step kernel must hold the env, and obs_dim <= 31 + " +
                                        std::to_string(MEV_POLICY_MAX_WIDTH) + ")");
+    const bool dev = (a->flags & MEV_DEVICE_PTRS) != 0;
+    const size_t E = size_t(h->cfg.num_envs), EN = E * size_t(h->cfg.num_agents), D = size_t(h->D);
+    if (multi && !dev)  // (device pointers: the kernel reads an entry >= count as count - 1)
+        for (size_t g = 0; g < EN; ++g)
+            if (multi->assign[g] >= multi->count)
+                return fail(MEV_E_RANGE, "assign[" + std::to_string(g) + "] = " + std::to_string(multi->assign[g]) +
+                                             " is outside [0, " + std::to_string(multi->count) + ")");
     HIP_TRY(hipSetDevice(h->cfg.device));
     if (int r = serve_stop(h)) return r;  // (the server holds the stream)
     if (h->last.lidar_u8 || !h->last.obs)  // a compact gather row: obs_0 decoded into the handle's buffers
@@ -1823,22 +1853,28 @@ static int rollout(mev_handle* h, const mev_rollout_args* a, float* value_seq, c
         memcpy(&h->sp_dev, &h->sp, sizeof(mev::SimParams));
         h->sp_valid = true;
     }
-    const bool dev = (a->flags & MEV_DEVICE_PTRS) != 0;
     const int T = a->length;
     const size_t n = rep ? size_t(rep->repeat) : 1;  // sub-steps per row
-    const size_t E = size_t(h->cfg.num_envs), EN = E * size_t(h->cfg.num_agents), D = size_t(h->D);
-    mev::RolloutRepeatArgs ra{};
+    mev::RolloutMultiArgs ra{};  // (the calls without `multi` launch with its bases: what they passed before)
     ra.repeat = int32_t(n);
     ra.in.dt = a->dt;
     ra.in.spawn_prob = spawn_prob(h, a->dt);
     ra.in.auto_reset = (a->flags & MEV_AUTO_RESET) ? 1 : 0;
     ra.in.rng_counter = h->rng_counter;  // sub-step t: + t (k_rollout; REPEAT: sub-step s of decision t + t n + s)
-    ra.net = pol->net;
+    if (multi) {
+        ra.P = multi->count;
+        for (int p = 0; p < multi->count; ++p) {
+            ra.nets[p] = multi->policies[p]->net;
+            for (int k = 0; k < 2; ++k) ra.sigmas[p][k] = multi->sigma ? multi->sigma[2 * p + k] : 0.0f;
+        }
+    } else {
+        ra.net = pol->net;
+    }
     ra.T = T;
     ra.pol_off = rp.pol_off;
     ra.obs0 = h->last.obs;
     ra.act_scratch = h->d_actions;
-    ra.noisy = a->sigma ? 1 : 0;
+    ra.noisy = (multi ? multi->sigma : a->sigma) ? 1 : 0;
     for (int k = 0; k < 2; ++k) {
         ra.sigma[k] = a->sigma ? a->sigma[k] : 0.0f;
         ra.lo[k] = a->lo[k];
@@ -1850,6 +1886,7 @@ static int rollout(mev_handle* h, const mev_rollout_args* a, float* value_seq, c
     ra.ctr_hi = uint32_t(a->noise_counter >> 32);
     Stage st(h, dev);
     st.in(&ra.in.spawn_route, a->spawn_route, size_t(T) * n * E);
+    st.in(&ra.assign, multi ? multi->assign : nullptr, EN);
     st.out(&ra.obs_seq, a->obs_seq, size_t(T) * EN * D);
     st.out(&ra.actions_seq, a->actions_seq, size_t(T) * EN * 2);
     st.out(&ra.mean_seq, a->mean_seq, size_t(T) * EN * 2);
@@ -1863,7 +1900,8 @@ static int rollout(mev_handle* h, const mev_rollout_args* a, float* value_seq, c
     if (int r = st.upload()) return r;
     h->rng_counter += uint64_t(T) * uint64_t(n);
     h->deal_valid = false;  // NPC counts change outside the dealt step: the deal restarts
-    if (rep) HIP_TRY(mev::launch_rollout_repeat(h->sp, h->d_sp, rp, ra, h->internal, h->stream));
+    if (multi) HIP_TRY(mev::launch_rollout_multi(h->sp, h->d_sp, rp, ra, h->internal, h->stream));
+    else if (rep) HIP_TRY(mev::launch_rollout_repeat(h->sp, h->d_sp, rp, ra, h->internal, h->stream));
     else HIP_TRY(mev::launch_rollout(h->sp, h->d_sp, rp, ra, h->internal, h->stream));
     // the last outputs: row T - 1.  Device pointers: tracked where the caller's arrays hold them, as after
     // mev_step.  Host pointers: the rows live in the staging block, so they are copied into the handle's buffers.
@@ -1909,6 +1947,23 @@ int mev_rollout_policy_repeat(mev_handle* h, const mev_rollout_repeat_args* ra) 
     if (ra->value_seq && ra->rollout.policy && !ra->rollout.policy->has_value)
         return fail(MEV_E_INVALID, "mev_rollout_policy_repeat: the policy has no value head (mev_policy_set_value_head)");
     return rollout(h, &ra->rollout, ra->value_seq, ra);
+}
+
+// mev_rollout_policies: mev_rollout_policy_repeat with a policy per agent slot (rollout()'s `multi`)
+int mev_rollout_policies(mev_handle* h, const mev_rollout_multi_args* ma) {
+    static_assert(mev::kMaxRolloutPolicies == MEV_MAX_ROLLOUT_POLICIES, "the kernel's by-value policy table");
+    if (!h || !ma) return fail(MEV_E_INVALID, "null argument");
+    const mev_rollout_repeat_args* ra = &ma->base;
+    if (ra->rollout.policy || ra->rollout.sigma)
+        return fail(MEV_E_INVALID, "mev_rollout_policies: base.rollout.policy and base.rollout.sigma must be NULL");
+    if (!ma->policies || !ma->assign) return fail(MEV_E_INVALID, "mev_rollout_policies: policies and assign required");
+    if (ma->count < 1 || ma->count > MEV_MAX_ROLLOUT_POLICIES)
+        return fail(MEV_E_INVALID, "count must be in 1.." + std::to_string(MEV_MAX_ROLLOUT_POLICIES));
+    if (ra->repeat < 1 || ra->repeat > MEV_MAX_REPEAT)
+        return fail(MEV_E_INVALID, "repeat must be in 1.." + std::to_string(MEV_MAX_REPEAT));
+    if (int64_t(ra->rollout.length) * int64_t(ra->repeat) > MEV_MAX_ROLLOUT_SUBSTEPS)
+        return fail(MEV_E_INVALID, "length * repeat must be at most " + std::to_string(MEV_MAX_ROLLOUT_SUBSTEPS));
+    return rollout(h, &ra->rollout, ra->value_seq, ra, ma);
 }
 
 // mev_gae (include/marlenv.h): k_gae's reverse scan.  Reads and writes its arguments only; host pointers go

@@ -451,6 +451,20 @@ struct RolloutRepeatArgs : RolloutArgs {
 };
 hipError_t launch_rollout_repeat(const SimParams& p, const SimParams* dp, const RolloutPlan& rp,
                                  const RolloutRepeatArgs& ra, const Outputs& out, hipStream_t s);
+// mev_rollout_policies (k_rollout's MULTI instantiations, on the REPEAT loop): agent slot (e, i) is driven by
+// nets[assign[e][i]] for the whole call -- an entry above P - 1 is read as P - 1 -- with that policy's sigma row
+// and value head.  The base's `net` and `sigma` are not read; `noisy` says whether sigma was given.  rp's LDS
+// holds the largest sum of hidden widths among the P nets.  A struct of its own on top of RolloutRepeatArgs,
+// as that one is on RolloutArgs: the other instantiations' kernel argument segments are what they were.
+constexpr int kMaxRolloutPolicies = 8;  // == MEV_MAX_ROLLOUT_POLICIES
+struct RolloutMultiArgs : RolloutRepeatArgs {
+    PolicyNet nets[kMaxRolloutPolicies];  // [P] used
+    int32_t P;                            // 1..kMaxRolloutPolicies
+    const uint8_t* assign;                // [E][N]
+    float sigmas[kMaxRolloutPolicies][2];
+};
+hipError_t launch_rollout_multi(const SimParams& p, const SimParams* dp, const RolloutPlan& rp,
+                                const RolloutMultiArgs& ra, const Outputs& out, hipStream_t s);
 
 // mev_gae (k_gae): the reverse scan of mev_gae.h's gae_step over T rows per (e, i).  c = gamma * lambda in f32.
 struct GaeArgs {

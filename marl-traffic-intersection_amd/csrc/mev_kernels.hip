@@ -4382,6 +4382,127 @@ __device__ __forceinline__ void policy_phase(const RolloutArgs& ra, const float*
     }
 }
 
+// mev_rollout_policies: the policy phase with a policy per agent slot.  policy_phase above is left as it
+// stands, statement for statement -- routing the single-policy call through a shared helper was tried, twice,
+// and moved the register allocation of the existing k_rollout instantiations (the compile-time REPEAT row with
+// VALUE: 105 -> 123 spilt VGPRs) -- so its per-group part is restated here as policy_pass, taking the net, the
+// sigma row and a per-lane `mine`: the same chains with the same operands in the same order, and only the
+// lanes with `mine` store.
+template <bool VALUE>
+__device__ __forceinline__ void policy_pass(const RolloutMultiArgs& ra, const PolicyNet& net, const float* sigma,
+                                            const bool mine, const float* xs, float* h1, const int a0, const int G,
+                                            float* act_row, float* mean_row, float* value_row, const bool step,
+                                            const int e, const int N, const int t, const int lane) {
+    constexpr int U = kPolicyAhead;
+    const int L = net.layers;
+    float* h2 = h1 + (size_t)net.out[0] * kPolicyGroup;   // [out[1]][8] (three layers)
+    policy_hidden(gmem(net.wt[0]), net.in[0], net.out[0], net.ld[0], xs, h1, lane);
+    wave_lds_sync();
+    const float* hl = h1;
+    if (L == 3) {
+        policy_hidden(gmem(net.wt[1]), net.in[1], net.out[1], net.ld[1], h1, h2, lane);
+        wave_lds_sync();
+        hl = h2;
+    }
+    const int a = VALUE ? lane >> 2 : lane >> 1, c = VALUE ? (lane & 3) < 2 ? lane & 3 : 2 : lane & 1;
+    const int ck = c & 1;  // (the component whose sigma and bounds a lane reads: the value lanes use none of it)
+    const bool on = a < G && mine;
+    const int al = a < G ? a : 0;
+    const __attribute__((address_space(1))) float* wl = gmem(net.wt[L - 1]);
+    const int in_w = net.in[L - 1], ldl = net.ld[L - 1];
+    float mu = ldu(wl, (uint32_t)(in_w * ldl + c));
+    float wc[U], wn[U];
+    policy_weights(wc, wl, 0, in_w, ldl, (uint32_t)c);
+    for (int k0 = 0; k0 < in_w; k0 += U) {
+        const bool more = k0 + U < in_w;
+        if (more) policy_weights(wn, wl, k0 + U, in_w, ldl, (uint32_t)c);
+        __builtin_amdgcn_sched_barrier(0);
+        float hv[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) hv[u] = hl[(k0 + u < in_w ? k0 + u : in_w - 1) * kPolicyGroup + al];
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+            if (k0 + u < in_w) mu = __builtin_fmaf(wc[u], hv[u], mu);
+        __builtin_amdgcn_sched_barrier(0);
+        if (more) {
+#pragma unroll
+            for (int u = 0; u < U; ++u) wc[u] = wn[u];
+        }
+    }
+    const int i = a0 + al;
+    float x = mu;
+    if (ra.noisy && (!VALUE || step)) {
+        uint32_t w[4];
+        philox4(ra.ctr_lo, ra.ctr_hi, (uint32_t)e * 64u + (uint32_t)i, (uint32_t)t, ra.seed_lo, ra.seed_hi, w);
+        const uint32_t w0 = ck ? w[2] : w[0], w1 = ck ? w[3] : w[1];
+        const uint32_t bs = __builtin_amdgcn_sad_u8(w1, 0u, __builtin_amdgcn_sad_u8(w0, 0u, 0u));
+        const float eps = ((float)bs - 1020.0f) * 0x1.39897ep-8f;
+        x = mu + sigma[ck] * eps;  // (multiply, then add: no FMA here)
+    }
+    const float act = fminf(fmaxf(x, ra.lo[ck]), ra.hi[ck]);
+    if (on && (!VALUE || (step && (lane & 3) < 2))) {
+        const uint32_t o = 2u * (uint32_t)(e * N + i) + (uint32_t)c;
+        if (mean_row) gmem(mean_row)[o] = mu;
+        gmem(act_row)[o] = act;
+    }
+    if constexpr (VALUE)
+        if (on && (lane & 3) == 2) gmem(value_row)[(uint32_t)(e * N + i)] = mu;
+}
+
+// The policies of env e at decision t: per group of 8 agents the observation rows staged in LDS once, exactly
+// as policy_phase stages them; every output lane reads its agent's assign byte (clamped to P - 1); then for
+// p ascending, if a lane of the group has p (a ballot: wave-uniform), policy_pass runs with net p -- for all 8
+// agents -- and only the lanes whose agent has p store, with sigma row p.  A policy that no agent of the group
+// has costs one ballot.  h1 / h2 are reused: a wave_lds_sync() between one policy's output layer and the next
+// one's hidden layers.  The table index p is the loop's: within [0, P) whatever `assign` holds.
+template <bool VALUE>
+__device__ __forceinline__ void policy_phase_multi(const RolloutMultiArgs& ra, const float* obs, const int ld,
+                                                   float* act_row, float* mean_row, float* value_row, const bool step,
+                                                   const int e, const int N, const int D, const int t, float* scratch,
+                                                   const int lane) {
+    constexpr int kCols = (kPolicyObsHead + kPolicyMaxWidth + WAVE - 1) / WAVE;  // columns per lane
+    float* xs = scratch;                                  // [D][8]
+    float* h1 = xs + (size_t)D * kPolicyGroup;            // [out[0]][8]
+    for (int a0 = 0; a0 < N; a0 += kPolicyGroup) {
+        const int G = N - a0 < kPolicyGroup ? N - a0 : kPolicyGroup;
+        if (a0 > 0) wave_lds_sync();  // (the previous group's chains have read their rows)
+        float v[kCols][kPolicyGroup];
+#pragma unroll
+        for (int a = 0; a < kPolicyGroup; ++a) {
+            const int ar = a < G ? a : G - 1;  // (a row the group does not have: its last one again, never used)
+            const __attribute__((address_space(1))) float* row = gmem(obs + ((size_t)e * N + a0 + ar) * ld);
+#pragma unroll
+            for (int q = 0; q < kCols; ++q) {
+                const int c = lane + q * WAVE;
+                v[q][a] = ldu(row, (uint32_t)(c < D ? c : D - 1));
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int q = 0; q < kCols; ++q) {
+            const int c = lane + q * WAVE;
+            if (c < D) {
+                *reinterpret_cast<float4*>(xs + c * kPolicyGroup) = make_float4(v[q][0], v[q][1], v[q][2], v[q][3]);
+                *reinterpret_cast<float4*>(xs + c * kPolicyGroup + 4) = make_float4(v[q][4], v[q][5], v[q][6], v[q][7]);
+            }
+        }
+        wave_lds_sync();
+        const int P = ra.P;
+        const int a = VALUE ? lane >> 2 : lane >> 1;  // the output lane's agent, as policy_pass has it
+        const bool on = a < G;
+        const int ap = (int)ldu(gmem(ra.assign), (uint32_t)(e * N + a0 + (on ? a : 0)));
+        const int pl = ap < P ? ap : P - 1;
+        bool again = false;  // (wave-uniform) a policy has run on this group: its h1 / h2 are still being read
+        for (int p = 0; p < P; ++p) {
+            if (ballot(on && pl == p) == 0) continue;  // no agent of the group has p
+            if (again) wave_lds_sync();
+            again = true;
+            policy_pass<VALUE>(ra, ra.nets[p], ra.sigmas[p], pl == p, xs, h1, a0, G, act_row, mean_row, value_row, step,
+                               e, N, t, lane);
+        }
+    }
+}
+
 // P1 / NC: the beams and agents per env at compile time, as k_step's (the row's key, mev_plan.h)
 // VALUE: mev_rollout_policy_values -- row t of value_seq from the policy phase of sub-step t, and after the
 // last sub-step one more policy phase on the rows it wrote (hidden layers and the value chain, no step) for
@@ -4403,11 +4524,16 @@ __device__ __forceinline__ void policy_phase(const RolloutArgs& ra, const float*
 // decision of ONE sub-step took 74 us where the plain call's sub-step takes 53.
 // The argument struct grows by a derived type (RolloutRepeatArgs) for REPEAT alone, and the plain call's loop
 // below is untouched.
-template <bool REPEAT>
-using RolloutKernArgs = typename std::conditional<REPEAT, RolloutRepeatArgs, RolloutArgs>::type;
-template <bool TRAFFIC, bool TAB, int NM, int KM, int RP1, int RNC, bool VALUE, bool REPEAT = false>
-__global__ __launch_bounds__(WAVE, 4) void k_rollout(const SimParams* __restrict__ pp, RolloutKernArgs<REPEAT> ra,
+// MULTI (mev_rollout_policies): the REPEAT loop with policy_phase_multi in policy_phase's place -- a policy per
+// agent slot from the table of RolloutMultiArgs, a further derived type -- and nothing else changed: repeat == 1 through the flat
+// loop is the plain call's bits (3.2l), so there is no MULTI form of the plain loop.
+template <bool REPEAT, bool MULTI>
+using RolloutKernArgs =
+    typename std::conditional<MULTI, RolloutMultiArgs, typename std::conditional<REPEAT, RolloutRepeatArgs, RolloutArgs>::type>::type;
+template <bool TRAFFIC, bool TAB, int NM, int KM, int RP1, int RNC, bool VALUE, bool REPEAT = false, bool MULTI = false>
+__global__ __launch_bounds__(WAVE, 4) void k_rollout(const SimParams* __restrict__ pp, RolloutKernArgs<REPEAT, MULTI> ra,
                                                      Outputs out0) {
+    static_assert(!MULTI || REPEAT, "a policy per agent slot: the flat loop only");
     constexpr int PK = 1;
     constexpr bool SPLIT = false, ESPLIT = false, WC = false;
     constexpr int P1 = RP1, NC = RNC;
@@ -4439,8 +4565,12 @@ __global__ __launch_bounds__(WAVE, 4) void k_rollout(const SimParams* __restrict
                 // the actions the policy writes are read back by this wave's own lanes in the body (the fences)
                 float* mean_row = ra.mean_seq ? ra.mean_seq + (size_t)t * EN * 2 : nullptr;
                 __builtin_amdgcn_s_setprio(kPrioCars);
-                policy_phase<VALUE>(ra, obs, obs_ld, act_row, mean_row, VALUE ? ra.value_seq + (size_t)t * EN : nullptr,
-                                    !VALUE || t < ra.T, env, N, D, t, scratch, lane);
+                if constexpr (MULTI)
+                    policy_phase_multi<VALUE>(ra, obs, obs_ld, act_row, mean_row, VALUE ? ra.value_seq + (size_t)t * EN : nullptr,
+                                              !VALUE || t < ra.T, env, N, D, t, scratch, lane);
+                else
+                    policy_phase<VALUE>(ra, obs, obs_ld, act_row, mean_row, VALUE ? ra.value_seq + (size_t)t * EN : nullptr,
+                                        !VALUE || t < ra.T, env, N, D, t, scratch, lane);
                 if (VALUE && t == ra.T) break;  // (the bootstrap row: no sub-step follows)
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
                 __builtin_amdgcn_wave_barrier();
@@ -4807,6 +4937,27 @@ hipError_t launch_rollout_repeat(const SimParams& p, const SimParams* dp, const 
                                  const RolloutRepeatArgs& ra, const Outputs& out, hipStream_t s) {
     if (rp.row < 0 || rp.row >= kRolloutRows || ra.T < 1 || ra.repeat < 1) return hipErrorInvalidValue;
     hipLaunchKernelGGL(kRolloutRepeatFns[rp.row][!p.dist_tab][ra.value_seq != nullptr], dim3(rp.grid), dim3(rp.block), rp.lds,
+                       s, dp, ra, out);
+    return hipGetLastError();
+}
+
+// ... and those with MULTI, on the REPEAT loop: kRolloutMultiFns[row][!TAB][VALUE]
+using RolloutMultiFn = void (*)(const SimParams*, RolloutMultiArgs, Outputs);
+#define MEV_ROLLOUT_MULTI_FNS(T, NM, KM, P1, NC)                                                                      \
+    {{k_rollout<T, true, NM, KM, P1, NC, false, true, true>, k_rollout<T, true, NM, KM, P1, NC, true, true, true>},   \
+     {k_rollout<T, false, NM, KM, P1, NC, false, true, true>, k_rollout<T, false, NM, KM, P1, NC, true, true, true>}},
+static const RolloutMultiFn kRolloutMultiFns[][2][2] = {MEV_ROLLOUT_KERNELS(MEV_ROLLOUT_MULTI_FNS)};
+#undef MEV_ROLLOUT_MULTI_FNS
+static_assert(sizeof kRolloutMultiFns / sizeof kRolloutMultiFns[0] == kRolloutRows, "one kernel pair per rollout row");
+static_assert(std::is_base_of<RolloutRepeatArgs, RolloutMultiArgs>::value && std::is_trivially_copyable<RolloutMultiArgs>::value,
+              "RolloutMultiArgs: RolloutRepeatArgs, then the policy table");
+
+hipError_t launch_rollout_multi(const SimParams& p, const SimParams* dp, const RolloutPlan& rp,
+                                const RolloutMultiArgs& ra, const Outputs& out, hipStream_t s) {
+    if (rp.row < 0 || rp.row >= kRolloutRows || ra.T < 1 || ra.repeat < 1 || ra.P < 1 || ra.P > kMaxRolloutPolicies ||
+        !ra.assign)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(kRolloutMultiFns[rp.row][!p.dist_tab][ra.value_seq != nullptr], dim3(rp.grid), dim3(rp.block), rp.lds,
                        s, dp, ra, out);
     return hipGetLastError();
 }

@@ -454,7 +454,8 @@ class VecIntersectionEnv:
         return pol
 
     def rollout(self, policy, T: int, dt: float = 1.0 / 60.0, sigma=None, lo=(-1.0, -1.0), hi=(1.0, 1.0), seed: int = 0,
-                counter: int = 0, spawn_route=None, outputs=_capi.ROLLOUT_OUTPUTS, copy: bool = False, repeat: int = 1):
+                counter: int = 0, spawn_route=None, outputs=_capi.ROLLOUT_OUTPUTS, copy: bool = False, repeat: int = 1,
+                assign=None):
         """T steps of observe -> policy -> step in one launch (Handle.rollout_policy), auto-reset as this env
         was made: a dict of obs_seq [T, E, N, obs_dim] (the observation after each sub-step), actions_seq,
         mean_seq [T, E, N, 2], reward_seq, done_seq, status_seq [T, E, N], terminated_seq, truncated_seq
@@ -469,13 +470,39 @@ class VecIntersectionEnv:
         stopping at its end; every row is a decision's, spawn_route is [T, repeat, E], and "substeps_seq"
         among the outputs gives the sub-steps each decision ran [T, E] (int32).  `repeat` does NOT default to
         the constructor's frame_skip -- this call never repeated -- so pass repeat=env.frame_skip to roll out
-        as `step` steps.  `gae` on such a dict applies gamma and lambda per decision."""
+        as `step` steps.  `gae` on such a dict applies gamma and lambda per decision.
+        A policy per agent slot (Handle.rollout_policies): `policy` a list or tuple of up to 8 policies of
+        `make_policy` and `assign` uint8 [E, N], or [N] for the same seats in every env -- slot (e, i) is driven by
+        policy[assign[e, i]] for the whole call, across respawns and auto-resets; sigma is then None or [P, 2], a
+        row per policy, "value_seq" needs a value head on every listed policy, and spawn_route is
+        [T, repeat, E].  `gae` takes the dict as it is; mask the loss to the learner's slots (assign == its index)."""
         T, repeat = int(T), int(repeat)
+        multi = isinstance(policy, (list, tuple))
+        if multi != (assign is not None):
+            raise ValueError("a list or tuple of policies goes with `assign`, a single policy without it")
         key = (T, tuple(outputs), "rollout")
         o = self._out_eval.get(key)
         values = "value_seq" in outputs
         outs = _capi._ROLLOUT_OUTS + ((_capi._VALUE_OUT,) if values else ()) + (_capi._SUBSTEPS_OUT,)
-        route_shape = (T, repeat, self.num_envs) if repeat != 1 or "substeps_seq" in outputs else (T, self.num_envs)
+        held = repeat != 1 or "substeps_seq" in outputs or multi
+        route_shape = (T, repeat, self.num_envs) if held else (T, self.num_envs)
+
+        def call(route, **kw):
+            if not multi:
+                return self._h.rollout_policy(policy, T, dt, sigma, lo, hi, seed, counter, self.auto_reset, route,
+                                              repeat=repeat, **kw)
+            if self.backend == "torch":
+                a = self._dev_tensor(assign, self._torch.uint8)
+                a = a.expand(self.num_envs, self.num_agents).contiguous() if a.dim() == 1 else a
+                if tuple(a.shape) != (self.num_envs, self.num_agents):
+                    raise ValueError(f"assign must be [E, N] or [N], got {tuple(a.shape)}")
+            else:
+                a = np.asarray(assign)
+                a = np.broadcast_to(a, (self.num_envs, self.num_agents)) if a.ndim == 1 else a
+                a = np.ascontiguousarray(a, np.uint8)
+            return self._h.rollout_policies(policy, a, T, dt, sigma, lo, hi, seed, counter, self.auto_reset, route,
+                                            repeat=repeat, **kw)
+
         if self.backend == "torch":
             t = self._torch
             self._bind_stream()
@@ -497,8 +524,7 @@ class VecIntersectionEnv:
                         for k in ("terminated", "truncated")}
                 self._h.get_outputs(last, device=True)
                 eb = last["terminated"] | last["truncated"]
-            self._h.rollout_policy(policy, T, dt, sigma, lo, hi, seed, counter, self.auto_reset, sp, out=o, device=True,
-                                   repeat=repeat)
+            call(sp, out=o, device=True)
             r = {k: v.clone() for k, v in o.items()} if copy else dict(o)
             if values:
                 r["ended_before"] = eb
@@ -510,8 +536,7 @@ class VecIntersectionEnv:
         if values:
             last = self._h.get_outputs()
             eb = ((last["terminated"] != 0) | (last["truncated"] != 0)).astype(np.uint8)
-        self._h.rollout_policy(policy, T, dt, sigma, lo, hi, seed, counter, self.auto_reset, spawn_route, out=o,
-                               repeat=repeat)
+        call(spawn_route, out=o)
         r = {k: v.copy() for k, v in o.items()} if copy else dict(o)
         if values:
             r["ended_before"] = eb

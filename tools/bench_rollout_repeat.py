@@ -73,8 +73,9 @@ def kernel_resources(lib_path):
             continue
         args = [v if k == "i" else ("true" if v == "1" else "false") for k, v in re.findall(r"L([bi])(\d+)E", t.group(2))]
         if t.group(1) == "k_rollout":
-            args = args + ["false"] * (8 - len(args))  # (a build before REPEAT: seven arguments)
-            key = "k_rollout<" + ", ".join(args[:7]) + ">" + (" REPEAT" if args[7] == "true" else "")
+            args = args + ["false"] * (9 - len(args))  # (a build before REPEAT: seven arguments; before MULTI: eight)
+            key = "k_rollout<" + ", ".join(args[:7]) + ">" + (" REPEAT" if args[7] == "true" else "") + \
+                (" MULTI" if args[8] == "true" else "")
         elif len(args) == 10 and args[:3] == ["false", "false", "8"] and args[7:] == ["64", "8", "true"]:
             key = "k_step<" + ", ".join(args) + "> (8 x 64, the world at compile time: the flagship row)"
         else:
