@@ -509,6 +509,7 @@ int mev_create(const mev_config* cfg, mev_handle** out) {
         }
     }
     h->sp.beam_cull = beam_cull_ok(rel.data(), c.lidar_rays);
+    h->sp.beams = mev::beam_model(rel.data(), c.lidar_rays);
     h->h_traffic = mev::default_traffic_routes(c.num_lanes);
     h->extend_route_hash();
 
@@ -1021,6 +1022,7 @@ int mev_set_beam_angles(mev_handle* h, const float* rel) {
     for (int b = 0; b < R; ++b)
         if (!(fabsf(rel[b]) <= 1.0e3f)) return fail(MEV_E_INVALID, "beam angles must be finite, |angle| <= 1000 rad");
     h->sp.beam_cull = beam_cull_ok(rel, R);  // (any other list: no culling, SimParams::beam_cull)
+    h->sp.beams = mev::beam_model(rel, R);   // (the step copies a changed SimParams to the device before it launches)
     HIP_TRY(hipSetDevice(h->cfg.device));
     if (int r_ = serve_stop(h)) return r_;  // (the server holds the stream)
     HIP_TRY(hipStreamSynchronize(h->stream));

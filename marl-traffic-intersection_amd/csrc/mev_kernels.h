@@ -17,6 +17,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "mev_beams.h"
 #include "mev_plan.h"
 #include "mev_refworld.h"
 
@@ -159,6 +160,8 @@ struct SimParams {
     // constant, uneven or wider than a revolution; a written Lidar.rel_angles): every beam
     // is then resolved against every candidate box -- the same probes, no culling.
     int32_t beam_cull;
+    // What the LiDAR derives from the beam offsets alone (mev_beams.h), refreshed with rel_angles.
+    BeamModel beams;
 };
 
 // The fused traffic k_step deals envs to workgroups by their NPC count: every env

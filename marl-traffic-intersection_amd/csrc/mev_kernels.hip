@@ -2779,17 +2779,17 @@ using PlanArgs = typename std::conditional<
     static_assert(std::is_base_of<BASE, T>::value && std::is_trivially_copyable<T>::value && \
                       __builtin_offsetof(T, M) == sizeof(BASE) && sizeof(T) == (SIZE),      \
                   #T ": " #BASE ", then " #M)
-static_assert(sizeof(SimParams) == 568 && sizeof(RepeatArgs) == 728 && __builtin_offsetof(RepeatArgs, p) == 0,
+static_assert(sizeof(SimParams) == 592 && sizeof(RepeatArgs) == 752 && __builtin_offsetof(RepeatArgs, p) == 0,
               "RepeatArgs: SimParams first");
-MEV_ARGS_LAYOUT(SeqArgs, RepeatArgs, rows, 1264);
-MEV_ARGS_LAYOUT(EvalArgs, SeqArgs, ev, 1312);
-MEV_ARGS_LAYOUT(LeafArgs, EvalArgs, lf, 1360);
-MEV_ARGS_LAYOUT(KeepArgs, EvalArgs, k, 1424);
-MEV_ARGS_LAYOUT(KeepLeafArgs, LeafArgs, k, 1472);
-MEV_ARGS_LAYOUT(SampleArgs, EvalArgs, m, 1384);
-MEV_ARGS_LAYOUT(SampleLeafArgs, LeafArgs, m, 1432);
-MEV_ARGS_LAYOUT(SampleKeepArgs, EvalArgs, m, 1496);
-MEV_ARGS_LAYOUT(SampleKeepLeafArgs, LeafArgs, m, 1544);
+MEV_ARGS_LAYOUT(SeqArgs, RepeatArgs, rows, 1288);
+MEV_ARGS_LAYOUT(EvalArgs, SeqArgs, ev, 1336);
+MEV_ARGS_LAYOUT(LeafArgs, EvalArgs, lf, 1384);
+MEV_ARGS_LAYOUT(KeepArgs, EvalArgs, k, 1448);
+MEV_ARGS_LAYOUT(KeepLeafArgs, LeafArgs, k, 1496);
+MEV_ARGS_LAYOUT(SampleArgs, EvalArgs, m, 1408);
+MEV_ARGS_LAYOUT(SampleLeafArgs, LeafArgs, m, 1456);
+MEV_ARGS_LAYOUT(SampleKeepArgs, EvalArgs, m, 1520);
+MEV_ARGS_LAYOUT(SampleKeepLeafArgs, LeafArgs, m, 1568);
 static_assert(__builtin_offsetof(SampleKeepArgs, k) == sizeof(SampleArgs) &&
                   __builtin_offsetof(SampleKeepLeafArgs, k) == sizeof(SampleLeafArgs),
               "KEEP with SAMPLE: KeepOuts after SampleIn");
@@ -3208,6 +3208,19 @@ struct LidarSrcLdsEnvs {
 #ifndef MEV_DENSE_ILP
 #define MEV_DENSE_ILP 2
 #endif
+// What phase 1's setup of one beam is told about its car centre: nothing (it derives the on-screen test and
+// takes the general bound), or lidar_body's agent pre-pass's wave-uniform bits -- the road region
+// (road_region_xin / _yin) and road_point_on_screen.
+struct LidarNoCentre {
+    static constexpr bool known = false;
+};
+struct LidarCentre {
+    static constexpr bool known = true;
+    bool xin, yin, on;
+};
+__device__ inline float readlane_f(float v, int l) {
+    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
+}
 // P1 = 1: R is a multiple of 64 (the dense phase-1 walk below is not compiled in); P1 = 2: R is
 // not (the dense walk for every pool, the agent-pair loop not compiled in); P1 >= 64: R = P1, a
 // compile-time beam count (64: config 3, 96: the reference's default LiDAR, 128: config 5).
@@ -3265,10 +3278,29 @@ __device__ __forceinline__ void lidar_body(const SimParams& p, const Outputs& ou
     const float crf = CORNER_RADIUS, ccen = rwf + crf;
     const float cr2p1 = crf * crf + 1.0f;
     const float rwm = rwf - 1.5f;
+    // The agent pre-pass of the one-wave kernels' agent-pair loop (PRE), lane = compacted agent: what a
+    // beam pass needs of its agent and what does not depend on the beam is fetched and decided here once --
+    // the pose (one LDS read; the passes take it with readlane, not with a read of ag[j] each) and, as
+    // three ballots, the road region of the car centre and whether its pixel is on screen: the very
+    // comparisons the general form and the off-screen test make (a NaN coordinate: both region bits 0, the
+    // general form, as before).  ag[] itself stays in LDS for phases 2 and 3.  (Not where the beam count
+    // compiles the agent-pair loop out -- P1 = 2, or a compile-time count that is no multiple of 64: those
+    // kernels keep their instructions.)
+    constexpr bool PRE = RB == 1 && PART == 0 && P1 != 2 && !(P1 >= WAVE && (P1 & (WAVE - 1)) != 0);
+    [[maybe_unused]] float4 al = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    [[maybe_unused]] unsigned long long xin_m = 0ull, yin_m = 0ull, onscr_m = 0ull;
+    if constexpr (PRE) {
+        al = ag[lane < nal ? lane : 0];
+        xin_m = ballot(road_region_xin(al.x, rwm));
+        yin_m = ballot(road_region_yin(al.y, rwm));
+        onscr_m = ballot(road_point_on_screen(al.x, al.y));
+    }
     // the reference's stop test of march probe k at (cx_, cy_) + d_k (dx_, dy_):
     // returns the beam's result (k << 1 | hit; S << 1 past the last probe) or -1
     // to go on, and the probe's real point
-    auto probe = [&](float cx_, float cy_, float dx_, float dy_, int k_, float& fx, float& fy) -> int {
+    // (kpos: the caller knows k_ > 0 -- phase 1's first probes after a jump from an on-screen car centre --
+    // and the road test drops the term)
+    auto probe_k = [&](auto kpos, float cx_, float cy_, float dx_, float dy_, int k_, float& fx, float& fy) -> int {
         const bool past = k_ >= S;
         const int kc = past ? S - 1 : k_;
         const float d = TAB ? gmem(p.dist_tab)[kc] : (float)kc * stp;
@@ -3284,20 +3316,25 @@ __device__ __forceinline__ void lidar_body(const SimParams& p, const Outputs& ou
         const float iax = fabs_f((float)(px - 375)), iay = fabs_f((float)(py - 375));
         const float qdx = iax - ccen, qdy = iay - ccen;
         const float onv = fmaxf(fminf(fminf(iax, iay) - rwf, fmaxf(iax, iay) - ccen), cr2p1 - (qdx * qdx + qdy * qdy));
-        const bool stop = off_screen | ((k_ > 0) & (onv > 0.0f));
+        bool stop;
+        if constexpr (decltype(kpos)::value) stop = off_screen | (onv > 0.0f);
+        else stop = off_screen | ((k_ > 0) & (onv > 0.0f));
         const int code = lidar_keep(stop ? ((k_ << 1) | (off_screen ? 0 : 1)) : -1);
         return past ? (S << 1) : code;
     };
     // probes k_ .. k_ + NPR - 1 in march order: the first stop wins; (fx, fy) is
     // the last probe's point
-    auto probes_n = [&](auto np, float cx_, float cy_, float dx_, float dy_, int k_, float& fx, float& fy) -> int {
+    auto probes_k = [&](auto kpos, auto np, float cx_, float cy_, float dx_, float dy_, int k_, float& fx, float& fy) -> int {
         int r = -1;
 #pragma unroll
         for (int t = 0; t < decltype(np)::value; ++t) {
-            const int c = probe(cx_, cy_, dx_, dy_, k_ + t, fx, fy);
+            const int c = probe_k(kpos, cx_, cy_, dx_, dy_, k_ + t, fx, fy);
             r = r >= 0 ? r : c;
         }
         return r;
+    };
+    auto probes_n = [&](auto np, float cx_, float cy_, float dx_, float dy_, int k_, float& fx, float& fy) -> int {
+        return probes_k(std::false_type{}, np, cx_, cy_, dx_, dy_, k_, fx, fy);
     };
     auto probes = [&](float cx_, float cy_, float dx_, float dy_, int k_, float& fx, float& fy) -> int {
         return probes_n(std::integral_constant<int, LIDAR_NPR>{}, cx_, cy_, dx_, dy_, k_, fx, fy);
@@ -3318,8 +3355,10 @@ __device__ __forceinline__ void lidar_body(const SimParams& p, const Outputs& ou
     // one beam: direction (Lidar.cpp:24-26) and the first probes; returns the
     // beam's result (>= 0) or -(next probe to test) - 1
     // (uni, wave-uniform: every lane's beam starts from the same car centre -- the
-    // wave-uniform safe bound; else a chunk holding two agents' beams)
-    auto setup = [&](const float4& a, float rel_b, auto small, float2& d, bool uni) -> int {
+    // wave-uniform safe bound; else a chunk holding two agents' beams.  Read only where RB == 0, to choose
+    // road_safe_uniform: with the entry bound a shared centre is known through pre or not used)
+    // (pre: what the agent pre-pass above knows about the car centre, LidarCentre, or LidarNoCentre)
+    auto setup = [&](const float4& a, float rel_b, auto small, float2& d, bool uni, auto pre) -> int {
         float sn, cs;
 #if defined(MEV_EXP_FASTSIN)  // timing-only (wrong results): phase 1's beam directions by the hardware sin/cos
         sn = __sinf(a.z + rel_b);
@@ -3331,17 +3370,34 @@ __device__ __forceinline__ void lidar_body(const SimParams& p, const Outputs& ou
 #endif
         const float dx = cs, dy = -sn;
         d = make_float2(dx, dy);
+        if constexpr (decltype(pre)::known) {
+            // The one-wave kernels' agent-pair loop: the car centre's road region and its on-screen test
+            // come from the pre-pass as scalars (the same bits: the pre-pass makes the very comparisons),
+            // and both are scalar branches -- the region bodies have fewer selects than the general form.
+            // (Not in the early split's LiDAR wave, where the branches measured slower: config 2 9.36 ->
+            // 9.48 us.)
+            static_assert(RB == 1 && PART == 0, "the pre-pass feeds the one-wave kernels' entry bound");
+            constexpr std::integral_constant<int, LIDAR_NPR> npr{};
+            float fx, fy;
+            if (pre.on) {
+                const float iadx = fabs_f(__builtin_amdgcn_rcpf(dx)), iady = fabs_f(__builtin_amdgcn_rcpf(dy));
+                const float safe = road_entry_safe_uniform(a.x, a.y, dx, dy, iadx, iady, rwm, ccen, crf, pre.xin, pre.yin);
+                // k1 >= 1 here (safe_steps is 0 or a positive count), so every probe from it has k > 0: the
+                // probes are instantiated without that term of the road test
+                const int k1 = 1 + safe_steps(safe, stp, inv_stp);
+                const int r = probes_k(std::true_type{}, npr, a.x, a.y, dx, dy, k1, fx, fy);
+                return r >= 0 ? r : -(k1 + LIDAR_NPR) - 1;
+            }
+            // the centre off screen: no safe stretch, from probe 0 with the full test (k1 = 0)
+            const int r = probes_n(npr, a.x, a.y, dx, dy, 0, fx, fy);
+            return r >= 0 ? r : -LIDAR_NPR - 1;
+        }
         const int px = (int)a.x, py = (int)a.y;
         const unsigned pmax = (unsigned)px > (unsigned)py ? (unsigned)px : (unsigned)py;
         const float idx = __builtin_amdgcn_rcpf(dx), idy = __builtin_amdgcn_rcpf(dy);
         float safe;
         if constexpr (RB == 1) {
-            // (uni: the car centre's road region as scalar branches, the same bits with fewer selects; not in
-            // the early split's LiDAR wave, where the branches measured slower: config 2 9.36 -> 9.48 us)
-            if (uni && PART == 0)
-                safe = road_entry_safe_uniform(a.x, a.y, dx, dy, idx, idy, fabs_f(idx), fabs_f(idy), rwm, ccen, crf);
-            else
-                safe = road_entry_safe(a.x, a.y, dx, dy, idx, idy, fabs_f(idx), fabs_f(idy), rwm, ccen, crf);
+            safe = road_entry_safe(a.x, a.y, dx, dy, idx, idy, fabs_f(idx), fabs_f(idy), rwm, ccen, crf);
         } else if (uni)
             safe = road_safe_uniform(a.x, a.y, dx, dy, idx, idy, fabs_f(idx), fabs_f(idy), rwm, ccen, crf);
         else
@@ -3360,7 +3416,7 @@ __device__ __forceinline__ void lidar_body(const SimParams& p, const Outputs& ou
             const bool vb = b < R;
             const float rel_b = b0 == 0 ? rel_c0 : (b0 == WAVE ? rel_c1 : (vb ? src.rel(b) : 0.0f));
             float2 d;
-            const int r = setup(a, rel_b, small, d, true);
+            const int r = setup(a, rel_b, small, d, true, LidarNoCentre{});
             if (vb) {
                 dir[j * R + b] = d;
                 res[j * R + b] = r >= 0 ? r : -r - 1;
@@ -3384,7 +3440,7 @@ __device__ __forceinline__ void lidar_body(const SimParams& p, const Outputs& ou
         if constexpr (PART == 2) {  // the respawned agents only
             for (unsigned long long tm = redo; tm; tm &= tm - 1ull) pass1_one(small, __builtin_ctzll(tm));
         } else if (dense) {
-            const float invRp = 1.0f / (float)R;
+            const float invRp = P1 >= WAVE ? 1.0f / (float)P1 : p.beams.inv_r;
             const int nq = nal * R;
             constexpr int DI = ILP > 1 ? MEV_DENSE_ILP : 1;
             for (int c0 = 0; c0 < nq; c0 += DI * WAVE) {
@@ -3403,7 +3459,7 @@ __device__ __forceinline__ void lidar_body(const SimParams& p, const Outputs& ou
                 float2 d[DI];
                 int r[DI];
 #pragma unroll
-                for (int u = 0; u < DI; ++u) r[u] = setup(a[u], rb[u], small, d[u], false);
+                for (int u = 0; u < DI; ++u) r[u] = setup(a[u], rb[u], small, d[u], false, LidarNoCentre{});
 #pragma unroll
                 for (int u = 0; u < DI; ++u) {
                     const bool vq = q[u] < nq;
@@ -3421,8 +3477,17 @@ __device__ __forceinline__ void lidar_body(const SimParams& p, const Outputs& ou
         for (int j = 0; j < nal; j += ILP) {
             if (PART == 0 && 4 * j >= nal) __builtin_amdgcn_s_setprio(kPrioP1B);
             float4 a[ILP];
+            LidarCentre ctr[ILP];
 #pragma unroll
-            for (int u = 0; u < ILP; ++u) a[u] = ag[j + u < nal ? j + u : j];
+            for (int u = 0; u < ILP; ++u) {
+                const int ju = j + u < nal ? j + u : j;
+                if constexpr (PRE) {  // the pass's agent from the pre-pass's lane: scalars, no LDS round trip
+                    a[u] = make_float4(readlane_f(al.x, ju), readlane_f(al.y, ju), readlane_f(al.z, ju), 0.0f);
+                    ctr[u] = {((xin_m >> ju) & 1ull) != 0ull, ((yin_m >> ju) & 1ull) != 0ull, ((onscr_m >> ju) & 1ull) != 0ull};
+                } else {
+                    a[u] = ag[ju];
+                }
+            }
             for (int b0 = 0; b0 < R; b0 += WAVE) {
                 const int b = b0 + lane;
                 const bool vb = b < R;
@@ -3430,7 +3495,10 @@ __device__ __forceinline__ void lidar_body(const SimParams& p, const Outputs& ou
                 float2 d[ILP];
                 int r[ILP];
 #pragma unroll
-                for (int u = 0; u < ILP; ++u) r[u] = setup(a[u], rel_b, small, d[u], true);
+                for (int u = 0; u < ILP; ++u) {
+                    if constexpr (PRE) r[u] = setup(a[u], rel_b, small, d[u], true, ctr[u]);
+                    else r[u] = setup(a[u], rel_b, small, d[u], true, LidarNoCentre{});
+                }
 #pragma unroll
                 for (int u = 0; u < ILP; ++u) {
                     const bool in = j + u < nal;  // wave-uniform
@@ -3449,7 +3517,8 @@ __device__ __forceinline__ void lidar_body(const SimParams& p, const Outputs& ou
     };
     // |heading| < 100 for every agent (always, unless set_state() planted a
     // wild heading): |h + rel| < 120, the range of the branch-free sincosf
-    const bool hsmall = ballot(lane < nal && !(fabs_f(ag[lane < nal ? lane : 0].z) < 100.0f)) == 0ull;
+    const float hl = PRE ? al.z : ag[lane < nal ? lane : 0].z;
+    const bool hsmall = ballot(lane < nal && !(fabs_f(hl) < 100.0f)) == 0ull;
     if (ILP > 1 && hsmall) phase1(std::true_type{});  // k_lidar: one instantiation (64 VGPRs)
     else phase1(std::false_type{});
     wave_lds_sync();
@@ -3469,7 +3538,7 @@ __device__ __forceinline__ void lidar_body(const SimParams& p, const Outputs& ou
     // over the provably safe stretch after the last one
     // (one beam per lane: measured, a second interleaved beam per lane doubles
     // the per-iteration cost while the long beams still set the trip count)
-    const float invR = 1.0f / (float)R;
+    const float invR = P1 >= WAVE ? 1.0f / (float)P1 : p.beams.inv_r;
     int next = qn < WAVE ? qn : WAVE;
     int slot = lane < qn ? (int)queue[lane] : -1;
     float cx = 0.0f, cy = 0.0f, dx = 0.0f, dy = 0.0f, idx = 0.0f, idy = 0.0f, iadx = 0.0f, iady = 0.0f;
@@ -3662,11 +3731,12 @@ __device__ __forceinline__ void lidar_body(const SimParams& p, const Outputs& ou
     // the range covers the angular span of the box's real slab (box_lo/box_hi):
     // a ray outside it never meets the slab, so none of its probes can land in
     // the box.
-    const float rel0 = src.rel(0);
+    // (rel0, dphi and what follows from them: fixed with the handle's offsets, computed where those are
+    // written -- mev_beams.h -- and not at the head of every step's phase 3)
+    const float rel0 = p.beams.rel0;
     const bool all_beams = R == 1 || !W::beam_cull(p);  // (no linear model of the offsets: SimParams::beam_cull)
-    const float dphi = R > 1 ? (src.rel(R - 1) - rel0) / (float)(R - 1) : 1.0f;
-    const float idphi = 1.0f / dphi;
-    const float period = 6.28318531f * idphi;  // beam indices per revolution
+    const float idphi = p.beams.idphi;  // 1 / dphi
+    const float period = p.beams.period;  // beam indices per revolution
     if constexpr (SEGL) {
         static_assert(std::is_same<Src, LidarSrcLds>::value, "segments by lane: one box table in the wave's LDS");
         // 3b's range arithmetic and 3c's probes: operation for operation those of the list path below

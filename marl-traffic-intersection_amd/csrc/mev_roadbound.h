@@ -231,16 +231,37 @@ MEV_HD float road_entry_safe(float fx, float fy, float dx, float dy, float idx, 
 // agent; road_safe_uniform's contract): which grass quadrants a ray can start in depends on the point
 // alone.  A car on the road is in the centre cross or in an arm unless it sits on a corner fillet;
 // anything else takes the general form.  The same bits as road_entry_safe.
-MEV_HD float road_entry_safe_uniform(float fx, float fy, float dx, float dy, float idx, float idy, float iadx,
-                                     float iady, float rwm, float ccen, float crf) {
-    (void)idx;
-    (void)idy;
-    // (the very comparisons the general form makes; a NaN coordinate takes the general form)
-    const bool xin = rb_uniform(fabs_f(fx - 375.0f) < rwm), yin = rb_uniform(fabs_f(fy - 375.0f) < rwm);
+//
+// The region of the point, the very comparisons the general form makes (a NaN coordinate fails both and
+// takes the general form):
+MEV_HD bool road_region_xin(float fx, float rwm) { return fabs_f(fx - 375.0f) < rwm; }
+MEV_HD bool road_region_yin(float fy, float rwm) { return fabs_f(fy - 375.0f) < rwm; }
+// ... and whether the point's truncated pixel is on the 750 px screen (phase 1 skips the safe stretch from
+// the car centre only then): both coordinates in [0, 750) in one unsigned comparison.
+MEV_HD bool road_point_on_screen(float fx, float fy) {
+    const int px = (int)fx, py = (int)fy;
+    const unsigned pmax = (unsigned)px > (unsigned)py ? (unsigned)px : (unsigned)py;
+    return pmax < 750u;
+}
+// xin, yin: road_region_xin(fx, rwm) and road_region_yin(fy, rwm), from the caller and wave-uniform (phase
+// 1's agent pre-pass evaluates them once per agent, one agent per lane, and hands each pass its agent's two
+// bits as scalars, so the beam passes no longer redo them in every lane).
+MEV_HD float road_entry_safe_uniform(float fx, float fy, float dx, float dy, float iadx, float iady, float rwm,
+                                     float ccen, float crf, bool xin, bool yin) {
     if (xin && yin) return road_entry_region<kRegX | kRegY>(fx, fy, dx, dy, iadx, iady, rwm, ccen, crf);
     if (xin) return road_entry_region<kRegX>(fx, fy, dx, dy, iadx, iady, rwm, ccen, crf);
     if (yin) return road_entry_region<kRegY>(fx, fy, dx, dy, iadx, iady, rwm, ccen, crf);
     return road_entry_region<0>(fx, fy, dx, dy, iadx, iady, rwm, ccen, crf);
+}
+// ... and for a caller that has not: the bits derived here, in every lane.  No kernel calls this form any
+// more -- phase 1's pair loop supplies the bits, every other caller of the entry bound takes road_entry_safe;
+// it is kept for the host check tests/native/roadbound_regions_check.cpp, which pins it to the general form.
+MEV_HD float road_entry_safe_uniform(float fx, float fy, float dx, float dy, float idx, float idy, float iadx,
+                                     float iady, float rwm, float ccen, float crf) {
+    (void)idx;
+    (void)idy;
+    return road_entry_safe_uniform(fx, fy, dx, dy, iadx, iady, rwm, ccen, crf, rb_uniform(road_region_xin(fx, rwm)),
+                                   rb_uniform(road_region_yin(fy, rwm)));
 }
 
 }  // namespace mev
