@@ -143,6 +143,10 @@ int mev_set_reward(mev_handle* h, const float* reward8);
  * (Car::update, cpp/Car.cpp:9-40); box = {x, y, heading, length, width}
  * (Car::check_collision, cpp/Car.cpp:86-141). */
 int mev_car_update(float* kin, float throttle, float steer_input, float dt);
+/* y[i] = tanh_c(x[i]) for i < n: the tanh of the rollout policies' activations (mev_policy_create, "THE
+ * ARITHMETIC IS PART OF THE CONTRACT"), the very function the kernels run.  A host helper: no handle, no device.
+ * x == y is allowed.  n < 0, or a null array with n > 0: MEV_E_INVALID. */
+int mev_tanh(const float* x, float* y, int64_t n);
 int mev_car_check_collision(const float* box_a, const float* box_b, int32_t* collide);
 
 /* Lane points / routes (reference cpp/RouteGen.cpp). */
@@ -663,12 +667,20 @@ int mev_update_plans(mev_handle* h, const mev_update_args* args);
  * A policy has one or two hidden layers of 1..MEV_POLICY_MAX_WIDTH units (hidden[1] == 0: one) and an
  * output layer of 2 units (throttle, steer); in_dim must equal the handle's obs_dim.  Layer l's weights
  * are row-major [out][in] (torch.nn.Linear.weight's layout), its biases [out]; with one hidden layer
- * w[2] / b[2] are not read.  flags: MEV_DEVICE_PTRS or 0.  Host pointers: every weight and bias must be
+ * w[2] / b[2] are not read.  flags: MEV_DEVICE_PTRS, and on mev_policy_create the activation bits below.  Host pointers: every weight and bias must be
  * finite (else MEV_E_INVALID) and the call is synchronous.  Device pointers: no validation, no
  * synchronisation -- the library repacks the weights into its own layout with a small kernel on the
  * handle's stream, so a training loop pushes new weights every iteration without a host copy, and a
  * rollout issued before an update on that stream runs the old weights.  mev_policy_update takes a spec of
  * the same shape.  A policy belongs to its handle: mev_destroy releases the handle's policies.
+ *
+ * ACTIVATIONS are a property of the policy, fixed by mev_policy_create's flags: MEV_POLICY_HIDDEN_TANH -- every
+ * hidden layer applies tanh_c (below) in the ReLU's place -- and MEV_POLICY_OUT_TANH -- mu[k] = tanh_c(layer(W_last,
+ * b_last, h)[k]), the squashed mean of DDPG / TD3-style actors.  Without them (flags 0 or MEV_DEVICE_PTRS) the
+ * policy is the ReLU policy with a raw mu, and every call gives it the bits it always gave.  mev_policy_update keeps
+ * the activations: it accepts MEV_DEVICE_PTRS only, an activation bit there is MEV_E_INVALID and the policy is
+ * untouched; any other unknown bit on either call is MEV_E_INVALID.  mev_policy_get_activations reads the two bits
+ * back.  In mev_rollout_policies the activations are each listed policy's own.
  *
  * THE ARITHMETIC IS PART OF THE CONTRACT.  For an observation row x[0..D), D = obs_dim, padding columns
  * included as they stand:
@@ -676,7 +688,44 @@ int mev_update_plans(mev_handle* h, const mev_update_args* args);
  *   layer(W, b, x)[j]: y = b[j]; for k = 0 .. in-1 (ascending): y = fmaf(W[j][k], x[k], y)   (f32, one rounding per k)
  *   relu(y) = y > 0.0f ? y : 0.0f                                                            (NaN and -0.0f give +0.0f)
  *   h1 = relu(layer(W0, b0, x)); h2 = relu(layer(W1, b1, h1)) (skipped with one hidden layer); mu = layer(W_last, b_last, h)
+ *   MEV_POLICY_HIDDEN_TANH: tanh_c in relu's place in h1 and h2.  MEV_POLICY_OUT_TANH: then mu[k] = tanh_c(mu[k]).
+ *   mean_seq holds that mu (the squashed mean), the noise and the clamp below follow unchanged (TD3's exploration
+ *   rule), and the value head (mev_policy_set_value_head) reads h_last after the hidden activation and is never squashed.
  *   action[k] = fminf(fmaxf(sigma ? mu[k] + sigma[k] * eps[k] : mu[k], lo[k]), hi[k])        (multiply, then add: no FMA here)
+ *
+ * tanh_c(y) is a tanh DEFINED AS ARITHMETIC -- no libm or device tanhf / expf, whose last bits differ between
+ * machines -- every operation f32 with one rounding, `/` the correctly rounded divide, fmaf a fused multiply-add
+ * (csrc/mev_act.h is this text as code; mev_tanh runs it on the host):
+ *
+ *   a  = |y|;  ac = a < 10.0f ? a : 10.0f                       (NaN gives 10)
+ *   s  = ac * ac
+ *   q  = fmaf(s, fmaf(s, fmaf(s, fmaf(s, Q4, Q3), Q2), Q1), Q0)
+ *   p  = fmaf(ac * s, q, ac)
+ *   x  = ac + ac;  n = rintf(x * LOG2E)                          (to nearest, ties to even)
+ *   r  = fmaf(-n, LN2_LO, fmaf(-n, LN2_HI, x))
+ *   g  = fmaf(r, fmaf(r, fmaf(r, fmaf(r, G4, G3), G2), G1), G0)
+ *   E  = fmaf(r, fmaf(r, g, 1.0f), 1.0f) * 2^n                   (2^n the float with the bits (n + 127) << 23)
+ *   t  = 1.0f - 2.0f / (E + 1.0f)
+ *   m  = a < 0x1p-12f ? a : a < 0.5625f ? p : t
+ *   tanh_c(y) = y != y ? +0.0f : m with y's sign bit
+ *
+ *   Q0..Q4 = -0x1.555554p-2f, 0x1.110fbap-3f, -0x1.b9915ep-5f, 0x1.5c6c6p-6f, -0x1.abecbp-8f
+ *   LOG2E = 0x1.715476p+0f, LN2_HI = 0x1.62e4p-1f, LN2_LO = 0x1.7f7d1cp-20f
+ *   G0..G4 = 0x1p-1f, 0x1.5554dcp-3f, 0x1.5554e8p-5f, 0x1.120c74p-7f, 0x1.6d445ep-10f
+ *
+ * So tanh_c(-y) has the bits of -tanh_c(y); +-0 and subnormals come back as they are; |tanh_c| <= 1, exactly 1 from
+ * |y| = 9.02 on, +-inf included; NaN gives +0.0f, as the ReLU does; and tanh_c does not decrease across any pair of
+ * adjacent floats.  Measured over EVERY finite float against tanh in double, in ulp of the result: at most 0.333
+ * below 2^-12, 0.814 in the polynomial region, 1.537 in the exponential region (just above 0.5625), 0.500 from 8
+ * on (tests/native/tanh_check.cpp exhaustive; the test suite asserts 1, 1, 2, 1 on a strided sweep).
+ * Measured (python tools/bench_rollout_act.py -> profiles/rollout_act_sweep.json; the method above): 4096
+ * envs x 8 agents x 64 beams, 95-64-64-2, T = 16: the tanh-hidden policy 0.975 ms (0.975-0.977) against 1.413 ms
+ * (1.412-1.419) for an eager torch forward of the Tanh module, a clamp and mev_step per sub-step, and 0.933 ms for the
+ * ReLU policy: 2.6 us per sub-step for 16 tanh_c per lane (47 VALU instructions each; estimated 1.3-5 us); the
+ * output tanh is not measurable.  T = 64: 3.799 against 5.687 ms; 64 envs: 0.582 against 1.407 ms.  All gains beyond
+ * the blocks' spreads.  ReLU policies run their own instantiations: against the parent commit in the same session the
+ * flagship mev_rollout_policy_repeat row ties (0.7835 / 0.7834 ms); the plain call is +0.14 % at T = 16 (beyond the
+ * spreads), a tie at T = 64 and -0.36 % at 64 envs.
  *
  * eps is mev_sample_plans' noise word for word: Philox4x32-10 with key noise_seed and counter
  * (lo32(noise_counter), hi32(noise_counter), e * 64 + i, t) -- the env index e in the candidate's place,
@@ -733,8 +782,12 @@ typedef struct {
     const float* w[3];       /* layer l: row-major [out][in] */
     const float* b[3];       /* [out]; the last used layer has out = 2 (throttle, steer) */
 } mev_policy_spec;
+#define MEV_POLICY_HIDDEN_TANH 0x10u /* mev_policy_create: every hidden layer applies tanh_c, not the ReLU */
+#define MEV_POLICY_OUT_TANH    0x20u /* mev_policy_create: mu[k] = tanh_c(mu[k]) before noise and clamp  */
 int mev_policy_create(mev_handle* h, const mev_policy_spec* spec, uint32_t flags, mev_policy** out);
 int mev_policy_update(mev_policy* p, const mev_policy_spec* spec, uint32_t flags);
+/* *flags = the policy's MEV_POLICY_HIDDEN_TANH | MEV_POLICY_OUT_TANH bits (0: the ReLU policy with a raw mu) */
+int mev_policy_get_activations(const mev_policy* p, uint32_t* flags);
 int mev_policy_destroy(mev_policy* p);
 
 #define MEV_MAX_ROLLOUT 1024

@@ -22,6 +22,8 @@ LIB_PATH = _build.LIB_PATH
 MEV_DEVICE_PTRS = 0x1
 MEV_AUTO_RESET = 0x2
 MEV_GATHER_TO_ROOT = 0x4
+MEV_POLICY_HIDDEN_TANH = 0x10  # mev_policy_create: tanh_c hidden layers
+MEV_POLICY_OUT_TANH = 0x20     # mev_policy_create: mu = tanh_c(mu)
 MEV_COMM_ID_BYTES = 128
 MEV_GATHER_F32 = 0
 MEV_GATHER_LIDAR_U8 = 1
@@ -55,6 +57,7 @@ EXPORTED = (
     "mev_sample_expand_plans", "mev_get_step_row", "mev_policy_create", "mev_policy_update", "mev_policy_destroy",
     "mev_rollout_policy", "mev_get_rollout_row", "mev_policy_set_value_head", "mev_policy_has_value_head",
     "mev_rollout_policy_values", "mev_gae", "mev_rollout_policy_repeat", "mev_rollout_policies",
+    "mev_tanh", "mev_policy_get_activations",
 )
 
 
@@ -316,6 +319,8 @@ def load_library(variant: str = None):
     L.mev_get_rollout_row.argtypes = [_vp, i32p]
     L.mev_policy_set_value_head.argtypes = [_vp, _vp, _vp, ctypes.c_uint32]
     L.mev_policy_has_value_head.argtypes = [_vp, i32p]
+    L.mev_policy_get_activations.argtypes = [_vp, ctypes.POINTER(ctypes.c_uint32)]
+    L.mev_tanh.argtypes = [f32p, f32p, ctypes.c_int64]
     L.mev_rollout_policy_values.argtypes = [_vp, ctypes.POINTER(MevRolloutValuesArgs)]
     L.mev_rollout_policy_repeat.argtypes = [_vp, ctypes.POINTER(MevRolloutRepeatArgs)]
     L.mev_rollout_policies.argtypes = [_vp, ctypes.POINTER(MevRolloutMultiArgs)]
@@ -895,11 +900,13 @@ class Handle:
         _check(self._lib.mev_sample_expand_plans(self._h, ctypes.byref(xa)))
         return out
 
-    def policy(self, weights, biases, device: bool = False) -> "Policy":
+    def policy(self, weights, biases, device: bool = False, hidden: str = "relu", out: str = "linear") -> "Policy":
         """An MLP policy held by the library (mev_policy_create): weights a list of 2 or 3 arrays [out][in]
         (torch.nn.Linear.weight's layout; the first takes obs_dim inputs, the last has 2 outputs), biases
-        the matching [out] arrays.  device=True: device tensors / pointers (then no check, no sync)."""
-        return Policy(self, weights, biases, device)
+        the matching [out] arrays.  device=True: device tensors / pointers (then no check, no sync).
+        hidden: "relu" or "tanh", the activation of every hidden layer; out: "linear" or "tanh", the latter
+        squashing mu before noise and clamp (tanh_c, the library's stated f32 tanh).  Fixed at creation."""
+        return Policy(self, weights, biases, device, hidden=hidden, out=out)
 
     def rollout_row(self) -> int:
         """The row of k_rollout's table rollout_policy runs for this handle (mev_get_rollout_row); -1: unsupported."""
@@ -1482,13 +1489,14 @@ class Policy:
     outputs, kept on the device in the library's own layout.  `update` takes new weights of the same
     shape; Handle.close releases a policy that was not closed."""
 
-    def __init__(self, handle: "Handle", weights, biases, device: bool = False):
+    def __init__(self, handle: "Handle", weights, biases, device: bool = False, hidden: str = "relu",
+                 out: str = "linear"):
         self._handle = handle
         self._ptr = None
         p = _vp()
+        flags = (MEV_DEVICE_PTRS if device else 0) | activation_flags(hidden, out)
         spec, _keep = self._spec(weights, biases, device)
-        _check(handle._lib.mev_policy_create(handle._h, ctypes.byref(spec), MEV_DEVICE_PTRS if device else 0,
-                                             ctypes.byref(p)))
+        _check(handle._lib.mev_policy_create(handle._h, ctypes.byref(spec), flags, ctypes.byref(p)))
         self._ptr = p
 
     def _spec(self, weights, biases, device):
@@ -1553,6 +1561,14 @@ class Policy:
         _check(self._handle._lib.mev_policy_has_value_head(self._p, ctypes.byref(has)))
         return bool(has.value)
 
+    @property
+    def activations(self):
+        """(hidden, out) as given at creation: ("relu" | "tanh", "linear" | "tanh") (mev_policy_get_activations)."""
+        f = ctypes.c_uint32()
+        _check(self._handle._lib.mev_policy_get_activations(self._p, ctypes.byref(f)))
+        return ("tanh" if f.value & MEV_POLICY_HIDDEN_TANH else "relu",
+                "tanh" if f.value & MEV_POLICY_OUT_TANH else "linear")
+
     def close(self):
         if self._ptr is not None and self._handle._h:
             self._handle._lib.mev_policy_destroy(self._ptr)
@@ -1563,6 +1579,25 @@ class Policy:
             self.close()
         except Exception:
             pass
+
+
+def activation_flags(hidden: str = "relu", out: str = "linear") -> int:
+    """mev_policy_create's activation bits for hidden in ("relu", "tanh") and out in ("linear", "tanh")."""
+    if hidden not in ("relu", "tanh"):
+        raise ValueError(f'hidden must be "relu" or "tanh", got {hidden!r}')
+    if out not in ("linear", "tanh"):
+        raise ValueError(f'out must be "linear" or "tanh", got {out!r}')
+    return (MEV_POLICY_HIDDEN_TANH if hidden == "tanh" else 0) | (MEV_POLICY_OUT_TANH if out == "tanh" else 0)
+
+
+def tanh_c(x):
+    """tanh_c of every element (mev_tanh): the rollout policies' tanh, the library's stated f32 arithmetic run on
+    the host -- the same bits as inside the kernels.  Returns a float32 array of x's shape."""
+    a = np.ascontiguousarray(x, np.float32)
+    y = np.empty_like(a)
+    f32p = ctypes.POINTER(ctypes.c_float)
+    _check(load_library().mev_tanh(a.ctypes.data_as(f32p), y.ctypes.data_as(f32p), a.size))
+    return y
 
 
 def car_update(kin, throttle: float, steer: float, dt: float):

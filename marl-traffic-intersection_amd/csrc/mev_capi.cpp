@@ -19,6 +19,7 @@
 #include <thread>
 #include <vector>
 
+#include "mev_act.h"
 #include "mev_kernels.h"
 #include "mev_routes.h"
 #include "mev_world.h"
@@ -760,6 +761,12 @@ int mev_car_update(float* kin, float throttle, float steer_input, float dt) {
     float c, s;
     mev::car_update(k, throttle, steer_input, dt, &c, &s);
     kin[0] = k.x; kin[1] = k.y; kin[2] = k.v; kin[3] = k.h; kin[4] = k.acc; kin[5] = k.steer;
+    return MEV_OK;
+}
+
+int mev_tanh(const float* x, float* y, int64_t n) {
+    if (n < 0 || (n > 0 && (!x || !y))) return fail(MEV_E_INVALID, n < 0 ? "negative count" : "null argument");
+    for (int64_t i = 0; i < n; ++i) y[i] = mev::tanh_c(x[i]);
     return MEV_OK;
 }
 
@@ -1669,11 +1676,21 @@ static int policy_shape(const mev_handle* h, const mev_policy_spec* spec, mev::P
 }
 
 // the spec's weights into the policy's block: staged (host pointers: checked finite first) and repacked on the stream
+// (the activation bits: at creation only, kept by every update)
+static_assert(MEV_POLICY_HIDDEN_TANH == (uint32_t)mev::kPolicyHiddenTanh && MEV_POLICY_OUT_TANH == (uint32_t)mev::kPolicyOutTanh,
+              "the header's activation bits are PolicyNet::act's");
 static int policy_load(mev_policy* p, const mev_policy_spec* spec, uint32_t flags) {
     mev_handle* h = p->h;
-    if (flags & ~MEV_DEVICE_PTRS) return fail(MEV_E_INVALID, "policy flags: MEV_DEVICE_PTRS or 0");
+    constexpr uint32_t kAct = MEV_POLICY_HIDDEN_TANH | MEV_POLICY_OUT_TANH;
+    const bool update = p->net.layers != 0;
+    if (update && (flags & kAct))
+        return fail(MEV_E_INVALID, "mev_policy_update: a policy's activations are fixed at creation (flags: MEV_DEVICE_PTRS or 0)");
+    if (flags & ~(MEV_DEVICE_PTRS | (update ? 0u : kAct)))
+        return fail(MEV_E_INVALID, update ? "policy flags: MEV_DEVICE_PTRS or 0"
+                                          : "policy flags: MEV_DEVICE_PTRS, MEV_POLICY_HIDDEN_TANH, MEV_POLICY_OUT_TANH or 0");
     mev::PolicyNet net{};
     if (int r = policy_shape(h, spec, &net)) return r;
+    net.act = update ? p->net.act : (int32_t)(flags & kAct);
     if (p->net.layers && (net.layers != p->net.layers || memcmp(net.out, p->net.out, sizeof net.out) != 0))
         return fail(MEV_E_INVALID, "mev_policy_update: the spec's shape differs from the policy's");
     const bool dev = (flags & MEV_DEVICE_PTRS) != 0;
@@ -1743,6 +1760,12 @@ int mev_policy_set_value_head(mev_policy* p, const float* wv, const float* bv, u
 int mev_policy_has_value_head(const mev_policy* p, int32_t* has) {
     if (!p || !has) return fail(MEV_E_INVALID, "null argument");
     *has = p->has_value ? 1 : 0;
+    return MEV_OK;
+}
+
+int mev_policy_get_activations(const mev_policy* p, uint32_t* flags) {
+    if (!p || !flags) return fail(MEV_E_INVALID, "null argument");
+    *flags = (uint32_t)p->net.act;
     return MEV_OK;
 }
 

@@ -406,10 +406,16 @@ hipError_t launch_serve(const SimParams& p, const SimParams* dp, const ServeArgs
 // the bias row wt[l][in[l] * ld[l] + j]; ld = out rounded up to 64, the padding zero.  The last
 // used layer has out = 2; column 2 of its block holds the value head (mev_policy_set_value_head: wv[k] in
 // row k, bv[0] in the bias row), zero while none is attached.
+// act: the policy's activations, fixed at creation -- kPolicyHiddenTanh: every hidden layer applies tanh_c
+// (mev_act.h) in the ReLU's place; kPolicyOutTanh: mu = tanh_c(mu) before the noise (never the value head).
+// 0: the ReLU policy, which runs the instantiations without ACT.
+constexpr int32_t kPolicyHiddenTanh = 0x10;  // == MEV_POLICY_HIDDEN_TANH
+constexpr int32_t kPolicyOutTanh = 0x20;     // == MEV_POLICY_OUT_TANH
 struct PolicyNet {
     const float* wt[3];
     int32_t in[3], out[3], ld[3];
     int32_t layers;  // 2 or 3
+    int32_t act;     // kPolicyHiddenTanh | kPolicyOutTanh
 };
 // repack a policy's [out][in] weights and [out] biases (device arrays) into dst (PolicyNet's layout)
 // keep_head: the value head's column is left as it stands

@@ -21,6 +21,7 @@
 #include "mev_nsort.h"
 #include "mev_roadbound.h"
 #include "mev_gae.h"
+#include "mev_act.h"
 
 namespace mev {
 
@@ -4297,8 +4298,13 @@ __device__ __forceinline__ void policy_weights(float (&w)[kPolicyAhead], const _
         w[u] = ldu(wt, (uint32_t)(k * ld) + j);
     }
 }
+// ACT (a flag of k_rollout's instantiation): the layer of a policy whose `act` has kPolicyHiddenTanh stores
+// tanh_c (mev_act.h) of its 8 chains in the ReLU's place -- a wave-uniform choice per policy, so that a ReLU and
+// a tanh policy can share a group under MULTI.  Without ACT the function is what it was.
+template <bool ACT = false>
 __device__ __forceinline__ void policy_hidden(const __attribute__((address_space(1))) float* wt, const int in_w,
-                                              const int out_w, const int ld, const float* x, float* y, const int lane) {
+                                              const int out_w, const int ld, const float* x, float* y, const int lane,
+                                              const bool tanh_h = false) {
     constexpr int U = kPolicyAhead;
     for (int j0 = 0; j0 < out_w; j0 += WAVE) {
         const uint32_t j = (uint32_t)(j0 + lane);  // (< ld: the rows are padded to whole waves)
@@ -4340,6 +4346,18 @@ __device__ __forceinline__ void policy_hidden(const __attribute__((address_space
                 for (int u = 0; u < U; ++u) wc[u] = wn[u];
             }
         }
+        if constexpr (ACT) {
+            if (tanh_h) {  // (wave-uniform)
+                if (j < (uint32_t)out_w) {
+                    float4 r0, r1;  // tanh_c: NaN gives +0.0f
+                    r0.x = tanh_c(acc[0]); r0.y = tanh_c(acc[1]); r0.z = tanh_c(acc[2]); r0.w = tanh_c(acc[3]);
+                    r1.x = tanh_c(acc[4]); r1.y = tanh_c(acc[5]); r1.z = tanh_c(acc[6]); r1.w = tanh_c(acc[7]);
+                    *reinterpret_cast<float4*>(y + j * kPolicyGroup) = r0;
+                    *reinterpret_cast<float4*>(y + j * kPolicyGroup + 4) = r1;
+                }
+                continue;
+            }
+        }
         if (j < (uint32_t)out_w) {
             float4 r0, r1;  // relu: NaN and -0.0f give +0.0f
             r0.x = acc[0] > 0.0f ? acc[0] : 0.0f; r0.y = acc[1] > 0.0f ? acc[1] : 0.0f;
@@ -4363,7 +4381,9 @@ __device__ __forceinline__ void policy_hidden(const __attribute__((address_space
 // layer's block (k_value_head_repack), stored to value_row at [e][i]; the fourth lane repeats column 2 and
 // stores nothing.  With step == false (the bootstrap row T: no sub-step follows) no noise word is drawn
 // and only the value is stored.
-template <bool VALUE>
+// ACT: the policy's activations are read (PolicyNet::act) -- the hidden layers' rule above, and with kPolicyOutTanh
+// mu = tanh_c(mu) on the lanes of the two action components, before the noise; the value lane is never squashed.
+template <bool VALUE, bool ACT = false>
 __device__ __forceinline__ void policy_phase(const RolloutArgs& ra, const float* obs, const int ld, float* act_row,
                                              float* mean_row, float* value_row, const bool step, const int e,
                                              const int N, const int D, const int t, float* scratch, const int lane) {
@@ -4398,11 +4418,12 @@ __device__ __forceinline__ void policy_phase(const RolloutArgs& ra, const float*
             }
         }
         wave_lds_sync();
-        policy_hidden(gmem(net.wt[0]), net.in[0], net.out[0], net.ld[0], xs, h1, lane);
+        const bool tanh_h = ACT && (net.act & kPolicyHiddenTanh) != 0;
+        policy_hidden<ACT>(gmem(net.wt[0]), net.in[0], net.out[0], net.ld[0], xs, h1, lane, tanh_h);
         wave_lds_sync();
         const float* hl = h1;
         if (L == 3) {
-            policy_hidden(gmem(net.wt[1]), net.in[1], net.out[1], net.ld[1], h1, h2, lane);
+            policy_hidden<ACT>(gmem(net.wt[1]), net.in[1], net.out[1], net.ld[1], h1, h2, lane, tanh_h);
             wave_lds_sync();
             hl = h2;
         }
@@ -4431,6 +4452,10 @@ __device__ __forceinline__ void policy_phase(const RolloutArgs& ra, const float*
                 for (int u = 0; u < U; ++u) wc[u] = wn[u];
             }
         }
+        if constexpr (ACT) {
+            const float sq = tanh_c(mu);
+            if ((net.act & kPolicyOutTanh) != 0 && (!VALUE || (lane & 3) < 2)) mu = sq;
+        }
         const int i = a0 + al;
         float x = mu;
         if (ra.noisy && (!VALUE || step)) {
@@ -4458,7 +4483,7 @@ __device__ __forceinline__ void policy_phase(const RolloutArgs& ra, const float*
 // VALUE: 105 -> 123 spilt VGPRs) -- so its per-group part is restated here as policy_pass, taking the net, the
 // sigma row and a per-lane `mine`: the same chains with the same operands in the same order, and only the
 // lanes with `mine` store.
-template <bool VALUE>
+template <bool VALUE, bool ACT = false>
 __device__ __forceinline__ void policy_pass(const RolloutMultiArgs& ra, const PolicyNet& net, const float* sigma,
                                             const bool mine, const float* xs, float* h1, const int a0, const int G,
                                             float* act_row, float* mean_row, float* value_row, const bool step,
@@ -4466,11 +4491,12 @@ __device__ __forceinline__ void policy_pass(const RolloutMultiArgs& ra, const Po
     constexpr int U = kPolicyAhead;
     const int L = net.layers;
     float* h2 = h1 + (size_t)net.out[0] * kPolicyGroup;   // [out[1]][8] (three layers)
-    policy_hidden(gmem(net.wt[0]), net.in[0], net.out[0], net.ld[0], xs, h1, lane);
+    const bool tanh_h = ACT && (net.act & kPolicyHiddenTanh) != 0;  // this policy's own rule
+    policy_hidden<ACT>(gmem(net.wt[0]), net.in[0], net.out[0], net.ld[0], xs, h1, lane, tanh_h);
     wave_lds_sync();
     const float* hl = h1;
     if (L == 3) {
-        policy_hidden(gmem(net.wt[1]), net.in[1], net.out[1], net.ld[1], h1, h2, lane);
+        policy_hidden<ACT>(gmem(net.wt[1]), net.in[1], net.out[1], net.ld[1], h1, h2, lane, tanh_h);
         wave_lds_sync();
         hl = h2;
     }
@@ -4499,6 +4525,10 @@ __device__ __forceinline__ void policy_pass(const RolloutMultiArgs& ra, const Po
             for (int u = 0; u < U; ++u) wc[u] = wn[u];
         }
     }
+    if constexpr (ACT) {
+        const float sq = tanh_c(mu);
+        if ((net.act & kPolicyOutTanh) != 0 && (!VALUE || (lane & 3) < 2)) mu = sq;
+    }
     const int i = a0 + al;
     float x = mu;
     if (ra.noisy && (!VALUE || step)) {
@@ -4525,7 +4555,7 @@ __device__ __forceinline__ void policy_pass(const RolloutMultiArgs& ra, const Po
 // agents -- and only the lanes whose agent has p store, with sigma row p.  A policy that no agent of the group
 // has costs one ballot.  h1 / h2 are reused: a wave_lds_sync() between one policy's output layer and the next
 // one's hidden layers.  The table index p is the loop's: within [0, P) whatever `assign` holds.
-template <bool VALUE>
+template <bool VALUE, bool ACT = false>
 __device__ __forceinline__ void policy_phase_multi(const RolloutMultiArgs& ra, const float* obs, const int ld,
                                                    float* act_row, float* mean_row, float* value_row, const bool step,
                                                    const int e, const int N, const int D, const int t, float* scratch,
@@ -4567,7 +4597,7 @@ __device__ __forceinline__ void policy_phase_multi(const RolloutMultiArgs& ra, c
             if (ballot(on && pl == p) == 0) continue;  // no agent of the group has p
             if (again) wave_lds_sync();
             again = true;
-            policy_pass<VALUE>(ra, ra.nets[p], ra.sigmas[p], pl == p, xs, h1, a0, G, act_row, mean_row, value_row, step,
+            policy_pass<VALUE, ACT>(ra, ra.nets[p], ra.sigmas[p], pl == p, xs, h1, a0, G, act_row, mean_row, value_row, step,
                                e, N, t, lane);
         }
     }
@@ -4597,10 +4627,14 @@ __device__ __forceinline__ void policy_phase_multi(const RolloutMultiArgs& ra, c
 // MULTI (mev_rollout_policies): the REPEAT loop with policy_phase_multi in policy_phase's place -- a policy per
 // agent slot from the table of RolloutMultiArgs, a further derived type -- and nothing else changed: repeat == 1 through the flat
 // loop is the plain call's bits (3.2l), so there is no MULTI form of the plain loop.
+// ACT: the policy phases read the policies' activations (tanh_c hidden layers, a tanh_c on mu).  A flag of the
+// instantiation again, chosen by the host where a policy of the call has an activation bit: the calls of ReLU
+// policies run the instantiations they ran before, instruction for instruction.
 template <bool REPEAT, bool MULTI>
 using RolloutKernArgs =
     typename std::conditional<MULTI, RolloutMultiArgs, typename std::conditional<REPEAT, RolloutRepeatArgs, RolloutArgs>::type>::type;
-template <bool TRAFFIC, bool TAB, int NM, int KM, int RP1, int RNC, bool VALUE, bool REPEAT = false, bool MULTI = false>
+template <bool TRAFFIC, bool TAB, int NM, int KM, int RP1, int RNC, bool VALUE, bool REPEAT = false, bool MULTI = false,
+          bool ACT = false>
 __global__ __launch_bounds__(WAVE, 4) void k_rollout(const SimParams* __restrict__ pp, RolloutKernArgs<REPEAT, MULTI> ra,
                                                      Outputs out0) {
     static_assert(!MULTI || REPEAT, "a policy per agent slot: the flat loop only");
@@ -4636,10 +4670,10 @@ __global__ __launch_bounds__(WAVE, 4) void k_rollout(const SimParams* __restrict
                 float* mean_row = ra.mean_seq ? ra.mean_seq + (size_t)t * EN * 2 : nullptr;
                 __builtin_amdgcn_s_setprio(kPrioCars);
                 if constexpr (MULTI)
-                    policy_phase_multi<VALUE>(ra, obs, obs_ld, act_row, mean_row, VALUE ? ra.value_seq + (size_t)t * EN : nullptr,
+                    policy_phase_multi<VALUE, ACT>(ra, obs, obs_ld, act_row, mean_row, VALUE ? ra.value_seq + (size_t)t * EN : nullptr,
                                               !VALUE || t < ra.T, env, N, D, t, scratch, lane);
                 else
-                    policy_phase<VALUE>(ra, obs, obs_ld, act_row, mean_row, VALUE ? ra.value_seq + (size_t)t * EN : nullptr,
+                    policy_phase<VALUE, ACT>(ra, obs, obs_ld, act_row, mean_row, VALUE ? ra.value_seq + (size_t)t * EN : nullptr,
                                         !VALUE || t < ra.T, env, N, D, t, scratch, lane);
                 if (VALUE && t == ra.T) break;  // (the bootstrap row: no sub-step follows)
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
@@ -4704,7 +4738,7 @@ __global__ __launch_bounds__(WAVE, 4) void k_rollout(const SimParams* __restrict
         float* act_row = ra.actions_seq ? ra.actions_seq + (size_t)t * EN * 2 : ra.act_scratch;
         float* mean_row = ra.mean_seq ? ra.mean_seq + (size_t)t * EN * 2 : nullptr;
         __builtin_amdgcn_s_setprio(kPrioCars);
-        policy_phase<VALUE>(ra, obs, obs_ld, act_row, mean_row, VALUE ? ra.value_seq + (size_t)t * EN : nullptr,
+        policy_phase<VALUE, ACT>(ra, obs, obs_ld, act_row, mean_row, VALUE ? ra.value_seq + (size_t)t * EN : nullptr,
                             !VALUE || t < ra.T, env, N, D, t, scratch, lane);
         if (VALUE && t == ra.T) break;  // (the bootstrap row: no sub-step follows)
         // the actions this wave wrote, read back by its own lanes in the body; the scratch is the body's again
@@ -4983,21 +5017,22 @@ hipError_t launch_step_window(const SimParams& p, const StepInputs& in, const Ou
     return launch_part(p, in, out, 0, p.E, s, nullptr, &w);
 }
 
-// k_rollout's instantiations in the order of MEV_ROLLOUT_KERNELS (mev_plan.h): kRolloutFns[row][!TAB][VALUE], and
-// those with REPEAT -- the same rows, their own argument type -- in kRolloutRepeatFns[row][!TAB][VALUE]
+// k_rollout's instantiations in the order of MEV_ROLLOUT_KERNELS (mev_plan.h): kRolloutFns[row][!TAB][VALUE][ACT], and
+// those with REPEAT -- the same rows, their own argument type -- in kRolloutRepeatFns[row][!TAB][VALUE][ACT]
+#define MEV_ROLLOUT_ACT(...) {k_rollout<__VA_ARGS__, false>, k_rollout<__VA_ARGS__, true>}
 using RolloutFn = void (*)(const SimParams*, RolloutArgs, Outputs);
 #define MEV_ROLLOUT_FNS(T, NM, KM, P1, NC)                                                   \
-    {{k_rollout<T, true, NM, KM, P1, NC, false>, k_rollout<T, true, NM, KM, P1, NC, true>},   \
-     {k_rollout<T, false, NM, KM, P1, NC, false>, k_rollout<T, false, NM, KM, P1, NC, true>}},
-static const RolloutFn kRolloutFns[][2][2] = {MEV_ROLLOUT_KERNELS(MEV_ROLLOUT_FNS)};
+    {{MEV_ROLLOUT_ACT(T, true, NM, KM, P1, NC, false, false, false), MEV_ROLLOUT_ACT(T, true, NM, KM, P1, NC, true, false, false)},   \
+     {MEV_ROLLOUT_ACT(T, false, NM, KM, P1, NC, false, false, false), MEV_ROLLOUT_ACT(T, false, NM, KM, P1, NC, true, false, false)}},
+static const RolloutFn kRolloutFns[][2][2][2] = {MEV_ROLLOUT_KERNELS(MEV_ROLLOUT_FNS)};
 #undef MEV_ROLLOUT_FNS
 static_assert(sizeof kRolloutFns / sizeof kRolloutFns[0] == kRolloutRows, "one kernel pair per rollout row");
 
 using RolloutRepeatFn = void (*)(const SimParams*, RolloutRepeatArgs, Outputs);
 #define MEV_ROLLOUT_REPEAT_FNS(T, NM, KM, P1, NC)                                                          \
-    {{k_rollout<T, true, NM, KM, P1, NC, false, true>, k_rollout<T, true, NM, KM, P1, NC, true, true>},   \
-     {k_rollout<T, false, NM, KM, P1, NC, false, true>, k_rollout<T, false, NM, KM, P1, NC, true, true>}},
-static const RolloutRepeatFn kRolloutRepeatFns[][2][2] = {MEV_ROLLOUT_KERNELS(MEV_ROLLOUT_REPEAT_FNS)};
+    {{MEV_ROLLOUT_ACT(T, true, NM, KM, P1, NC, false, true, false), MEV_ROLLOUT_ACT(T, true, NM, KM, P1, NC, true, true, false)},   \
+     {MEV_ROLLOUT_ACT(T, false, NM, KM, P1, NC, false, true, false), MEV_ROLLOUT_ACT(T, false, NM, KM, P1, NC, true, true, false)}},
+static const RolloutRepeatFn kRolloutRepeatFns[][2][2][2] = {MEV_ROLLOUT_KERNELS(MEV_ROLLOUT_REPEAT_FNS)};
 #undef MEV_ROLLOUT_REPEAT_FNS
 static_assert(sizeof kRolloutRepeatFns / sizeof kRolloutRepeatFns[0] == kRolloutRows, "one kernel pair per rollout row");
 static_assert(std::is_base_of<RolloutArgs, RolloutRepeatArgs>::value && std::is_trivially_copyable<RolloutRepeatArgs>::value,
@@ -5006,7 +5041,7 @@ static_assert(std::is_base_of<RolloutArgs, RolloutRepeatArgs>::value && std::is_
 hipError_t launch_rollout_repeat(const SimParams& p, const SimParams* dp, const RolloutPlan& rp,
                                  const RolloutRepeatArgs& ra, const Outputs& out, hipStream_t s) {
     if (rp.row < 0 || rp.row >= kRolloutRows || ra.T < 1 || ra.repeat < 1) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(kRolloutRepeatFns[rp.row][!p.dist_tab][ra.value_seq != nullptr], dim3(rp.grid), dim3(rp.block), rp.lds,
+    hipLaunchKernelGGL(kRolloutRepeatFns[rp.row][!p.dist_tab][ra.value_seq != nullptr][ra.net.act != 0], dim3(rp.grid), dim3(rp.block), rp.lds,
                        s, dp, ra, out);
     return hipGetLastError();
 }
@@ -5014,9 +5049,9 @@ hipError_t launch_rollout_repeat(const SimParams& p, const SimParams* dp, const 
 // ... and those with MULTI, on the REPEAT loop: kRolloutMultiFns[row][!TAB][VALUE]
 using RolloutMultiFn = void (*)(const SimParams*, RolloutMultiArgs, Outputs);
 #define MEV_ROLLOUT_MULTI_FNS(T, NM, KM, P1, NC)                                                                      \
-    {{k_rollout<T, true, NM, KM, P1, NC, false, true, true>, k_rollout<T, true, NM, KM, P1, NC, true, true, true>},   \
-     {k_rollout<T, false, NM, KM, P1, NC, false, true, true>, k_rollout<T, false, NM, KM, P1, NC, true, true, true>}},
-static const RolloutMultiFn kRolloutMultiFns[][2][2] = {MEV_ROLLOUT_KERNELS(MEV_ROLLOUT_MULTI_FNS)};
+    {{MEV_ROLLOUT_ACT(T, true, NM, KM, P1, NC, false, true, true), MEV_ROLLOUT_ACT(T, true, NM, KM, P1, NC, true, true, true)},   \
+     {MEV_ROLLOUT_ACT(T, false, NM, KM, P1, NC, false, true, true), MEV_ROLLOUT_ACT(T, false, NM, KM, P1, NC, true, true, true)}},
+static const RolloutMultiFn kRolloutMultiFns[][2][2][2] = {MEV_ROLLOUT_KERNELS(MEV_ROLLOUT_MULTI_FNS)};
 #undef MEV_ROLLOUT_MULTI_FNS
 static_assert(sizeof kRolloutMultiFns / sizeof kRolloutMultiFns[0] == kRolloutRows, "one kernel pair per rollout row");
 static_assert(std::is_base_of<RolloutRepeatArgs, RolloutMultiArgs>::value && std::is_trivially_copyable<RolloutMultiArgs>::value,
@@ -5027,7 +5062,9 @@ hipError_t launch_rollout_multi(const SimParams& p, const SimParams* dp, const R
     if (rp.row < 0 || rp.row >= kRolloutRows || ra.T < 1 || ra.repeat < 1 || ra.P < 1 || ra.P > kMaxRolloutPolicies ||
         !ra.assign)
         return hipErrorInvalidValue;
-    hipLaunchKernelGGL(kRolloutMultiFns[rp.row][!p.dist_tab][ra.value_seq != nullptr], dim3(rp.grid), dim3(rp.block), rp.lds,
+    bool act = false;  // a listed policy with an activation bit: the ACT instantiation, for the whole call
+    for (int q = 0; q < ra.P; ++q) act = act || ra.nets[q].act != 0;
+    hipLaunchKernelGGL(kRolloutMultiFns[rp.row][!p.dist_tab][ra.value_seq != nullptr][act], dim3(rp.grid), dim3(rp.block), rp.lds,
                        s, dp, ra, out);
     return hipGetLastError();
 }
@@ -5035,7 +5072,7 @@ hipError_t launch_rollout_multi(const SimParams& p, const SimParams* dp, const R
 hipError_t launch_rollout(const SimParams& p, const SimParams* dp, const RolloutPlan& rp, const RolloutArgs& ra,
                           const Outputs& out, hipStream_t s) {
     if (rp.row < 0 || rp.row >= kRolloutRows || ra.T < 1) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(kRolloutFns[rp.row][!p.dist_tab][ra.value_seq != nullptr], dim3(rp.grid), dim3(rp.block), rp.lds, s, dp, ra, out);
+    hipLaunchKernelGGL(kRolloutFns[rp.row][!p.dist_tab][ra.value_seq != nullptr][ra.net.act != 0], dim3(rp.grid), dim3(rp.block), rp.lds, s, dp, ra, out);
     return hipGetLastError();
 }
 

@@ -392,17 +392,39 @@ class VecIntersectionEnv:
         return dict(o, actions_out=ao)
 
     @staticmethod
+    def _policy_activations(module):
+        """(hidden, out) of an nn.Sequential(Linear, A, Linear[, A, Linear][, Tanh]): A is ReLU or Tanh, the same
+        at every hidden layer -> "relu" | "tanh"; a trailing Tanh is the output activation -> "tanh", else
+        "linear".  ValueError for any other module, and for Sequential(Linear, Tanh, Linear) -- one tanh hidden
+        layer and a raw mean -- which make_policy has always refused and takes as arrays with hidden="tanh"."""
+        layers = list(module.children())
+        names = [type(x).__name__ for x in layers]
+        out = "linear"
+        if len(layers) in (4, 6) and names[-1] == "Tanh":
+            out, layers, names = "tanh", layers[:-1], names[:-1]
+        shape = "nn.Sequential(Linear, A, Linear[, A, Linear][, Tanh]) with biases, A = ReLU or Tanh"
+        if not (len(layers) in (3, 5) and all(n == "Linear" and x.bias is not None for n, x in zip(names[0::2], layers[0::2]))
+                and all(n in ("ReLU", "Tanh") for n in names[1::2])):
+            raise ValueError(f"a policy module is {shape}")
+        if len(set(names[1::2])) != 1:
+            raise ValueError(f"a policy module is {shape}: the hidden activation A must be the same at every hidden "
+                             f"layer, got {names[1::2]}")
+        hidden = "tanh" if names[1] == "Tanh" else "relu"
+        if hidden == "tanh" and out == "linear" and len(layers) == 3:
+            # Sequential(Linear, Tanh, Linear) was refused before tanh policies existed, and that refusal is part of
+            # what callers and the suite rely on (a module that is silently not the ReLU network it was taken for)
+            raise ValueError("nn.Sequential(Linear, Tanh, Linear) is not taken from a module: pass its arrays, "
+                             'make_policy((weights, biases), hidden="tanh")')
+        return hidden, out
+
+    @staticmethod
     def _policy_arrays(module_or_arrays):
-        """(weights, biases) of an nn.Sequential(Linear, ReLU, Linear[, ReLU, Linear]) -- its parameters'
-        own tensors -- or of a (weights, biases) pair of array lists."""
+        """(weights, biases) of an nn.Sequential(Linear, A, Linear[, A, Linear][, Tanh]) (_policy_activations) --
+        its parameters' own tensors -- or of a (weights, biases) pair of array lists."""
         m = module_or_arrays
         if hasattr(m, "children"):
-            layers = list(m.children())
-            lin = layers[0::2]
-            ok = (len(layers) in (3, 5) and all(type(x).__name__ == "Linear" and x.bias is not None for x in lin)
-                  and all(type(x).__name__ == "ReLU" for x in layers[1::2]))
-            if not ok:
-                raise ValueError("a policy module is nn.Sequential(Linear, ReLU, Linear[, ReLU, Linear]) with biases")
+            VecIntersectionEnv._policy_activations(m)
+            lin = [x for x in m.children() if type(x).__name__ == "Linear"]
             return [x.weight for x in lin], [x.bias for x in lin]
         weights, biases = m
         return list(weights), list(biases)
@@ -430,20 +452,33 @@ class VecIntersectionEnv:
         dev = lambda x: self._dev_tensor(x.detach() if hasattr(x, "detach") else x, t.float32)
         return dev(w), dev(b), True
 
-    def make_policy(self, module_or_arrays, value=None):
-        """An MLP policy on the device (Handle.policy) from an nn.Sequential(Linear, ReLU, Linear[, ReLU,
-        Linear]) or a (weights, biases) pair of array lists ([out][in] and [out]; the last layer has 2
-        outputs: throttle, steer).  value: a critic head on the same trunk, nn.Linear(H_last, 1) or a (w, b)
+    def make_policy(self, module_or_arrays, value=None, hidden=None, out=None):
+        """An MLP policy on the device (Handle.policy) from an nn.Sequential(Linear, A, Linear[, A, Linear][,
+        Tanh]) or a (weights, biases) pair of array lists ([out][in] and [out]; the last layer has 2
+        outputs: throttle, steer).  A is nn.ReLU or nn.Tanh, the same at every hidden layer (the stock 64-64 tanh
+        PPO actor); a trailing nn.Tanh squashes the mean before noise and clamp (DDPG / TD3 actors).  The tanh is
+        tanh_c, the library's stated f32 tanh (_capi.tanh_c), within 2 ulp of the exact one.  One shape is not taken
+        from a module, as before: Sequential(Linear, Tanh, Linear) -- pass its arrays with hidden="tanh".  With arrays the
+        keywords hidden ("relu" | "tanh") and out ("linear" | "tanh") say the same; with a module they must agree
+        with it where given.  The activations are fixed at creation: refresh keeps them.  value: a critic head on the same trunk, nn.Linear(H_last, 1) or a (w, b)
         pair ([H_last] or [1][H_last], and [1]); `rollout` can then return value_seq.
         `policy.refresh(module_or_arrays, value)` pushes new weights of the same shape, the head's included.
         torch backend: the weights are read on the current stream by a small kernel, no host copy, no sync."""
+        if hasattr(module_or_arrays, "children"):
+            mh, mo = self._policy_activations(module_or_arrays)
+            if hidden not in (None, mh) or out not in (None, mo):
+                raise ValueError(f"the module's activations are hidden={mh!r}, out={mo!r}; got hidden={hidden!r}, out={out!r}")
+            hidden, out = mh, mo
+        hidden, out = hidden or "relu", out or "linear"
         w, b, device = self._policy_inputs(module_or_arrays)
-        pol = self._h.policy(w, b, device=device)
+        pol = self._h.policy(w, b, device=device, hidden=hidden, out=out)
         if value is not None:
             vw, vb, device = self._value_inputs(value)
             pol.set_value_head(vw, vb, device=device)
 
         def refresh(source=module_or_arrays, value=value):
+            if hasattr(source, "children") and self._policy_activations(source) != (hidden, out):
+                raise ValueError(f"refresh: the policy's activations are fixed at creation (hidden={hidden!r}, out={out!r})")
             w, b, device = self._policy_inputs(source)
             pol.update(w, b, device=device)
             if value is not None:
